@@ -32,9 +32,9 @@ for step in "$@"; do
     hang:*) # a test suspected of hanging: per-test timeout with a dump of every thread's stack (faulthandler), then exit
       timeout 400 python -X faulthandler -m pytest tests -m gpu -q -x --timeout 150 --timeout-method thread -k "${step#hang:}" > "$OUT/pytest_hang.log" 2>&1; tail -120 "$OUT/pytest_hang.log" | cut -c1-220 ;;
     tests:*) ( time timeout 1200 python -m pytest tests -m gpu -q --maxfail=15 --timeout 420 --timeout-method signal -k "${step#tests:}" >> "$OUT/pytest_focus.log" 2>&1 ) 2>&1 | grep real; tail -15 "$OUT/pytest_focus.log" ;;
-    bench) ( time timeout 900 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2>&1 | grep real; tail -c 6000 "$OUT/bench_default.json"; tail -5 "$OUT/bench_default.err" ;;
-    bench_c128) timeout 300 python bench.py --dtype c128 --steps 10 --warmup 3 --no-cpu-baseline --no-extra > "$OUT/bench_c128.json" 2>/dev/null; cut -c1-400 "$OUT/bench_c128.json" ;;
-    bench1) ( time timeout 900 python bench.py --force-distributed --distributed-extras --no-cpu-baseline --kDisplayTimings > "$OUT/bench_one_rank.json" 2> "$OUT/bench_one_rank.err" ) 2>&1 | grep real; echo "rc=$?"; tail -c 5000 "$OUT/bench_one_rank.json"; grep -v "^$" "$OUT/bench_one_rank.err" | tail -40 ;;
+    bench) ( time timeout 900 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" ) 2>&1 | grep real; tail -c 6000 "$OUT/bench_default.json"; tail -5 "$OUT/bench_default.err" ;;
+    bench_c128) timeout 300 python bench.py --full --dtype c128 --steps 10 --warmup 3 --no-cpu-baseline --no-extra > "$OUT/bench_c128.json" 2>/dev/null; cut -c1-400 "$OUT/bench_c128.json" ;;
+    bench1) ( time timeout 900 python bench.py --full --force-distributed --distributed-extras --no-cpu-baseline --kDisplayTimings > "$OUT/bench_one_rank.json" 2> "$OUT/bench_one_rank.err" ) 2>&1 | grep real; echo "rc=$?"; tail -c 5000 "$OUT/bench_one_rank.json"; grep -v "^$" "$OUT/bench_one_rank.err" | tail -40 ;;
     packets|packets:*) # packet path A/B on one device, P logical partitions: sorted streams (default) | pre-indexed + atomics | state-carrying + atomics
       variants="${step#packets}"; variants="${variants#:}"; [ -z "$variants" ] && variants="streams indexed states"
       for v in $variants; do
@@ -47,7 +47,7 @@ for step in "$@"; do
       WITH_MEM=1 CMD="python $GRAFT_REPO_ROOT/scripts/tile_bench.py --L 28 --P 8 --steps 3" bash scripts/gpu_profile_cmd.sh "${TAG}_packets" > "$OUT/packets_prof.log" 2>&1
       grep -E "k_tile|k_scatter|k_window|k_diag" "gpurun_out/prof_${TAG}_packets/summary.txt" | cut -c1-200 | head -30 ;;
     bench1p) # one RCCL rank through the C host's packet path only (chain_32: every packet is an own-partition packet)
-      ( time timeout 600 python bench.py --force-distributed --exchange packets --no-cpu-baseline --no-extra --steps 5 --warmup 2 --kDisplayTimings > "$OUT/bench_one_rank_packets.json" 2> "$OUT/bench_one_rank_packets.err" ) 2>&1 | grep real; echo "rc=$?"; tail -c 3000 "$OUT/bench_one_rank_packets.json"; grep -v "^$" "$OUT/bench_one_rank_packets.err" | tail -25 ;;
+      ( time timeout 600 python bench.py --full --force-distributed --exchange packets --no-cpu-baseline --no-extra --steps 5 --warmup 2 --kDisplayTimings > "$OUT/bench_one_rank_packets.json" 2> "$OUT/bench_one_rank_packets.err" ) 2>&1 | grep real; echo "rc=$?"; tail -c 3000 "$OUT/bench_one_rank_packets.json"; grep -v "^$" "$OUT/bench_one_rank_packets.err" | tail -25 ;;
     lattice) # the reference's benchmark model: K4 mode 5 (factorised point group) against mode 4 (one network per coset), same box
       for k4 in default cosets; do
         for m in heisenberg_square_6x6 heisenberg_square_4x4; do

@@ -7,7 +7,7 @@ MODEL=${MODEL:-heisenberg_chain_32}; DTYPE=${DTYPE:-f64}; TAG=${TAG:-pmc}; MODE=
 ROOT=$GRAFT_REPO_ROOT
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
-CMD="python $ROOT/bench.py --model $MODEL --dtype $DTYPE --mode $MODE --steps 4 --warmup 2 --no-cpu-baseline --no-extra"
+CMD="python $ROOT/bench.py --model $MODEL --dtype $DTYPE --mode $MODE --steps 4 --warmup 2 --full --no-cpu-baseline --no-extra"
 cd /tmp
 timeout -k 5 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $CMD > $OUT/trace.log 2>&1
 timeout -k 5 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pmc -- $CMD > $OUT/pmc_fetch.log 2>&1

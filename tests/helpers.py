@@ -24,6 +24,17 @@ def golden():
         return json.load(f)
 
 
+# the reference's model inputs (its data/*.yaml) and facts read from its build files, recorded by
+# tests/golden/make_reference_fixtures.py
+REFERENCE_DATA = os.path.join(HERE, "golden", "data")
+
+
+@functools.lru_cache(maxsize=None)
+def reference_facts():
+    with open(os.path.join(HERE, "golden", "reference.json"), encoding="utf-8") as f:
+        return json.load(f)
+
+
 @functools.lru_cache(maxsize=None)
 def golden_vectors():
     return np.load(os.path.join(HERE, "golden", "vectors.npz"))

@@ -132,7 +132,7 @@ def test_default_cpu_sample_and_model_config_need_no_reference_tree():
 
 
 def test_cpu_baseline_legs_on_small_samples():
-    """the `cpu_baseline` objects of the default run (the oracle timed on the host cores; the only place outside tests/ and smoke()
+    """the `cpu_baseline` objects of the --full run (the oracle timed on the host cores; the only place outside tests/ and smoke()
     that may call oracle/): both legs on samples that take a second -- they must produce a positive rate, say what the sample was,
     and label a scaled figure as scaled"""
     from oracle import c_oracle as CO
@@ -151,3 +151,37 @@ def test_cpu_baseline_legs_on_small_samples():
     for obj in (measured, scaled):
         obj.pop("probe", None)
         json.dumps(obj)
+
+
+def test_dump_outputs_is_a_fixed_float64_sample(tmp_path):
+    """--dump-outputs: float64 files only, the same positions in every run, the values at those positions, < 64 MB in all"""
+    import numpy as np
+    import torch
+
+    n = 3 * bench.DUMP_SAMPLE
+    y = torch.from_numpy(np.random.RandomState(1).rand(n))
+    bench.dump_outputs(str(tmp_path / "a"), "y", y)
+    bench.dump_outputs(str(tmp_path / "b"), "y", y)
+    idx, val = (np.load(str(tmp_path / "a" / f)) for f in ("y_index.npy", "y.npy"))
+    assert idx.dtype == val.dtype == np.float64 and len(idx) == len(val) <= bench.DUMP_SAMPLE
+    assert np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(val, y.numpy()[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(str(tmp_path / "b" / "y_index.npy")))
+    yc = torch.complex(y, -y)  # c128: real and imaginary part, the largest dump there is
+    bench.dump_outputs(str(tmp_path / "c"), "y", yc)
+    files = sorted(os.listdir(str(tmp_path / "c")))
+    assert files == ["y_imag.npy", "y_index.npy", "y_real.npy"]
+    assert np.array_equal(np.load(str(tmp_path / "c" / "y_imag.npy")), -np.load(str(tmp_path / "c" / "y_real.npy")))
+    assert sum(os.path.getsize(str(tmp_path / "c" / f)) for f in files) < 64e6
+    small = torch.arange(10, dtype=torch.float64)  # short vectors: whole
+    bench.dump_outputs(str(tmp_path / "d"), "y", small)
+    assert sorted(os.listdir(str(tmp_path / "d"))) == ["y.npy"]
+    assert np.array_equal(np.load(str(tmp_path / "d" / "y.npy")), small.numpy())
+
+
+def test_inject_fault_needs_full():
+    """the fault-injection hook tests the parity checks, which only --full runs: without it the benchmark refuses at once"""
+    import subprocess
+
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--inject-fault"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--full" in p.stderr

@@ -269,7 +269,7 @@ def _run_bench(*extra):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-distributed", "--model", "heisenberg_chain_24",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra", *extra],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra", *extra],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert lines, p.stderr[-2000:]
@@ -308,7 +308,7 @@ def _run_bench_one_gpu(*extra, model="heisenberg_chain_24"):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", model, "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert lines, p.stderr[-2000:]
     return p.returncode, json.loads(lines[-1]), p.stderr

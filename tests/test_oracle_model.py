@@ -4,7 +4,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import SMALL_MODELS, golden, golden_vectors, model_config, oracle_for, oracle_reps
+from helpers import REFERENCE_DATA, SMALL_MODELS, golden, golden_vectors, model_config, oracle_for, oracle_reps
 from oracle import c_oracle as CO
 from oracle import model as M
 
@@ -44,14 +44,13 @@ def test_v1_representative_fixture():
     assert list(CO.COracle(m).enumerate()) == want
 
 
-def test_generated_chain_configs_equal_reference_yaml(have_reference):
-    if not have_reference:
-        pytest.skip("reference not mounted")
+def test_generated_chain_configs_equal_reference_yaml():
     import yaml
 
     for L, symm in [(10, False), (24, False), (32, False), (24, True), (36, True), (40, True)]:
         name = f"heisenberg_chain_{L}" + ("_symm" if symm else "")
-        ref = yaml.safe_load(open(f"/root/reference/data/{name}.yaml", encoding="utf-8"))
+        with open(os.path.join(REFERENCE_DATA, f"{name}.yaml"), encoding="utf-8") as f:
+            ref = yaml.safe_load(f)
         mine = M.heisenberg_chain_config(L, symm=symm, spin_inversion=-1 if L == 10 else None)
         assert ref["basis"] == {**mine["basis"]}, name
         assert [(t["expression"], t["sites"]) for t in ref["hamiltonian"]["terms"]] == \

@@ -132,17 +132,14 @@ def test_golden_files_without_a_model_are_failures_not_skips(tmp_path):
     assert len(res) == 1 and not res[0]["ok"] and "no model" in res[0]["detail"]
 
 
-def test_make_check_matrix_is_the_reference_makefiles(have_reference):
-    """the file lists of check.py are the Makefile's (read here, where /root/reference exists)"""
-    if not have_reference:
-        pytest.skip("/root/reference is absent (GPU box)")
-    import re
-
+def test_make_check_matrix_is_the_reference_makefiles():
+    """the file lists of check.py are the Makefile's (read from it into tests/golden/reference.json by
+    tests/golden/make_reference_fixtures.py)"""
     from distributed_matvec_amd import check
+    from helpers import reference_facts
 
-    mk = open("/root/reference/Makefile").read()
-    states = re.findall(r"--kRepresentatives data/matvec/(\w+)\.h5", mk.split("check-states-enumeration:")[1].split(".PHONY")[0])
-    matvec = re.findall(r"--kVectors data/matvec/(\w+)\.h5", mk.split("check-matrix-vector-product:")[1].split("TEST_DATA_URL")[0])
+    states, matvec = reference_facts()["make_check_states"], reference_facts()["make_check_matvec"]
+    assert len(states) == 14 and len(matvec) == 13
     assert states == check.MAKE_CHECK_STATES
     assert matvec == check.MAKE_CHECK_MATVEC
     for n in set(states) | set(matvec):  # ... and every one of them has its model in tests/golden/models.json (what the GPU box reads)

@@ -2,7 +2,7 @@
 /root/reference/src/ForeignTypes.chpl:261-288): the YAML subset of the reference's data files parsed and compiled by the
 library itself -- a C or Chapel caller needs no Python.  Checked against the Python mirror (PyYAML + config.py, an independent
 implementation of the same compilation) on every model of tests/golden/models.json written out in two YAML styles, and on
-the reference's own files when the reference tree is present (this container; never on the GPU box)."""
+the reference's own files (recorded under tests/golden/data)."""
 import ctypes as C
 import glob
 import os
@@ -13,7 +13,7 @@ import yaml
 
 import distributed_matvec_amd as D
 from distributed_matvec_amd import _lib
-from helpers import golden, product_terms
+from helpers import REFERENCE_DATA, golden, product_terms
 
 
 def reference_style(cfg):
@@ -97,9 +97,8 @@ def test_c_loader_equals_python_mirror(name, style):
 
 
 def test_reference_data_files_when_present():
-    files = sorted(glob.glob("/root/reference/data/*.yaml"))
-    if not files:
-        pytest.skip("the reference tree is not mounted (GPU box)")
+    files = sorted(glob.glob(os.path.join(REFERENCE_DATA, "*.yaml")))
+    assert len(files) == 22, files  # the reference's data/*.yaml, recorded by tests/golden/make_reference_fixtures.py
     L = _lib.load()
     for f in files:
         with open(f, encoding="utf-8") as fh:
@@ -111,7 +110,7 @@ def test_reference_data_files_when_present():
         finally:
             L.ls_hs_destroy_yaml_config(conf)
     # and through the host mirror of loadConfigFromYaml, which now is load -> clone -> destroy as in ForeignTypes.chpl:261-288
-    basis, h = D.loadConfigFromYaml("/root/reference/data/heisenberg_chain_10.yaml", hamiltonian=True)
+    basis, h = D.loadConfigFromYaml(os.path.join(REFERENCE_DATA, "heisenberg_chain_10.yaml"), hamiltonian=True)
     assert basis.numberSites() == 10 and basis.spinInversion() == -1 and h.numberOffDiagTerms() == 10
 
 
