@@ -218,6 +218,7 @@ def load():
         "ls_hs_init": (None, []),
         "ls_hs_exit": (None, []),
         "ls_hs_create_spin_basis": (bp, [C.c_int, C.c_int, C.c_int, C.c_int, c_intp, c_intp]),
+        "ls_hs_create_basis": (bp, [C.c_int, C.c_int, C.c_int, C.c_int]),
         "ls_hs_clone_basis": (bp, [bp]),
         "ls_hs_destroy_basis": (None, [bp]),
         "ls_hs_create_operator_from_terms": (op, [bp, C.c_int, c_f64p, c_u64p, c_u64p, c_u64p, c_u64p]),

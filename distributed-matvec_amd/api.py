@@ -72,6 +72,11 @@ class Basis:
     @staticmethod
     def fromSpec(spec: _config.BasisSpec) -> "Basis":
         L = _lib.load()
+        if spec.is_fermionic:  # no symmetries: parse_basis refuses them
+            p = L.ls_hs_create_basis(_config.PARTICLES[spec.particle], spec.number_sites, spec.number_particles, spec.number_up)
+            if not p:
+                raise LsAmdError(L.ls_amd_last_error().decode())
+            return Basis(p, True, spec)
         ng = len(spec.permutations)
         perms = (C.c_int * max(1, ng * spec.number_sites))(*[v for p in spec.permutations for v in p])
         sectors = (C.c_int * max(1, ng))(*spec.sectors)
@@ -93,6 +98,9 @@ class Basis:
     def numberBits(self): return int(_lib.load().ls_hs_basis_number_bits(self.payload))
     def numberWords(self): return int(_lib.load().ls_hs_basis_number_words(self.payload))
     def spinInversion(self): return int(self.payload.contents.spin_inversion)
+    def particleType(self): return int(self.payload.contents.particle_type)  # config.PARTICLES
+    def numberParticles(self): return int(self.payload.contents.number_particles)
+    def numberUp(self): return int(self.payload.contents.number_up)
     def isStateIndexIdentity(self): return bool(self.payload.contents.state_index_is_identity)
     def requiresProjection(self): return bool(self.payload.contents.requires_projection)
     def isHammingWeightFixed(self): return bool(_lib.load().ls_hs_basis_has_fixed_hamming_weight(self.payload))
@@ -240,8 +248,8 @@ def loadConfigFromDict(cfg: dict, hamiltonian: bool = False, observables: bool =
     if hamiltonian:
         if cfg.get("hamiltonian") is None:
             raise LsAmdError("halt: config does not contain a Hamiltonian")  # ForeignTypes.chpl:273-274
-        h = Operator.fromSpec(basis, _config.parse_operator(cfg["hamiltonian"]))
-    obs = [Operator.fromSpec(basis, _config.parse_operator(o)) for o in (cfg.get("observables") or [])] if observables else []
+        h = Operator.fromSpec(basis, _config.parse_operator(cfg["hamiltonian"], bspec))
+    obs = [Operator.fromSpec(basis, _config.parse_operator(o, bspec)) for o in (cfg.get("observables") or [])] if observables else []
     if not hamiltonian and not observables:
         return basis
     if hamiltonian and not observables:

@@ -10,9 +10,17 @@ monomial applied to a site tuple yields a handful of terms
 (ls_hs_create_operator_from_terms).  No numerics on the hot path happen here.
 
 Conventions: site i <-> bit i; bit 0 = spin up (sigma^z = +1); S^a = sigma^a / 2.
+
+Fermions (``particle: spinless-fermion | spinful-fermion``): one bit per mode -- mode i = bit i for spinless fermions, mode
+(i, up) = bit i and mode (i, down) = bit i + L for spinful ones -- and the Jordan-Wigner order is the bit order:
+    c+_k |n> = (-1)^{sum_{k' < k} n_k'} |n + e_k>
+(include/ls_hs.h).  Operators ``c†ᵢσ``, ``cᵢσ``, ``nᵢσ`` with σ in {↑, ↓} (no σ for spinless fermions); a monomial compiles to
+one term per occupation pattern of the modes it touches, its sign mask the XOR of the "modes below k" masks of its c / c†
+factors without those modes (their occupations are fixed by the pattern and folded into v).
 """
 from __future__ import annotations
 
+import cmath
 import itertools
 from dataclasses import dataclass, field
 
@@ -50,6 +58,85 @@ def parse_expression(expr: str):
     if not factors:
         raise ValueError(f"expression {expr!r} has no operators")
     return scalar, factors
+
+
+_SPIN_ARROW = {"↑": 0, "↓": 1}
+
+
+def parse_fermion_expression(expr: str, spinful: bool):
+    """'-1 × c†₀↑ c₁↑' -> (-1+0j, [('+', 0, 0), ('-', 1, 0)]): kind in {'+', '-', 'n'}, local site, spin (0 up, 1 down)."""
+    scalar = 1.0 + 0j
+    factors = []
+    for tok in expr.replace("×", " ").replace("*", " ").split():
+        if tok[0] in ("c", "n"):
+            rest = tok[1:]
+            if tok[0] == "c" and rest.startswith("†"):
+                kind, rest = "+", rest[1:]
+            else:
+                kind = "-" if tok[0] == "c" else "n"
+            spin = None
+            if rest and rest[-1] in _SPIN_ARROW:
+                spin, rest = _SPIN_ARROW[rest[-1]], rest[:-1]
+            if not rest or any(ch not in _SUB for ch in rest):
+                raise ValueError(f"cannot parse site index in {tok!r}")
+            idx = 0
+            for ch in rest:
+                idx = idx * 10 + _SUB[ch]
+            if spinful and spin is None:
+                raise ValueError(f"spinful-fermion operator {tok!r} needs a spin index (↑ or ↓)")
+            if not spinful and spin is not None:
+                raise ValueError(f"spinless-fermion operator {tok!r} takes no spin index")
+            factors.append((kind, idx, spin or 0))
+        elif tok[0] in ("σ", "S"):
+            raise ValueError(f"spin operator {tok!r} in a fermionic expression {expr!r}")
+        else:
+            scalar *= complex(tok)
+    if not factors:
+        raise ValueError(f"expression {expr!r} has no operators")
+    return scalar, factors
+
+
+def fermion_monomial_terms(expr: str, sites, spinful: bool, number_sites: int):
+    """Terms (v, m, r, x, s) of one fermionic monomial on one tuple of global sites (sign convention: module docstring)."""
+    scalar, factors = parse_fermion_expression(expr, spinful)
+    k = 1 + max(f[1] for f in factors)
+    if len(sites) != k:
+        raise ValueError(f"expression {expr!r} needs {k} sites, got {sites}")
+    if len(set(sites)) != len(sites):
+        raise ValueError(f"repeated site in {sites}")
+    modes = [int(sites[i]) + (number_sites if s else 0) for _, i, s in factors]
+    touched = sorted(set(modes))
+    M = 0
+    for q in touched:
+        M |= 1 << q
+    s_mask = 0
+    for (kind, _, _), q in zip(factors, modes):
+        if kind != "n":
+            s_mask ^= (1 << q) - 1
+    s_mask &= ~M
+    terms = []
+    for pat in range(1 << len(touched)):
+        r = 0
+        for j, q in enumerate(touched):
+            if (pat >> j) & 1:
+                r |= 1 << q
+        occ, v = r, scalar
+        for (kind, _, _), q in reversed(list(zip(factors, modes))):  # written left-to-right, acting right-to-left
+            bit = 1 << q
+            if kind == "n":
+                if not occ & bit:
+                    v = 0
+                    break
+                continue
+            if (kind == "+") == bool(occ & bit):
+                v = 0
+                break
+            if bin(occ & M & (bit - 1)).count("1") & 1:
+                v = -v
+            occ ^= bit
+        if v != 0:
+            terms.append((complex(v), M, r, r ^ occ, s_mask))
+    return terms
 
 
 def _compose(first, second):
@@ -117,6 +204,9 @@ def monomial_terms(expr: str, sites):
     return terms
 
 
+PARTICLES = {"spin-1/2": 0, "spinful-fermion": 1, "spinless-fermion": 2}  # ls_hs_particle_type
+
+
 @dataclass
 class BasisSpec:
     number_sites: int
@@ -124,6 +214,13 @@ class BasisSpec:
     spin_inversion: int = 0
     permutations: list = field(default_factory=list)
     sectors: list = field(default_factory=list)
+    particle: str = "spin-1/2"
+    number_particles: int = -1  # fermions: -1 unrestricted
+    number_up: int = -1  # spinful fermions: -1 = only number_particles fixed
+
+    @property
+    def is_fermionic(self) -> bool:
+        return self.particle != "spin-1/2"
 
 
 @dataclass
@@ -136,9 +233,24 @@ def parse_basis(cfg: dict) -> BasisSpec:
     hw = b.get("hamming_weight", None)
     inv = b.get("spin_inversion", None)
     syms = b.get("symmetries", None) or []
-    particle = b.get("particle", "spin-1/2")
+    particle = b.get("particle") or "spin-1/2"
+    if particle not in PARTICLES:
+        raise ValueError(f"unknown particle {particle!r} (spin-1/2, spinful-fermion or spinless-fermion)")
     if particle != "spin-1/2":
-        raise ValueError(f"only spin-1/2 bases are supported, got {particle!r}")
+        if "number_spins" in b:
+            raise ValueError(f"number_spins is a key of spin-1/2 bases, not of particle {particle!r} (use number_sites)")
+        for key in ("hamming_weight", "spin_inversion", "symmetries"):
+            if b.get(key):
+                raise ValueError(f"{key} is not supported for particle {particle!r}")
+        if "number_sites" not in b:
+            raise ValueError(f"particle {particle!r} needs number_sites")
+        npart, nup = b.get("number_particles", None), b.get("number_up", None)
+        if particle == "spinless-fermion" and nup is not None:
+            raise ValueError("number_up is a key of spinful-fermion bases")
+        if nup is not None and npart is None:
+            raise ValueError("a fixed number_up needs a fixed number_particles")
+        return BasisSpec(number_sites=int(b["number_sites"]), particle=particle,
+                         number_particles=-1 if npart is None else int(npart), number_up=-1 if nup is None else int(nup))
     return BasisSpec(
         number_sites=int(b["number_spins"]),
         hamming_weight=-1 if hw is None else int(hw),
@@ -148,14 +260,20 @@ def parse_basis(cfg: dict) -> BasisSpec:
     )
 
 
-def parse_operator(section: dict) -> OperatorSpec:
+def parse_operator(section: dict, basis: BasisSpec = None) -> OperatorSpec:
+    """`basis` decides the operator language: σ / S for spin-1/2 (or None), c† / c / n for fermionic bases."""
+    fermionic = basis is not None and basis.is_fermionic
     terms = []
     for t in section["terms"]:
         if "expression" not in t:
             raise ValueError("only the `expression:` schema is supported (data/*.yaml); "
                              "old-schema `matrix:` files are inputs of input_for_matvec.py only")
         for sites in t["sites"]:
-            terms.extend(monomial_terms(t["expression"], [int(q) for q in sites]))
+            if fermionic:
+                terms.extend(fermion_monomial_terms(t["expression"], [int(q) for q in sites],
+                                                    basis.particle == "spinful-fermion", basis.number_sites))
+            else:
+                terms.extend(monomial_terms(t["expression"], [int(q) for q in sites]))
     return OperatorSpec(terms)
 
 
@@ -177,3 +295,28 @@ def heisenberg_chain_config(L: int, symm: bool = False, spin_inversion=None) -> 
     lattice = [[i, (i + 1) % L] for i in range(L)]
     terms = [{"expression": e, "sites": lattice} for e in ("σˣ₀ σˣ₁", "σʸ₀ σʸ₁", "σᶻ₀ σᶻ₁")]
     return {"basis": basis, "hamiltonian": {"name": "Heisenberg Hamiltonian", "terms": terms}}
+
+
+def hubbard_config(sites: int, bonds, t=1.0, U=4.0, number_up=None, number_down=None, V=0.0, peierls=0.0) -> dict:
+    """Spinful Hubbard model -t sum_<ij>,s (e^{i phi} c+_is c_js + h.c.) + U sum_i n_i↑ n_i↓ + V sum_<ij> n_i n_j over `bonds`
+    (pairs (i, j)); half filling with N↑ = N↓ by default."""
+    nu = sites // 2 if number_up is None else number_up
+    nd = sites // 2 if number_down is None else number_down
+    bonds = [[int(i), int(j)] for i, j in bonds]
+    fwd = complex(-t) * cmath.exp(1j * peierls)
+    terms = []
+    for s in ("↑", "↓"):
+        terms.append({"expression": f"{_c(fwd)} × c†₀{s} c₁{s}", "sites": bonds})
+        terms.append({"expression": f"{_c(fwd.conjugate())} × c†₁{s} c₀{s}", "sites": bonds})
+    if U:
+        terms.append({"expression": f"{U!r} × n₀↑ n₀↓", "sites": [[i] for i in range(sites)]})
+    if V:
+        for s1 in ("↑", "↓"):
+            for s2 in ("↑", "↓"):
+                terms.append({"expression": f"{V!r} × n₀{s1} n₁{s2}", "sites": bonds})
+    return {"basis": {"particle": "spinful-fermion", "number_sites": sites, "number_particles": nu + nd, "number_up": nu},
+            "hamiltonian": {"name": "Hubbard", "terms": terms}}
+
+
+def _c(z: complex) -> str:
+    return repr(z.real) if z.imag == 0 else f"{z.real!r}{z.imag:+.17g}j"

@@ -138,6 +138,7 @@ struct ls_amd_operator_ext;
 static struct ls_amd_basis_ext *basis_ext_of(ls_hs_basis const *b);
 static struct ls_amd_operator_ext *operator_ext_of(ls_hs_operator const *op);
 #define BEXT(b) basis_ext_of(b)
+#define NBITS(b) (BEXT(b)->nbits) /* width of a basis state: number_sites counts sites, not modes */
 #define OEXT(op) operator_ext_of(op)
 
 /* ============================================================================================ */
@@ -239,7 +240,11 @@ uint64_t ls_hs_fixed_hamming_index_to_state(ptrdiff_t idx, int hamming_weight) {
 /* basis                                                                                        */
 /* ============================================================================================ */
 struct ls_amd_basis_ext {
-    int hamming_weight; /* -1 unrestricted */
+    int hamming_weight; /* -1 unrestricted (and for the spinful product basis: two weights, see below) */
+    int nbits;          /* bits of a basis state: number_sites, or 2 number_sites for spinful fermions */
+    /* spinful fermions with fixed (N_up, N_down): the product of the weight-N_up words of the low half (mode (i, up) = bit i)
+     * and the weight-N_down words of the high half (mode (i, down) = bit i + L) -- index kind LSK_INDEX_PRODUCT */
+    int product, prod_up, prod_dn;
     int n_generators;
     int *gen_perms;     /* [n_generators][L] */
     int *gen_sectors;
@@ -515,6 +520,7 @@ ls_hs_basis *ls_hs_create_spin_basis(int number_sites, int hamming_weight, int s
     b->spin_inversion = spin_inversion;
     b->kernels = NULL;
     ext->hamming_weight = hamming_weight < 0 ? -1 : hamming_weight;
+    ext->nbits = number_sites;
     ext->n_generators = number_generators;
     ext->gen_perms = (int *)malloc(sizeof(int) * (size_t)(number_generators > 0 ? number_generators : 1) * number_sites);
     ext->gen_sectors = (int *)malloc(sizeof(int) * (size_t)(number_generators > 0 ? number_generators : 1));
@@ -528,10 +534,54 @@ ls_hs_basis *ls_hs_create_spin_basis(int number_sites, int hamming_weight, int s
     return b;
 }
 
+/* FFI.chpl:143-144 (declared, commented out, in the reference).  Fermionic bases are unprojected: a basis state is a word of
+ * occupation numbers, one bit per mode -- L modes for spinless fermions, 2 L for spinful ones (mode (i, up) = bit i, mode
+ * (i, down) = bit i + L, as the reference's x = (xB << numberSites) | xA, StatesEnumeration.chpl:248-252).  Internally they are
+ * spin bases over that many bits, except the spinful (N, N_up) basis, which is the product of two fixed-weight halves. */
+ls_hs_basis *ls_hs_create_basis(ls_hs_particle_type particle_type, int number_sites, int number_particles, int number_up) {
+    if (particle_type == LS_HS_SPIN) return ls_hs_create_spin_basis(number_sites, number_up, 0, 0, NULL, NULL);
+    if (particle_type == LS_HS_SPINLESS_FERMION) {
+        if (number_sites < 1 || number_sites > 64) { set_error("spinless fermions: number_sites must be in [1, 64]"); return NULL; }
+        if (number_particles < -1 || number_particles > number_sites) { set_error("spinless fermions: number_particles must be in [0, number_sites] or -1"); return NULL; }
+        if (number_up != -1) { set_error("spinless fermions have no number_up (pass -1)"); return NULL; }
+        ls_hs_basis *b = ls_hs_create_spin_basis(number_sites, number_particles, 0, 0, NULL, NULL);
+        if (!b) return NULL;
+        b->particle_type = LS_HS_SPINLESS_FERMION;
+        b->number_particles = number_particles;
+        b->number_up = -1;
+        return b;
+    }
+    if (particle_type != LS_HS_SPINFUL_FERMION) { set_error("unknown particle type %d", particle_type); return NULL; }
+    if (number_sites < 1 || number_sites > 32) { set_error("spinful fermions: number_sites must be in [1, 32] (2 number_sites modes in one word)"); return NULL; }
+    if (number_particles < -1 || number_particles > 2 * number_sites) { set_error("spinful fermions: number_particles must be in [0, 2 number_sites] or -1"); return NULL; }
+    if (number_up != -1) {
+        if (number_particles < 0) { set_error("spinful fermions: a fixed number_up needs a fixed number_particles"); return NULL; }
+        if (number_up < 0 || number_up > number_sites || number_particles - number_up < 0 || number_particles - number_up > number_sites) {
+            set_error("spinful fermions: need 0 <= number_up <= number_sites and 0 <= number_particles - number_up <= number_sites"); return NULL;
+        }
+    }
+    ls_hs_basis *b = ls_hs_create_spin_basis(2 * number_sites, number_up == -1 ? number_particles : -1, 0, 0, NULL, NULL);
+    if (!b) return NULL;
+    struct ls_amd_basis_ext *e = BEXT(b);
+    b->number_sites = number_sites;
+    b->particle_type = LS_HS_SPINFUL_FERMION;
+    b->number_particles = number_particles;
+    b->number_up = number_up;
+    if (number_up != -1) {
+        e->product = 1;
+        e->prod_up = number_up;
+        e->prod_dn = number_particles - number_up;
+        b->state_index_is_identity = false;
+    }
+    return b;
+}
+
 ls_hs_basis *ls_hs_clone_basis(ls_hs_basis const *basis) {
     struct ls_amd_basis_ext const *e = BEXT(basis);
-    ls_hs_basis *b = ls_hs_create_spin_basis(basis->number_sites, e->hamming_weight, basis->spin_inversion,
-                                             e->n_generators, e->gen_perms, e->gen_sectors);
+    ls_hs_basis *b = basis->particle_type != LS_HS_SPIN
+                         ? ls_hs_create_basis(basis->particle_type, basis->number_sites, basis->number_particles, basis->number_up)
+                         : ls_hs_create_spin_basis(basis->number_sites, e->hamming_weight, basis->spin_inversion,
+                                                   e->n_generators, e->gen_perms, e->gen_sectors);
     if (!b) return NULL;
     if (basis->representatives.elts) { /* deep copy, like upstream's clone keeps the built states */
         size_t bytes = 8 * basis->representatives.num_elts;
@@ -618,18 +668,28 @@ void ls_hs_destroy_basis(ls_hs_basis *b) {
 }
 
 uint64_t ls_hs_min_state_estimate(ls_hs_basis const *b) {
-    int h = BEXT(b)->hamming_weight;
+    struct ls_amd_basis_ext const *e = BEXT(b);
+    if (e->product) return (((1ULL << e->prod_dn) - 1) << b->number_sites) | ((1ULL << e->prod_up) - 1);
+    int h = e->hamming_weight;
     return h > 0 ? ((1ULL << h) - 1) : 0;
 }
 /* with spin inversion the highest admissible state has the top site bit clear (see oracle notes) */
 uint64_t ls_hs_max_state_estimate(ls_hs_basis const *b) {
-    int const L = b->number_sites - (b->spin_inversion != 0 ? 1 : 0);
-    int h = BEXT(b)->hamming_weight;
+    struct ls_amd_basis_ext const *e = BEXT(b);
+    if (e->product) { /* (weights <= L <= 32; an empty half contributes nothing and is not shifted: 2 L - 0 may be 64) */
+        int const L = b->number_sites;
+        uint64_t const dn = e->prod_dn ? ((1ULL << e->prod_dn) - 1) << (2 * L - e->prod_dn) : 0;
+        uint64_t const up = e->prod_up ? ((1ULL << e->prod_up) - 1) << (L - e->prod_up) : 0;
+        return dn | up;
+    }
+    int const L = NBITS(b) - (b->spin_inversion != 0 ? 1 : 0);
+    int h = e->hamming_weight;
     if (h >= 0) return h == 0 ? 0 : ((1ULL << h) - 1) << (L - h);
     return L >= 64 ? ~0ULL : ((1ULL << L) - 1);
 }
-int ls_hs_basis_number_bits(ls_hs_basis const *b) { return b->number_sites; }
-int ls_hs_basis_number_words(ls_hs_basis const *b) { return (b->number_sites + 63) / 64; }
+/* 2 number_sites for spinful fermions; read off the prefix alone, like the reference, for structs nobody registered */
+int ls_hs_basis_number_bits(ls_hs_basis const *b) { return b->number_sites * (b->particle_type == LS_HS_SPINFUL_FERMION ? 2 : 1); }
+int ls_hs_basis_number_words(ls_hs_basis const *b) { return (ls_hs_basis_number_bits(b) + 63) / 64; }
 bool ls_hs_basis_has_fixed_hamming_weight(ls_hs_basis const *b) { return BEXT(b)->hamming_weight >= 0; }
 bool ls_hs_basis_has_spin_inversion_symmetry(ls_hs_basis const *b) { return b->spin_inversion != 0; }
 bool ls_hs_basis_has_permutation_symmetries(ls_hs_basis const *b) { return BEXT(b)->order > 1; }
@@ -644,7 +704,7 @@ void ls_hs_unchecked_set_representatives(ls_hs_basis *b, chpl_external_array con
 
 int ls_amd_basis_group_order(ls_hs_basis const *b) { return BEXT(b)->order; }
 uint64_t ls_amd_basis_apply_group_element(ls_hs_basis const *b, int element, uint64_t state) {
-    return host_apply_elem(BEXT(b)->elems + element, state, b->number_sites);
+    return host_apply_elem(BEXT(b)->elems + element, state, NBITS(b));
 }
 int ls_amd_basis_group_character(ls_hs_basis const *b, int element, double *re, double *im) {
     if (element < 0 || element >= BEXT(b)->order) return set_error("element out of range");
@@ -773,7 +833,7 @@ int ls_amd_test_d4_mask(ls_hs_basis const *b) {
     struct ls_amd_basis_ext *e = BEXT(b);
     if (ls_amd_test_translation_cosets(b, NULL) <= 0) return 0;
     pthread_mutex_lock(&g_device_tables_lock);
-    if (e->d4_mask == 0) classify_d4_cosets(e, b->number_sites);
+    if (e->d4_mask == 0) classify_d4_cosets(e, NBITS(b));
     pthread_mutex_unlock(&g_device_tables_lock);
     return e->d4_mask > 0 ? e->d4_mask : 0;
 }
@@ -784,14 +844,14 @@ int ls_amd_test_d4_mask(ls_hs_basis const *b) {
 int ls_amd_test_translation_cosets(ls_hs_basis const *b, int *n_cosets) {
     struct ls_amd_basis_ext *e = BEXT(b);
     pthread_mutex_lock(&g_device_tables_lock);
-    if (e->tw == 0) find_translation_cosets(e, b->number_sites);
+    if (e->tw == 0) find_translation_cosets(e, NBITS(b));
     pthread_mutex_unlock(&g_device_tables_lock);
     if (n_cosets) *n_cosets = e->tw > 0 ? e->n_cosets : 0;
     return e->tw;
 }
 uint64_t ls_amd_test_rep_by_cosets(ls_hs_basis const *b, uint64_t a) {
     struct ls_amd_basis_ext *e = BEXT(b);
-    int const L = b->number_sites;
+    int const L = NBITS(b);
     if (ls_amd_test_translation_cosets(b, NULL) <= 0) return ~0ULL;
     uint64_t const mask = L >= 64 ? ~0ULL : ((1ULL << L) - 1);
     int const tw = e->tw, th = L / tw;
@@ -836,12 +896,12 @@ static int basis_device_unlocked(ls_hs_basis const *b, lsk_basis *out) {
         DEV(lsk_h2d(p, e->elems, sizeof(lsk_group_elem) * e->order));
         e->d_elems = (lsk_group_elem *)p;
     }
-    out->number_sites = b->number_sites;
+    out->number_sites = NBITS(b);
     out->hamming_weight = e->hamming_weight;
     out->spin_inversion = b->spin_inversion;
     out->n_elems = e->order;
     out->proj = e->order > 1 ? LSK_PROJ_FULL : (b->spin_inversion != 0 ? LSK_PROJ_INVERSION : LSK_PROJ_NONE);
-    out->site_mask = b->number_sites >= 64 ? ~0ULL : ((1ULL << b->number_sites) - 1);
+    out->site_mask = NBITS(b) >= 64 ? ~0ULL : ((1ULL << NBITS(b)) - 1);
     out->inv_order = 1.0 / ((double)e->order * (b->spin_inversion != 0 ? 2.0 : 1.0));
     out->elems = e->d_elems;
     out->chars_pm1 = 1;
@@ -867,7 +927,7 @@ static int basis_device_unlocked(ls_hs_basis const *b, lsk_basis *out) {
     if (trivial && e->order > 1 && !k4_general) {
         out->k4_mode = 1;
         /* full cyclic group of the ring (every rotation k = 0..L-1), optionally with all reflections? */
-        int const L = b->number_sites;
+        int const L = NBITS(b);
         uint64_t rot = 0, rev = 0;
         int other = 0;
         for (int g = 0; g < e->order; ++g) {
@@ -1222,15 +1282,15 @@ ls_hs_operator *ls_hs_create_operator_from_terms(ls_hs_basis const *basis, int n
     struct ls_amd_basis_ext *be = (struct ls_amd_basis_ext *)reg_get(basis);
     if (!be) { set_error("unknown basis: create it with ls_hs_create_spin_basis or register it with ls_amd_adopt_basis"); return NULL; }
     uint64_t *offx = NULL;
-    struct ls_amd_operator_ext *ext = build_operator_ext(basis->number_sites, basis->spin_inversion != 0, number_terms, v, m, r,
+    struct ls_amd_operator_ext *ext = build_operator_ext(NBITS(basis), basis->spin_inversion != 0, number_terms, v, m, r,
                                                          x, s, &offx);
     if (!ext) return NULL;
     ls_hs_operator *op = (ls_hs_operator *)calloc(1, sizeof(*op));
     reg_put(op, ext, REG_OPERATOR);
     op->basis = (ls_hs_basis *)basis;
     __atomic_add_fetch(&be->refcount, 1, __ATOMIC_RELAXED);
-    op->diag_terms = make_nbt(ext->diag, NULL, ext->n_diag, basis->number_sites);
-    op->off_diag_terms = make_nbt(ext->off, offx, ext->n_off, basis->number_sites);
+    op->diag_terms = make_nbt(ext->diag, NULL, ext->n_diag, NBITS(basis));
+    op->off_diag_terms = make_nbt(ext->off, offx, ext->n_off, NBITS(basis));
     free(offx);
     return op;
 }
@@ -1243,9 +1303,16 @@ ls_hs_operator *ls_hs_create_operator_from_terms(ls_hs_basis const *basis, int n
 int ls_amd_adopt_basis(ls_hs_basis const *basis, int number_generators, int const *permutations, int const *sectors) {
     if (!basis) return set_error("null basis");
     if (reg_get(basis)) return set_error("basis %p is already registered", (void const *)basis);
-    if (basis->particle_type != LS_HS_SPIN) return set_error("only spin bases are supported (DistributedMatrixVector.chpl works on spin configs)");
-    ls_hs_basis *tmp = ls_hs_create_spin_basis(basis->number_sites, basis->number_up >= 0 ? basis->number_up : -1, basis->spin_inversion,
-                                               number_generators, permutations, sectors);
+    ls_hs_basis *tmp;
+    if (basis->particle_type != LS_HS_SPIN) {
+        /* fermionic prefixes: number_sites, number_particles, number_up, particle_type; no symmetries (fermionic permutation signs
+         * are not implemented) */
+        if (number_generators != 0 || basis->spin_inversion != 0 || basis->requires_projection)
+            return set_error("fermionic bases with symmetries are not supported");
+        tmp = ls_hs_create_basis(basis->particle_type, basis->number_sites, basis->number_particles, basis->number_up);
+    } else
+        tmp = ls_hs_create_spin_basis(basis->number_sites, basis->number_up >= 0 ? basis->number_up : -1, basis->spin_inversion,
+                                      number_generators, permutations, sectors);
     if (!tmp) return -1;
     if (tmp->requires_projection != basis->requires_projection) {
         ls_hs_destroy_basis(tmp);
@@ -1282,7 +1349,7 @@ int ls_amd_adopt_operator(ls_hs_operator const *op) {
             v[2 * k] = parts[q]->v[i].re; v[2 * k + 1] = parts[q]->v[i].im;
             m[k] = parts[q]->m[i]; r[k] = parts[q]->r[i]; x[k] = parts[q]->x[i]; s[k] = parts[q]->s[i];
         }
-    struct ls_amd_operator_ext *ext = build_operator_ext(op->basis->number_sites, op->basis->spin_inversion != 0, n, v, m, r, x, s, NULL);
+    struct ls_amd_operator_ext *ext = build_operator_ext(NBITS(op->basis), op->basis->spin_inversion != 0, n, v, m, r, x, s, NULL);
     free(v); free(m); free(r); free(x); free(s);
     if (!ext) return -1;
     ext->adopted = 1;
@@ -1509,6 +1576,10 @@ struct ls_amd_plan {
     int one_rank_full_basis; /* FAMILY_TILE with one rank that owns the full fixed-weight basis (plan_setup_part) */
     lsk_pairplan pairs;
     void *d_pair_recs, *d_rank_low, *d_pair_binom, *d_states32, *d_pair_rows, *d_pair_sites;
+    int global_index;  /* a temporary plan that only builds the index of the GLOBAL basis (replicated-x plans): no product index */
+    int has_hubbard;   /* species-split row kernel (lsk_hubbard_apply): spinful product basis, separable operator */
+    lsk_hubbard hubbard;
+    void *d_hub[6];    /* words / ranks / amplitudes of the two species tables */
     int has_chain; /* staged row kernel (lsk_chain) */
     int chain_cached;      /* leading non-adjacent exchange groups whose partner ranks are cached */
     void *d_chain_cache;   /* [chain_cached][count] u32, or u64 when chain_wide */
@@ -2105,7 +2176,7 @@ static int push_staged_eligible(ls_amd_plan const *pl) {
     struct ls_amd_operator_ext const *ext = OEXT(op);
     char const *e = getenv("LS_AMD_ROW_KERNEL");
     if (e && strcmp(e, "generic") == 0) return 0;
-    if (op->basis->number_sites > 64 || op->basis->spin_inversion != 0 || pl->dbs.proj != LSK_PROJ_NONE || !ext->is_real ||
+    if (NBITS(op->basis) > 64 || op->basis->spin_inversion != 0 || pl->dbs.proj != LSK_PROJ_NONE || !ext->is_real ||
         ext->runs.n_runs <= 0 || BEXT(op->basis)->hamming_weight < 0)
         return 0;
     for (int q = 0; q < ext->runs.n_runs; ++q) if (ext->runs.cnt[q] >> 16) return 0; /* directed runs: k_direct's DIRECTED instantiation */
@@ -2116,7 +2187,7 @@ static int chain_eligible(ls_amd_plan const *pl) {
     struct ls_amd_operator_ext const *ext = OEXT(op);
     char const *e = getenv("LS_AMD_ROW_KERNEL"); /* auto (default) | generic: k_direct | pairs: k_pairs_t where it applies | pairrows / pairsites: k_pairs_row / k_pairs_site where they apply */
     if (e && (strcmp(e, "generic") == 0 || strcmp(e, "pairs") == 0 || strcmp(e, "pairrows") == 0 || strcmp(e, "pairsites") == 0)) return 0;
-    int const L = op->basis->number_sites;
+    int const L = NBITS(op->basis);
     int const inv = op->basis->spin_inversion != 0;
     /* Inversion sectors WITHOUT permutations (round 6; BASELINE config 1's sector, BatchedOperator.chpl:119-161): at half filling the
      * canonical state of {sigma, ~sigma} is the one with the top site clear, so the basis is the full set of weight-L/2 words of
@@ -2145,7 +2216,7 @@ static int setup_chain(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t con
     int nc = ext->n_groups - ext->runs.n_run_groups;
     /* the cached pairs: flip mask + amplitude.  Inversion sectors (chain_eligible): the run bond that touches the top site becomes
      * a cached pair, pairs that touch the top site carry the sector's sign, and THIS plan's copy of the run table loses that bond */
-    int const Ls = pl->op->basis->number_sites;
+    int const Ls = NBITS(pl->op->basis);
     int const inv = pl->dbs.proj == LSK_PROJ_INVERSION;
     uint64_t const top = 1ULL << (Ls - 1);
     uint64_t cx[3];
@@ -2174,7 +2245,7 @@ static int setup_chain(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t con
     /* ranks are 32-bit while the whole basis (index.count states: x is indexed by global rank) has < 2^32 - 1 states;
      * LS_AMD_CHAIN_WIDE=1 forces the 64-bit instantiation (test hook: no in-tree config is that large) */
     char const *ew = getenv("LS_AMD_CHAIN_WIDE");
-    pl->chain_wide = index.count >= 0xffffffffLL || (ew && atoi(ew) != 0 && pl->op->basis->number_sites > 32);
+    pl->chain_wide = index.count >= 0xffffffffLL || (ew && atoi(ew) != 0 && NBITS(pl->op->basis) > 32);
     size_t const es = pl->chain_wide ? sizeof(uint64_t) : sizeof(uint32_t);
     if (nc > 0 && n > 0) {
         void *q;
@@ -2203,7 +2274,7 @@ static int setup_chain(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t con
      * 8.59 -> 8.41 ms; c128: 15.40 -> 15.70 ms, so complex vectors keep the two arrays).  This shape has no unfused
      * instantiation (it sat at 98 SGPRs, one resident block per CU short); a second cached pair stays in the cache
      * array, whose layout [pair][row] is what the kernel indexes.  No room for the records: the generic row kernel. */
-    if (!pl->cplx && pl->op->basis->number_sites <= 32 && !pl->chain_wide && n > 0) {
+    if (!pl->cplx && NBITS(pl->op->basis) <= 32 && !pl->chain_wide && n > 0) {
         void *q;
         if (lsk_malloc(&q, sizeof(uint64_t) * (size_t)n) != 0) {
             if (pl->d_chain_cache) { lsk_free(pl->d_chain_cache); pl->d_chain_cache = NULL; }
@@ -2234,7 +2305,7 @@ static int pair_cmp(void const *pa, void const *pb) {
 static int setup_pairs(ls_amd_plan *pl, int64_t n, uint64_t const *d_reps, void *stream) {
     ls_hs_operator const *op = pl->op;
     struct ls_amd_operator_ext const *ext = OEXT(op);
-    int const L = op->basis->number_sites, hw = BEXT(op->basis)->hamming_weight;
+    int const L = NBITS(op->basis), hw = BEXT(op->basis)->hamming_weight;
     char const *e = getenv("LS_AMD_ROW_KERNEL");
     if (e && strcmp(e, "generic") == 0) return 0;
     int const wide = L > 32; /* 33..64 sites (round 6): the kernel streams the 8-byte representatives themselves */
@@ -2417,7 +2488,7 @@ static int streams_wanted(ls_amd_plan const *pl) {
 }
 static int setup_packet_index(ls_amd_plan *pl, uint64_t const *const *d_reps, int64_t const *counts, void *stream) {
     ls_hs_basis const *b = pl->op->basis;
-    int const L = b->number_sites, h = BEXT(b)->hamming_weight, P = pl->P;
+    int const L = NBITS(b), h = BEXT(b)->hamming_weight, P = pl->P;
     char const *e = getenv("LS_AMD_PACKET_INDEX");
     int const for_streams = streams_wanted(pl); /* the streams need every packet's index at its destination */
     if ((e && atoi(e) == 0) || g_no_packet_index) return 0;
@@ -2482,9 +2553,105 @@ static int setup_packet_index(ls_amd_plan *pl, uint64_t const *const *d_reps, in
     return 0;
 }
 
+/* Species-split row kernel (k_hubbard, lsk.h): one process, pull, a Hermitian operator on the spinful product basis whose every
+ * off-diagonal group lives inside one species half (support of x, m and s) -- Hubbard hopping of any range and phase, one-species
+ * density-assisted terms; the diagonal is arbitrary.  The tables hold <row word|H|partner word> for every word of a species and
+ * every group of that species whose partner has the species' weight: O(C(L, N_up) + C(L, N_down)) entries, never O(nnz).
+ * LS_AMD_ROW_KERNEL=generic keeps k_direct. */
+static int hubbard_species(ls_amd_plan *pl, int half, int weight, lsk_species *sp, void **d_words, void **d_rank, void **d_coef,
+                           int64_t *nnz_words) {
+    struct ls_amd_operator_ext const *ext = OEXT(pl->op);
+    int const L = pl->op->basis->number_sites, shift = half ? L : 0;
+    uint64_t const hmask = ((1ULL << L) - 1) << shift;
+    int64_t const n = (int64_t)binom(L, weight);
+    int const cc = pl->hubbard.cplx_coef;
+    int *gs = (int *)malloc(sizeof(int) * (ext->n_groups > 0 ? ext->n_groups : 1));
+    int ng = 0;
+    if (gs) for (int g = 0; g < ext->n_groups; ++g) if ((ext->groups[g].x & hmask) != 0) gs[ng++] = g;
+    uint32_t *words = (uint32_t *)malloc(4 * (size_t)n);
+    int *cnt = (int *)calloc((size_t)n, sizeof(int));
+    int deg = 0;
+    uint32_t *rank = (uint32_t *)malloc(4 * (size_t)n * (ng > 0 ? ng : 1));
+    double *coef = (double *)malloc(8 * (size_t)(cc ? 2 : 1) * n * (ng > 0 ? ng : 1));
+    if (!gs || !words || !cnt || !rank || !coef) {
+        free(gs); free(words); free(cnt); free(rank); free(coef);
+        return set_error("species tables: out of host memory");
+    }
+    for (int64_t a = 0; a < n; ++a) words[a] = (uint32_t)ls_hs_fixed_hamming_index_to_state((ptrdiff_t)a, weight);
+    for (int64_t a = 0; a < n; ++a) {
+        int k = 0;
+        for (int q = 0; q < ng; ++q) {
+            lsk_group const *G = &ext->groups[gs[q]];
+            uint64_t const partner = ((uint64_t)words[a] << shift) ^ G->x;
+            if (__builtin_popcountll(partner) != weight) continue;
+            double re, im;
+            eval_terms(ext->off, G->begin, G->end, partner, &re, &im); /* the partner's expansion reaches this row with <row|H|partner> */
+            if (re == 0.0 && im == 0.0) continue;
+            int64_t const r = (int64_t)ls_hs_fixed_hamming_state_to_index(partner >> shift);
+            int64_t const e = (int64_t)k * n + a; /* [slot][word]: filled below in the final layout once deg is known */
+            rank[e] = (uint32_t)r;
+            if (cc) { coef[2 * e] = re; coef[2 * e + 1] = im; } else coef[e] = re;
+            ++k;
+        }
+        cnt[a] = k;
+        if (k > deg) deg = k;
+    }
+    /* the slots were written with stride n for slot k, i.e. already [slot][word]; pad every word to deg with (self, 0) */
+    int64_t active = 0;
+    for (int64_t a = 0; a < n; ++a) {
+        active += cnt[a];
+        for (int k = cnt[a]; k < deg; ++k) {
+            int64_t const e = (int64_t)k * n + a;
+            rank[e] = (uint32_t)a;
+            if (cc) { coef[2 * e] = 0.0; coef[2 * e + 1] = 0.0; } else coef[e] = 0.0;
+        }
+    }
+    int rc = upload(d_words, words, 4 * (size_t)n) || upload(d_rank, rank, 4 * (size_t)n * (deg > 0 ? deg : 1)) ||
+             upload(d_coef, coef, 8 * (size_t)(cc ? 2 : 1) * n * (deg > 0 ? deg : 1));
+    free(gs); free(words); free(cnt); free(rank); free(coef);
+    if (rc) return -1;
+    sp->n = n;
+    sp->deg = deg;
+    sp->words = (uint32_t const *)*d_words;
+    sp->rank = (uint32_t const *)*d_rank;
+    sp->coef = (double const *)*d_coef;
+    *nnz_words = active;
+    return 0;
+}
+static int setup_hubbard(ls_amd_plan *pl, part_state const *ps, void *stream) {
+    ls_hs_basis const *b = pl->op->basis;
+    struct ls_amd_basis_ext const *be = BEXT(b);
+    struct ls_amd_operator_ext const *ext = OEXT(pl->op);
+    char const *env = getenv("LS_AMD_ROW_KERNEL");
+    if (env && strcmp(env, "generic") == 0) return 0;
+    if (!be->product || pl->P != 1 || pl->n_local != 1 || pl->family != FAMILY_DIRECT_PULL || !ext->is_hermitian) return 0;
+    int const L = b->number_sites;
+    uint64_t const lo = (1ULL << L) - 1, hi = lo << L;
+    for (int g = 0; g < ext->n_groups; ++g) { /* separable: every group inside one species half */
+        lsk_group const *G = &ext->groups[g];
+        uint64_t support = G->x;
+        for (int k = G->begin; k < G->end; ++k) support |= ext->off[k].m | ext->off[k].s;
+        if ((support & lo) && (support & hi)) return 0;
+    }
+    int64_t const na = (int64_t)binom(L, be->prod_up), nb = (int64_t)binom(L, be->prod_dn);
+    /* the rows must be the product basis in its own order (plan_setup_part verified it: the plan's index is then PRODUCT) */
+    if (ps->index.kind != LSK_INDEX_PRODUCT || ps->count != na * nb || na > ((int64_t)1 << 26) || nb > ((int64_t)1 << 26)) return 0;
+    memset(&pl->hubbard, 0, sizeof(pl->hubbard));
+    pl->hubbard.L = L;
+    pl->hubbard.cplx_coef = !ext->is_real;
+    int64_t act_up = 0, act_dn = 0;
+    if (hubbard_species(pl, 0, be->prod_up, &pl->hubbard.up, &pl->d_hub[0], &pl->d_hub[1], &pl->d_hub[2], &act_up) != 0 ||
+        hubbard_species(pl, 1, be->prod_dn, &pl->hubbard.dn, &pl->d_hub[3], &pl->d_hub[4], &pl->d_hub[5], &act_dn) != 0)
+        return -1;
+    if (build_tilemap(pl, ps->count, 256) != 0) return -1;
+    pl->nnz = act_up * nb + act_dn * na; /* off-diagonal non-zeros */
+    pl->has_hubbard = 1;
+    return 0;
+}
+
 static int plan_setup_part(ls_amd_plan *pl, part_state *ps, int part_id, int num_rounds, void *stream) {
     ls_hs_basis const *b = pl->op->basis;
-    int const L = b->number_sites;
+    int const L = NBITS(b);
     int const h = BEXT(b)->hamming_weight;
     uint64_t const *d_binom;
     if (device_binom(&d_binom) != 0) return -1;
@@ -2508,6 +2675,23 @@ static int plan_setup_part(ls_amd_plan *pl, part_state *ps, int part_id, int num
             DEV(lsk_d2h(&flag, pl->d_err, sizeof(int)));
             DEV(lsk_h2d(pl->d_err, &zero, sizeof(int)));
             if (!flag) { ps->index.kind = LSK_INDEX_COMBINADIC; closed_form = 1; }
+        }
+    }
+    if (!closed_form && pl->P == 1 && !pl->global_index && (pl->family == FAMILY_DIRECT_PULL || pl->family == FAMILY_DIRECT_PUSH) &&
+        BEXT(b)->product && ps->count > 0) {
+        /* the spinful product basis in its own order: two closed-form ranks (LSK_INDEX_PRODUCT), verified on the device */
+        lsk_index pix = ps->index;
+        pix.kind = LSK_INDEX_PRODUCT;
+        pix.prod_sites = b->number_sites; pix.prod_up = BEXT(b)->prod_up; pix.prod_dn = BEXT(b)->prod_dn;
+        pix.prod_na = (int64_t)binom(b->number_sites, BEXT(b)->prod_up);
+        if (ps->count == pix.prod_na * (int64_t)binom(b->number_sites, BEXT(b)->prod_dn)) {
+            int zero = 0, flag = 0;
+            DEV(lsk_h2d(pl->d_err, &zero, sizeof(int)));
+            DEV(lsk_check_product(pix, ps->count, ps->d_reps, pl->d_err, stream));
+            DEV(lsk_sync(stream));
+            DEV(lsk_d2h(&flag, pl->d_err, sizeof(int)));
+            DEV(lsk_h2d(pl->d_err, &zero, sizeof(int)));
+            if (!flag) { ps->index = pix; closed_form = 1; }
         }
     }
     if (pl->P == 1 && pl->family == FAMILY_TILE && pl->dbs.proj == LSK_PROJ_NONE && b->spin_inversion == 0 && h >= 0 &&
@@ -2841,7 +3025,7 @@ int ls_amd_plan_create(ls_amd_plan **out, ls_hs_operator const *op, ls_amd_dtype
              * as the fallback for bases whose keys do not fit the 8-byte entries (lsk_gtab_bits). */
             char const *e = getenv("LS_AMD_PULL_INDEXED");
             pl->idx_mode = e ? atoi(e) != 0 : 1;
-            if (pl->idx_mode && (counts[0] >= 0xffffffffLL || lsk_gtab_bits(op->basis->number_sites, counts[0], (int64_t)1 << 40) < 0)) pl->idx_mode = 0;
+            if (pl->idx_mode && (counts[0] >= 0xffffffffLL || lsk_gtab_bits(NBITS(op->basis), counts[0], (int64_t)1 << 40) < 0)) pl->idx_mode = 0;
         }
     } else pl->family = FAMILY_TILE;
 
@@ -2909,11 +3093,12 @@ int ls_amd_plan_create(ls_amd_plan **out, ls_hs_operator const *op, ls_amd_dtype
             ls_amd_plan_destroy(pl);
             return -1;
         }
+        if (!pl->has_chain && !pl->has_pairs && setup_hubbard(pl, ps0, stream) != 0) { ls_amd_plan_destroy(pl); return -1; }
         if (pl->family == FAMILY_DIRECT_PUSH && combinadic && push_staged_eligible(pl)) {
             if (build_tilemap(pl, ps0->count, lsk_push_tile_rows(pl->cplx)) != 0) { ls_amd_plan_destroy(pl); return -1; }
             pl->has_push_staged = 1;
         }
-        if (!pl->has_chain && !pl->has_pairs && !pl->has_push_staged && build_tilemap(pl, ps0->count, 256) != 0) { ls_amd_plan_destroy(pl); return -1; }
+        if (!pl->has_chain && !pl->has_pairs && !pl->has_push_staged && !pl->has_hubbard && build_tilemap(pl, ps0->count, 256) != 0) { ls_amd_plan_destroy(pl); return -1; }
         if (pl->family == FAMILY_DIRECT_PULL && !OEXT(op)->is_hermitian) {
             /* a gather never sees a state that is mapped OUT of the basis (the reference's halt, DMV:115-118): checked once, here;
              * ls_amd_plan_check reports it after every matvec like the push kernels' error flag */
@@ -2943,7 +3128,7 @@ int ls_amd_plan_create(ls_amd_plan **out, ls_hs_operator const *op, ls_amd_dtype
             for (int p = 0; p < pl->n_local; ++p) {
                 part_state *ps = &pl->parts[p];
                 if (ps->index.kind != LSK_INDEX_SEARCH || ps->index.dir || ps->count <= 0 || ps->count >= 0xffffffffLL) continue;
-                if (ls_amd_internal_gtab_acquire(&ps->scatter_gt, op->basis->number_sites, ps->d_reps, ps->count, NULL, 1, stream) != 0) {
+                if (ls_amd_internal_gtab_acquire(&ps->scatter_gt, NBITS(op->basis), ps->d_reps, ps->count, NULL, 1, stream) != 0) {
                     ps->scatter_gt = NULL; /* (the error text stays readable through ls_amd_last_error; the plan works without the table) */
                 }
             }
@@ -2967,7 +3152,7 @@ int ls_amd_plan_create(ls_amd_plan **out, ls_hs_operator const *op, ls_amd_dtype
         /* static index table + room for x * norm(rep), acquired here: a table that cannot be built (no memory, a key that
          * finds no place within 255 buckets) puts the plan on the value-table path instead of failing the first matvec */
         part_state *ps = &pl->parts[0];
-        int ok = ls_amd_internal_gtab_acquire(&pl->gtab, op->basis->number_sites, ps->d_reps, ps->count, NULL, 1, stream) == 0;
+        int ok = ls_amd_internal_gtab_acquire(&pl->gtab, NBITS(op->basis), ps->d_reps, ps->count, NULL, 1, stream) == 0;
         if (ok && pl->dbs.k4_mode != 0 &&
             lsk_malloc(&pl->d_xs, (size_t)(pl->cplx ? 16 : 8) * (size_t)(ps->count > 0 ? ps->count : 1)) != 0) {
             ls_amd_internal_gtab_release(pl->gtab);
@@ -3044,6 +3229,7 @@ void ls_amd_plan_destroy(ls_amd_plan *pl) {
     if (pl->d_chain_cache) lsk_free(pl->d_chain_cache);
     if (pl->d_chain_rec) lsk_free(pl->d_chain_rec);
     if (pl->d_pair_recs) lsk_free(pl->d_pair_recs);
+    for (int k = 0; k < 6; ++k) if (pl->d_hub[k]) lsk_free(pl->d_hub[k]);
     if (pl->d_pair_rows) lsk_free(pl->d_pair_rows);
     if (pl->d_pair_sites) lsk_free(pl->d_pair_sites);
     if (pl->d_rank_low) lsk_free(pl->d_rank_low);
@@ -3152,11 +3338,12 @@ static int plan_create_replicated_impl(ls_amd_plan **out, ls_hs_operator const *
         gps.d_reps = d_reps_global;
         tmp.P = 1;
         tmp.family = FAMILY_DIRECT_PULL; /* no tile-side tables */
+        tmp.global_index = 1;
         if (pl->dbs.proj == LSK_PROJ_FULL) {
             uint64_t const *d_binom;
             if (device_binom(&d_binom) != 0) { ls_amd_plan_destroy(pl); return -1; }
             gps.index.count = count_global; gps.index.reps = d_reps_global; gps.index.binom = d_binom;
-            if (count_global > 0 && build_search_index(&gps, op->basis->number_sites, stream) != 0) { ls_amd_plan_destroy(pl); return -1; }
+            if (count_global > 0 && build_search_index(&gps, NBITS(op->basis), stream) != 0) { ls_amd_plan_destroy(pl); return -1; }
         } else if (plan_setup_part(&tmp, &gps, 0, 1, stream) != 0) { ls_amd_plan_destroy(pl); return -1; }
         pl->gindex = gps.index;
         pl->d_gtable = gps.d_table;
@@ -3340,6 +3527,7 @@ char const *ls_amd_plan_kernel_name(ls_amd_plan const *pl) {
     switch (pl->family) {
     case FAMILY_DIRECT_PUSH: return pl->has_push_staged ? "direct-push+staged" : "direct-push";
     case FAMILY_DIRECT_PULL:
+        if (pl->has_hubbard) return "direct-pull+hubbard";
         return pl->has_chain ? "direct-pull+staged" : pl->has_pairs ? (pl->pairs.sites ? "direct-pull+pairsites" : pl->pairs.rows ? "direct-pull+pairrows" : "direct-pull+pairs") : "direct-pull";
     case FAMILY_TILE_PULL: return pl->idx_mode ? (pl->slot_cache ? "tile-pull+indexed+cached" : (pl->d_vtab ? "tile-pull+values" : "tile-pull+indexed")) : "tile-pull";
     case FAMILY_REPL_DIRECT:
@@ -3355,10 +3543,11 @@ int ls_amd_plan_packet_bytes(ls_amd_plan const *pl) { return pl->key_bytes + (pl
  * plus one cached partner rank per cached pair; the generic row kernels read the 8-byte state; the projected pull kernel
  * the state and norm(alpha) */
 int ls_amd_plan_row_bytes(ls_amd_plan const *pl) {
+    if (pl->has_hubbard) return 0; /* the species tables are O(sqrt N) and cache-resident: x and y are the whole stream */
     if (pl->has_pairs) return pl->pairs.wide ? 8 : 4; /* the plan's 4-byte copy of the states, or (33..64 sites) the 8-byte representatives */
     if (pl->has_chain) {
         if (pl->d_chain_rec) return 8;
-        int const narrow = pl->op->basis->number_sites <= 32 && !pl->chain_wide;
+        int const narrow = NBITS(pl->op->basis) <= 32 && !pl->chain_wide;
         return (narrow ? 4 : 8) + pl->chain_cached * (pl->chain_wide ? 8 : 4);
     }
     if (pl->family == FAMILY_TILE_PULL || pl->family == FAMILY_REPL_TILE) return 16;
@@ -3447,7 +3636,7 @@ int ls_amd_scatter(ls_amd_plan *pl, int64_t n, uint64_t const *d_betas, void con
                    void *stream) {
     part_state *ps = &pl->parts[0];
     if (pl->streams) return set_error("ls_amd_scatter: the plan writes sorted streams (consumed by windows, dist.c)");
-    if (ps->index.kind == LSK_INDEX_COMBINADIC) return set_error("ls_amd_scatter: plan has no search index");
+    if (ps->index.kind == LSK_INDEX_COMBINADIC || ps->index.kind == LSK_INDEX_PRODUCT) return set_error("ls_amd_scatter: plan has no search index");
     int const st = stage_begin(pl, ST_SCATTER, stream);
     if (pl->key_bytes == 4) { /* pre-indexed packets: d_betas is the segment's u32 index array */
         lsk_segs sg;
@@ -3469,7 +3658,7 @@ int ls_amd_scatter_round(ls_amd_plan *pl, int num_segments, int64_t const *count
                          void *d_y, void *stream) {
     part_state *ps = &pl->parts[0];
     if (pl->streams) return set_error("ls_amd_scatter_round: the plan writes sorted streams (consumed by windows, dist.c)");
-    if (ps->index.kind == LSK_INDEX_COMBINADIC) return set_error("ls_amd_scatter_round: plan has no search index");
+    if (ps->index.kind == LSK_INDEX_COMBINADIC || ps->index.kind == LSK_INDEX_PRODUCT) return set_error("ls_amd_scatter_round: plan has no search index");
     int const st = stage_begin(pl, ST_SCATTER, stream);
     int s = 0;
     while (s < num_segments) {
@@ -3645,6 +3834,8 @@ int ls_amd_matvec(ls_amd_plan *pl, void const *const *d_x, void *const *d_y, voi
                           pl->d_chain_cache, pl->chain_v[0], pl->chain_v[1], stream));
         else if (pl->has_pairs)
             DEV(lsk_pairs(pl->pairs, pl->dbs.hamming_weight, pl->cplx, pl->tilemap, ps->count, d_x[0], d_y[0], stream));
+        else if (pl->has_hubbard)
+            DEV(lsk_hubbard_apply(pl->hubbard, pl->dop, pl->cplx, pl->tilemap, d_x[0], d_y[0], stream));
         else if (pl->has_push_staged)
             DEV(lsk_push_staged(pl->dop, pl->dbs, ps->index, pl->cplx, pl->tilemap, ps->count, ps->d_reps, d_x[0], d_y[0], pl->d_err, stream));
         else
@@ -3777,7 +3968,7 @@ int ls_amd_plan_check(ls_amd_plan *pl, void *stream) {
 /* enumeration and layout converters                                                            */
 /* ============================================================================================ */
 static int64_t candidate_count(ls_hs_basis const *b) {
-    int const Leff = b->number_sites - (b->spin_inversion != 0 ? 1 : 0);
+    int const Leff = NBITS(b) - (b->spin_inversion != 0 ? 1 : 0);
     int const h = BEXT(b)->hamming_weight;
     if (h >= 0) return (int64_t)binom(Leff, h);
     if (Leff >= 62) return -1;
@@ -3789,9 +3980,14 @@ int ls_amd_enumerate_states(ls_hs_basis const *basis, int num_locales, uint64_t 
     lsk_basis dbs;
     uint64_t const *d_binom;
     if (basis_device(basis, &dbs) != 0 || device_binom(&d_binom) != 0) return -1;
-    int64_t ncand = candidate_count(basis);
-    if (ncand < 0) return set_error("basis too large to enumerate");
-    DEV(lsk_enumerate(dbs, d_binom, ncand, d_states, count, stream));
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    if (e->product) {
+        DEV(lsk_enumerate_product(basis->number_sites, e->prod_up, e->prod_dn, d_binom, d_states, count, stream));
+    } else {
+        int64_t ncand = candidate_count(basis);
+        if (ncand < 0) return set_error("basis too large to enumerate");
+        DEV(lsk_enumerate(dbs, d_binom, ncand, d_states, count, stream));
+    }
     if (d_masks) {
         void *p;
         DEV(lsk_malloc(&p, (size_t)(*count > 0 ? *count : 1)));
@@ -4103,13 +4299,31 @@ void ls_hs_state_index(ls_hs_basis const *basis_c, ptrdiff_t n, uint64_t const *
     ix.reps = e->d_reps_cache;
     ix.binom = d_binom;
     if (b->state_index_is_identity) ix.kind = LSK_INDEX_IDENTITY;
-    else {
+    if (e->product && e->index_kind != LSK_INDEX_SEARCH) {
+        /* the spinful product basis: two closed-form ranks, once the representatives are known to be the whole basis in order */
+        ix.prod_sites = b->number_sites; ix.prod_up = e->prod_up; ix.prod_dn = e->prod_dn;
+        ix.prod_na = (int64_t)binom(b->number_sites, e->prod_up);
+        if (e->index_kind != LSK_INDEX_PRODUCT) {
+            int flag = 1;
+            void *df = NULL;
+            ix.kind = LSK_INDEX_PRODUCT;
+            if (ix.count == ix.prod_na * (int64_t)binom(b->number_sites, e->prod_dn) && lsk_malloc(&df, sizeof(int)) == 0) {
+                flag = 0;
+                if (lsk_h2d(df, &flag, sizeof(int)) != 0 || lsk_check_product(ix, ix.count, ix.reps, (int *)df, NULL) != 0 ||
+                    lsk_sync(NULL) != 0 || lsk_d2h(&flag, df, sizeof(int)) != 0) flag = 1;
+                lsk_free(df);
+            }
+            e->index_kind = flag ? LSK_INDEX_SEARCH : LSK_INDEX_PRODUCT;
+        }
+        ix.kind = e->index_kind;
+    }
+    if (!b->state_index_is_identity && ix.kind != LSK_INDEX_PRODUCT) {
         if (!e->d_index_table) {
             part_state ps;
             memset(&ps, 0, sizeof(ps));
             ps.count = ix.count;
             ps.d_reps = ix.reps;
-            if (build_search_index(&ps, b->number_sites, NULL) != 0 || lsk_sync(NULL) != 0) { halt_with("%s", g_last_error); return; }
+            if (build_search_index(&ps, NBITS(b), NULL) != 0 || lsk_sync(NULL) != 0) { halt_with("%s", g_last_error); return; }
             e->d_index_table = ps.d_table;
             e->index_shift = ps.index.shift;
         }

@@ -293,7 +293,7 @@ extern "C" int lsk_state_info(lsk_basis bs, int64_t n, uint64_t const *alphas, u
 __global__ __launch_bounds__(kBlock) void k_state_index(lsk_index ix, int64_t n, uint64_t const *__restrict__ spins,
                                                         int64_t *__restrict__ indices) {
     __shared__ uint64_t s_binom[64 * LSK_BINOM_K];
-    if (ix.kind == LSK_INDEX_COMBINADIC) load_binom(s_binom, ix.binom);
+    if (ix.kind == LSK_INDEX_COMBINADIC || ix.kind == LSK_INDEX_PRODUCT) load_binom(s_binom, ix.binom);
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         uint64_t s = spins[i];
         int64_t idx;
@@ -302,7 +302,8 @@ __global__ __launch_bounds__(kBlock) void k_state_index(lsk_index ix, int64_t n,
             idx = rank_combinadic(s, s_binom);
             // membership: the basis is the first `count` states of one popcount class
             if (idx >= ix.count || __popcll(s) != __popcll(ix.reps[0])) idx = -1;
-        } else idx = search_index(ix, s);
+        } else if (ix.kind == LSK_INDEX_PRODUCT) idx = product_index(ix, s, s_binom);
+        else idx = search_index(ix, s);
         indices[i] = idx;
     }
 }
@@ -662,6 +663,50 @@ __global__ __launch_bounds__(kBlock) void k_enum_write(lsk_basis bs, uint64_t co
             if (c + 1 < c1) s = (bs.hamming_weight > 0) ? next_fixed_hamming(s) : s + 1;
         }
     }
+}
+
+// The spinful product basis (fixed N_up, N_down): row i = b n_a + a holds unrank(b) << L | unrank(a) -- ascending, since the down
+// word is the high half and colex order of one weight is numeric order.  (StatesEnumeration.chpl:225-266 is the reference's branch;
+// it sizes the output by a countA that is always 1 -- all n_a n_b states are written here.)
+__global__ __launch_bounds__(kBlock) void k_enum_product(int L, int n_up, int n_dn, int64_t n_a, int64_t n,
+                                                         uint64_t const *__restrict__ g_binom, uint64_t *__restrict__ out) {
+    __shared__ uint64_t s_binom[64 * LSK_BINOM_K];
+    load_binom(s_binom, g_binom);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t b = i / n_a, a = i - b * n_a;
+        out[i] = (unrank_combinadic(b, n_dn, s_binom) << L) | unrank_combinadic(a, n_up, s_binom);
+    }
+}
+extern "C" int lsk_enumerate_product(int L, int n_up, int n_dn, uint64_t const *d_binom, uint64_t **d_states, int64_t *count,
+                                     void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    *d_states = nullptr;
+    *count = 0;
+    if (L < 1 || L > 32 || n_up < 0 || n_up > L || n_dn < 0 || n_dn > L) { snprintf(g_err, sizeof(g_err), "lsk_enumerate_product: bad shape"); return -1; }
+    uint64_t h_binom[2];
+    LSK_CHECK(hipMemcpy(&h_binom[0], d_binom + (size_t)L * LSK_BINOM_K + n_up, 8, hipMemcpyDeviceToHost));
+    LSK_CHECK(hipMemcpy(&h_binom[1], d_binom + (size_t)L * LSK_BINOM_K + n_dn, 8, hipMemcpyDeviceToHost));
+    const int64_t n_a = (int64_t)h_binom[0], n = n_a * (int64_t)h_binom[1];
+    void *p = nullptr;
+    LSK_CHECK(hipMalloc(&p, 8 * (size_t)(n > 0 ? n : 1)));
+    *d_states = (uint64_t *)p;
+    hipLaunchKernelGGL(k_enum_product, dim3(grid_for(n)), dim3(kBlock), 0, s, L, n_up, n_dn, n_a, n, d_binom, *d_states);
+    LSK_LAUNCH_CHECK();
+    LSK_CHECK(hipStreamSynchronize(s));
+    *count = n;
+    return 0;
+}
+__global__ __launch_bounds__(kBlock) void k_check_product(lsk_index ix, int64_t n, uint64_t const *__restrict__ reps, int *flag) {
+    __shared__ uint64_t s_binom[64 * LSK_BINOM_K];
+    load_binom(s_binom, ix.binom);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        if (product_index(ix, reps[i], s_binom) != i) atomicExch(flag, 1);
+}
+extern "C" int lsk_check_product(lsk_index ix, int64_t n, uint64_t const *reps, int *d_flag, void *stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_check_product, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, ix, n, reps, d_flag);
+    LSK_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int lsk_enumerate(lsk_basis bs, uint64_t const *d_binom, int64_t n_cand, uint64_t **d_states,

@@ -76,8 +76,8 @@ __global__ __launch_bounds__(kBlock) void k_direct(lsk_runs runs, int n_groups, 
                                                    int64_t const *__restrict__ row_gidx) {
     typedef typename WordTraits<W>::binom_t BT;
     typedef WordTraits<W> WT;
-    __shared__ BT s_binom[INDEX == LSK_INDEX_COMBINADIC ? 64 * LSK_BINOM_K : 1];
-    if (INDEX == LSK_INDEX_COMBINADIC) {
+    __shared__ BT s_binom[(INDEX == LSK_INDEX_COMBINADIC || INDEX == LSK_INDEX_PRODUCT) ? 64 * LSK_BINOM_K : 1];
+    if (INDEX == LSK_INDEX_COMBINADIC || INDEX == LSK_INDEX_PRODUCT) {
         for (int k = threadIdx.x; k < 64 * LSK_BINOM_K; k += blockDim.x) s_binom[k] = (BT)ix.binom[k];
         __syncthreads();
     }
@@ -96,6 +96,7 @@ __global__ __launch_bounds__(kBlock) void k_direct(lsk_runs runs, int n_groups, 
         if (gx & 1) {
             if (INDEX == LSK_INDEX_COMBINADIC) ig = rank_combinadic_w<W, BT>(a, s_binom);
             else if (INDEX == LSK_INDEX_IDENTITY) ig = (int64_t)a;
+            else if constexpr (INDEX == LSK_INDEX_PRODUCT) ig = product_index(ix, (uint64_t)a, s_binom);
             else ig = row_gidx[i];
         }
         double xr, xi = 0.0;
@@ -250,6 +251,9 @@ __global__ __launch_bounds__(kBlock) void k_direct(lsk_runs runs, int n_groups, 
                     if (WT::popc(beta) != bs.hamming_weight) { atomicExch(err, 1); continue; }
                     idx = rank_combinadic_w<W, BT>(beta, s_binom);
                 }
+            } else if constexpr (INDEX == LSK_INDEX_PRODUCT) { // spinful product basis: two closed-form ranks (lsk.h)
+                idx = product_index(ix, (uint64_t)beta, s_binom);
+                if (idx < 0) { atomicExch(err, 1); continue; } // DMV:115-118
             } else {
                 idx = search_index(ix, (uint64_t)beta);
                 if (idx < 0) { atomicExch(err, 1); continue; } // DMV:115-118
@@ -348,6 +352,12 @@ static int direct_dispatch(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx
     case LSK_INDEX_COMBINADIC:
         return cplx ? launch_direct1<true, LSK_INDEX_COMBINADIC>(op, bs, ix, pull, n, reps, x, y, d_err, stream, gx, row_gidx)
                     : launch_direct1<false, LSK_INDEX_COMBINADIC>(op, bs, ix, pull, n, reps, x, y, d_err, stream, gx, row_gidx);
+    case LSK_INDEX_PRODUCT:
+        if (bs.proj != LSK_PROJ_NONE) { snprintf(g_err, sizeof(g_err), "lsk_direct: product index on a projected basis"); return -1; }
+        if (pull) return cplx ? launch_direct3<uint64_t, true, LSK_INDEX_PRODUCT, false, true>(op, bs, ix, n, reps, x, y, d_err, stream, gx, row_gidx)
+                              : launch_direct3<uint64_t, false, LSK_INDEX_PRODUCT, false, true>(op, bs, ix, n, reps, x, y, d_err, stream, gx, row_gidx);
+        return cplx ? launch_direct3<uint64_t, true, LSK_INDEX_PRODUCT, false, false>(op, bs, ix, n, reps, x, y, d_err, stream, gx, row_gidx)
+                    : launch_direct3<uint64_t, false, LSK_INDEX_PRODUCT, false, false>(op, bs, ix, n, reps, x, y, d_err, stream, gx, row_gidx);
     default:
         return cplx ? launch_direct1<true, LSK_INDEX_SEARCH>(op, bs, ix, pull, n, reps, x, y, d_err, stream, gx, row_gidx)
                     : launch_direct1<false, LSK_INDEX_SEARCH>(op, bs, ix, pull, n, reps, x, y, d_err, stream, gx, row_gidx);
@@ -370,6 +380,7 @@ __global__ __launch_bounds__(kBlock) void k_direct_validate(int n_groups, lsk_gr
             bool inside;
             if (INDEX == LSK_INDEX_IDENTITY) inside = (beta & ~bs.site_mask) == 0;
             else if (INDEX == LSK_INDEX_COMBINADIC) inside = __popcll(beta) == bs.hamming_weight && (beta & ~bs.site_mask) == 0;
+            else if (INDEX == LSK_INDEX_PRODUCT) inside = product_index(ix, beta, ix.binom) >= 0;
             else inside = search_index(ix, beta) >= 0;
             if (!inside) atomicExch(err, 1);
         }
@@ -381,6 +392,7 @@ extern "C" int lsk_direct_validate(lsk_operator op, lsk_basis bs, lsk_index ix, 
     hipStream_t s = (hipStream_t)stream;
     if (ix.kind == LSK_INDEX_IDENTITY) hipLaunchKernelGGL(k_direct_validate<LSK_INDEX_IDENTITY>, g, b, 0, s, op.n_groups, op.groups, op.off, bs, ix, n, reps, d_err);
     else if (ix.kind == LSK_INDEX_COMBINADIC) hipLaunchKernelGGL(k_direct_validate<LSK_INDEX_COMBINADIC>, g, b, 0, s, op.n_groups, op.groups, op.off, bs, ix, n, reps, d_err);
+    else if (ix.kind == LSK_INDEX_PRODUCT) hipLaunchKernelGGL(k_direct_validate<LSK_INDEX_PRODUCT>, g, b, 0, s, op.n_groups, op.groups, op.off, bs, ix, n, reps, d_err);
     else hipLaunchKernelGGL(k_direct_validate<LSK_INDEX_SEARCH>, g, b, 0, s, op.n_groups, op.groups, op.off, bs, ix, n, reps, d_err);
     LSK_LAUNCH_CHECK();
     return 0;
@@ -1449,3 +1461,81 @@ extern "C" int lsk_narrow_states(int64_t n, uint64_t const *reps, uint32_t *out,
 
 
 
+
+// ---------------------------------------------------------------------------------------------
+// Species-split row kernel (k_hubbard): pull over the spinful product basis (lsk.h, LSK_INDEX_PRODUCT) for an operator whose
+// off-diagonal terms each live inside one species half -- hopping of any range and phase, one-species density-assisted terms --
+// and any diagonal.  Reading x as an n_b x n_a matrix X (row i = b n_a + a):
+//   y[b, a] = d(state) x[b, a] + sum_k cu[k][a] x[b, ru[k][a]] + sum_k cd[k][b] x[rd[k][b], a]
+// Partner ranks are O(1) table reads (one table per species, O(sqrt N) entries: the path stays matrix-free).  Consecutive lanes
+// hold consecutive a: the up partners are gathers inside the row's own strip X[b, :] (n_a entries, L2-resident while a block
+// walks it), the down partners are coalesced reads of the same a-range in other strips.  Padding slots carry amplitude 0 and the
+// row's own rank, so every lane runs the same trip count.  Tiles come from the host's tile map (XCD dealing, as in k_direct).
+// ---------------------------------------------------------------------------------------------
+template <bool CPLX, bool CCOEF>
+__global__ __launch_bounds__(kBlock) void k_hubbard(lsk_hubbard hb, lsk_runs runs, int n_diag, lsk_term const *__restrict__ diag,
+                                                    uint64_t const *__restrict__ tilemap, int64_t slots_per_xcd,
+                                                    double const *__restrict__ x, double *y) {
+    const int xcd = blockIdx.x & 7;
+    const int64_t blocks_per_xcd = gridDim.x >> 3; // grid is a multiple of 8
+    const int64_t n_a = hb.up.n, n_b = hb.dn.n;
+    tilemap += (int64_t)xcd * slots_per_xcd;
+    for (int64_t t = blockIdx.x >> 3; t < slots_per_xcd; t += blocks_per_xcd) {
+        const uint64_t slot = tilemap[t];
+        if ((uint64_t)threadIdx.x >= (slot >> 48)) continue;
+        const int64_t i = (int64_t)(slot & 0xffffffffffffULL) + threadIdx.x;
+        const int64_t b = i / n_a, a = i - b * n_a;
+        const int64_t strip = b * n_a;
+        const uint64_t st = ((uint64_t)hb.dn.words[b] << hb.L) | (uint64_t)hb.up.words[a];
+        double dr, di;
+        diag_coeff<uint64_t, !CCOEF>(runs, n_diag, diag, st, dr, di);
+        double accr, acci = 0.0;
+        if (CPLX) {
+            const double xr = x[2 * i], xi = x[2 * i + 1];
+            accr = dr * xr - di * xi;
+            acci = dr * xi + di * xr;
+        } else accr = dr * x[i];
+        if (n_diag == 0) { // no diagonal pass in the reference either: y is accumulated into (DMV:1062-1063), as in k_direct
+            if (CPLX) { accr = y[2 * i]; acci = y[2 * i + 1]; } else accr = y[i];
+        }
+        for (int k = 0; k < hb.up.deg; ++k) {
+            const int64_t e = (int64_t)k * n_a + a;
+            const int64_t j = strip + hb.up.rank[e];
+            if (CPLX) {
+                const double xr = x[2 * j], xi = x[2 * j + 1];
+                const double cr = CCOEF ? hb.up.coef[2 * e] : hb.up.coef[e], ci = CCOEF ? hb.up.coef[2 * e + 1] : 0.0;
+                accr += cr * xr - ci * xi;
+                acci += cr * xi + ci * xr;
+            } else accr = fma(hb.up.coef[e], x[j], accr);
+        }
+        for (int k = 0; k < hb.dn.deg; ++k) {
+            const int64_t e = (int64_t)k * n_b + b;
+            const int64_t j = (int64_t)hb.dn.rank[e] * n_a + a;
+            if (CPLX) {
+                const double xr = x[2 * j], xi = x[2 * j + 1];
+                const double cr = CCOEF ? hb.dn.coef[2 * e] : hb.dn.coef[e], ci = CCOEF ? hb.dn.coef[2 * e + 1] : 0.0;
+                accr += cr * xr - ci * xi;
+                acci += cr * xi + ci * xr;
+            } else accr = fma(hb.dn.coef[e], x[j], accr);
+        }
+        if (CPLX) { y[2 * i] = accr; y[2 * i + 1] = acci; } else __builtin_nontemporal_store(accr, y + i);
+    }
+}
+template <bool CPLX, bool CCOEF>
+static int launch_hubbard(lsk_hubbard hb, lsk_operator op, lsk_tilemap tm, void const *x, void *y, void *stream) {
+    int64_t gb = tm.slots_per_xcd * 8;
+    int64_t cap = resident_grid(k_hubbard<CPLX, CCOEF>, gb);
+    cap &= ~(int64_t)7; // XCD dealing needs a multiple of 8
+    if (cap < 8) cap = 8;
+    if (gb > cap) gb = cap;
+    hipLaunchKernelGGL((k_hubbard<CPLX, CCOEF>), dim3((unsigned)gb), dim3(kBlock), 0, (hipStream_t)stream, hb, op.runs, op.n_diag,
+                       op.diag, tm.entries, tm.slots_per_xcd, (double const *)x, (double *)y);
+    LSK_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int lsk_hubbard_apply(lsk_hubbard hb, lsk_operator op, int cplx, lsk_tilemap tm, void const *x, void *y, void *stream) {
+    if (tm.slots_per_xcd == 0) return 0;
+    if (!tm.entries || (!cplx && hb.cplx_coef)) { snprintf(g_err, sizeof(g_err), "lsk_hubbard_apply: plan out of range"); return -1; }
+    if (cplx) return hb.cplx_coef ? launch_hubbard<true, true>(hb, op, tm, x, y, stream) : launch_hubbard<true, false>(hb, op, tm, x, y, stream);
+    return launch_hubbard<false, false>(hb, op, tm, x, y, stream);
+}

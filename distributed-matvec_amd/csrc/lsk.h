@@ -104,7 +104,9 @@ typedef struct lsk_basis {
     lsk_group_elem const *elems; /* device [n_elems] */
 } lsk_basis;
 
-enum { LSK_INDEX_IDENTITY = 0, LSK_INDEX_COMBINADIC = 1, LSK_INDEX_SEARCH = 2 };
+/* PRODUCT: the spinful-fermion basis with fixed (N_up, N_down) on L sites -- index = rank(high L bits) * n_low + rank(low L bits),
+ * two colex ranks (prod_* fields of lsk_index); -1 when a half has the wrong weight */
+enum { LSK_INDEX_IDENTITY = 0, LSK_INDEX_COMBINADIC = 1, LSK_INDEX_SEARCH = 2, LSK_INDEX_PRODUCT = 3 };
 
 /* Rank directory of a hash partition of an unprojected fixed-weight basis (optional part of a SEARCH index): the global
  * (colex) rank g of a state is closed-form, and the local index is the number of this partition's states below it --
@@ -125,6 +127,8 @@ typedef struct lsk_index {
     uint64_t const *binom; /* device [64 * LSK_BINOM_K] */
     lsk_rankdir const *dir; /* device [ceil(C(dir_sites, dir_weight) / 64)] or NULL */
     int dir_sites, dir_weight;
+    int prod_sites, prod_up, prod_dn; /* PRODUCT: L, weight of the low / high half */
+    int64_t prod_na;                  /* PRODUCT: C(L, prod_up) */
 } lsk_index;
 /* dir[] for the n ascending states `reps` (all of weight `weight` on `sites` sites), entries = ceil(C(sites, weight) / 64); *d_flag is
  * raised if a state has another weight or the directory does not give reps[i] -> i back */
@@ -294,6 +298,22 @@ int lsk_push_staged(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, lsk_t
                     void const *x, void *y, int *d_err, void *stream);
 int lsk_pairs_tile_rows(int cplx);
 int lsk_pairs(lsk_pairplan pp, int hamming_weight, int cplx, lsk_tilemap tm, int64_t n, void const *x, void *y, void *stream);
+/* ---- species-split row kernel (k_hubbard, k_rows.hip): pull over the spinful product basis, every off-diagonal term inside one
+ * species half.  Row i = b * n_a + a (a: colex rank of the up word, b: of the down word); per species a neighbour table in
+ * [slot][rank] layout -- partner rank (u32) and the matrix element <row|H|partner> (f64, or (re, im) pairs when cplx_coef) --
+ * padded with zero amplitudes to `deg` slots; words[] are the species words by rank.  Diagonal terms come from op. */
+typedef struct lsk_species {
+    int64_t n;                  /* C(L, weight) */
+    int deg;                    /* slots per word */
+    uint32_t const *words;      /* device [n] */
+    uint32_t const *rank;       /* device [deg][n] */
+    double const *coef;         /* device [deg][n] (x2 when cplx_coef) */
+} lsk_species;
+typedef struct lsk_hubbard {
+    int L, cplx_coef;
+    lsk_species up, dn;
+} lsk_hubbard;
+int lsk_hubbard_apply(lsk_hubbard hb, lsk_operator op, int cplx, lsk_tilemap tm, void const *x, void *y, void *stream);
 int lsk_narrow_states(int64_t n, uint64_t const *reps, uint32_t *out, void *stream);
 
 /* fused_records != 0 (32-bit states and ranks): `reps` is out[] of lsk_chain_pack -- state | partner rank of the first
@@ -495,6 +515,10 @@ int lsk_exclusive_scan_i64(int64_t n, int64_t const *in, int64_t *out, void *str
 /* number of candidate states (fixed-Hamming rank space or 2^L), given the top-bit cut */
 int lsk_enumerate(lsk_basis bs, uint64_t const *d_binom, int64_t n_candidates, uint64_t **d_states,
                   int64_t *count, void *stream);
+/* the spinful product basis in ascending order: state = unrank(b, n_dn) << L | unrank(a, n_up), b outer, a inner */
+int lsk_enumerate_product(int L, int n_up, int n_dn, uint64_t const *d_binom, uint64_t **d_states, int64_t *count, void *stream);
+/* *d_flag = 1 unless reps[i] is the i-th state of the product basis of ix (PRODUCT index) for all i < n */
+int lsk_check_product(lsk_index ix, int64_t n, uint64_t const *reps, int *d_flag, void *stream);
 int lsk_masks(int64_t n, uint64_t const *states, int P, uint8_t *masks, void *stream);
 int lsk_mask_counts(int64_t n, uint8_t const *masks, int P, int64_t *h_counts, void *stream);
 int lsk_block_to_hashed(int64_t n, uint8_t const *masks, int P, int elt_size, void const *src,

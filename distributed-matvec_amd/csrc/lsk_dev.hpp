@@ -837,6 +837,13 @@ __device__ __forceinline__ int64_t rank_combinadic_w(W s, BT const *binom) {
     return idx;
 }
 
+// PRODUCT index (lsk.h): two colex ranks of the species halves, -1 when a half has the wrong weight or a bit at or above 2 L is set
+__device__ __forceinline__ int64_t product_index(lsk_index const &ix, uint64_t s, uint64_t const *binom) {
+    const uint64_t lo = s & ((1ULL << ix.prod_sites) - 1), hi = s >> ix.prod_sites; // (prod_sites <= 32)
+    if ((hi >> ix.prod_sites) != 0 || __popcll(lo) != ix.prod_up || __popcll(hi) != ix.prod_dn) return -1;
+    return rank_combinadic(hi, binom) * ix.prod_na + rank_combinadic(lo, binom);
+}
+
 // diagonal coefficient with the zz-run shortcut: sum_b v (-1)^{[bits b, b+1 differ]} = v (cnt - 2 #differ)
 template <typename W, bool REAL>
 __device__ __forceinline__ void diag_coeff(lsk_runs const &runs, int n_diag, lsk_term const *__restrict__ diag,

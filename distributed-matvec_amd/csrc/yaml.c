@@ -8,7 +8,10 @@
  *
  *   basis:        number_spins, hamming_weight (int | null), spin_inversion (1 | -1 | absent), particle (spin-1/2),
  *                 symmetries: [{permutation: [...], sector: int}]
+ *                 or particle: spinless-fermion | spinful-fermion, number_sites, number_particles (int | null),
+ *                 number_up (spinful only; int | null)
  *   hamiltonian:  terms: [{expression: "0.8 × σˣ₀ σˣ₁", sites: [[i, j], ...]}]     (other keys hold YAML anchors)
+ *                 fermionic bases: c†ᵢσ, cᵢσ, nᵢσ (σ = ↑ | ↓ for spinful fermions, absent for spinless ones)
  *   observables:  [ {terms: ...}, ... ]                                              (always empty in the reference's files)
  *
  * Syntax handled: block mappings and block sequences by indentation, flow sequences and mappings (nested, over several lines),
@@ -542,6 +545,95 @@ static int monomial_terms(char const *expr, int const *sites, int n_sites, int n
     return 0;
 }
 
+/* Fermionic monomials ("-1 × c†₀↑ c₁↑", "n₀↑ n₀↓"; spinless: no arrow), by the convention of include/ls_hs.h and the Python mirror
+ * (config.fermion_monomial_terms): mode (i, up) = bit i, (i, down) = bit i + L; one term per occupation pattern of the touched
+ * modes, sign mask = XOR of the "modes below k" masks of the c / c+ factors without the touched modes, their parity folded into v */
+typedef struct { char kind; int idx, spin; } ffactor; /* kind: '+' creation, '-' annihilation, 'n' number */
+static int parse_fermion_expression(char const *expr, int spinful, cplx *scalar, ffactor *f, int *nf) {
+    scalar->re = 1.0; scalar->im = 0.0;
+    *nf = 0;
+    char const *p = expr;
+    while (*p) {
+        while (*p == ' ' || *p == '\t' || *p == '*') ++p;
+        if (utf8_starts(p, "\xc3\x97")) { p += 2; continue; } /* the multiplication sign */
+        if (!*p) break;
+        if (*p == 'c' || *p == 'n') {
+            char kind = *p == 'n' ? 'n' : '-';
+            ++p;
+            if (kind == '-' && utf8_starts(p, "\xe2\x80\xa0")) { kind = '+'; p += 3; } /* the dagger */
+            int idx = 0, digits = 0, spin = -1;
+            while ((unsigned char)p[0] == 0xe2 && (unsigned char)p[1] == 0x82 && (unsigned char)p[2] >= 0x80 && (unsigned char)p[2] <= 0x89) {
+                idx = idx * 10 + ((unsigned char)p[2] - 0x80);
+                p += 3;
+                if (++digits > 6) return ls_amd_internal_error("site index too long in the expression '%s'", expr);
+            }
+            if (utf8_starts(p, "\xe2\x86\x91")) { spin = 0; p += 3; }      /* up arrow */
+            else if (utf8_starts(p, "\xe2\x86\x93")) { spin = 1; p += 3; } /* down arrow */
+            if (!digits || (*p && *p != ' ' && *p != '\t' && *p != '*')) return ls_amd_internal_error("cannot parse site index in the expression '%s'", expr);
+            if (spinful && spin < 0) return ls_amd_internal_error("spinful-fermion operator in '%s' needs a spin index (up or down arrow)", expr);
+            if (!spinful && spin >= 0) return ls_amd_internal_error("spinless-fermion operator in '%s' takes no spin index", expr);
+            if (*nf >= MAX_FACTORS) return ls_amd_internal_error("too many factors in the expression '%s'", expr);
+            f[*nf].kind = kind; f[*nf].idx = idx; f[*nf].spin = spin < 0 ? 0 : spin;
+            ++*nf;
+        } else if (utf8_starts(p, "\xcf\x83") || *p == 'S') {
+            return ls_amd_internal_error("spin operator in a fermionic expression '%s'", expr);
+        } else {
+            char *end;
+            double const v = strtod(p, &end);
+            if (end == p) return ls_amd_internal_error("cannot parse '%s' in the expression '%s'", p, expr);
+            cplx sc = {v, 0.0};
+            if (*end == 'j' || *end == 'i') { sc.re = 0.0; sc.im = v; ++end; }
+            else if (*end == '+' || *end == '-') { /* a complex literal "a+bj" (Python's complex()), one token */
+                char *end2;
+                double const w = strtod(end, &end2);
+                if (end2 != end && (*end2 == 'j' || *end2 == 'i')) { sc.im = w; end = end2 + 1; }
+            }
+            *scalar = c_mul(*scalar, sc);
+            p = end;
+        }
+    }
+    if (*nf == 0) return ls_amd_internal_error("the expression '%s' has no operators", expr);
+    return 0;
+}
+static int fermion_monomial_terms(char const *expr, int const *sites, int n_sites, int number_sites, int spinful, term_list *out) {
+    cplx scalar;
+    ffactor f[MAX_FACTORS];
+    int nf, max_idx = -1;
+    if (parse_fermion_expression(expr, spinful, &scalar, f, &nf) != 0) return -1;
+    for (int q = 0; q < nf; ++q) if (f[q].idx > max_idx) max_idx = f[q].idx;
+    if (n_sites != max_idx + 1) return ls_amd_internal_error("the expression '%s' needs %d sites, got %d", expr, max_idx + 1, n_sites);
+    for (int i = 0; i < n_sites; ++i) {
+        if (sites[i] < 0 || sites[i] >= number_sites) return ls_amd_internal_error("site %d out of range in the sites of '%s'", sites[i], expr);
+        for (int j = 0; j < i; ++j) if (sites[i] == sites[j]) return ls_amd_internal_error("repeated site %d in the sites of '%s'", sites[i], expr);
+    }
+    int mode[MAX_FACTORS], touched[MAX_FACTORS], n_touched = 0;
+    uint64_t M = 0, smask = 0;
+    for (int q = 0; q < nf; ++q) {
+        mode[q] = sites[f[q].idx] + (f[q].spin ? number_sites : 0);
+        uint64_t const bit = 1ULL << mode[q];
+        if (!(M & bit)) touched[n_touched++] = mode[q];
+        M |= bit;
+        if (f[q].kind != 'n') smask ^= bit - 1;
+    }
+    smask &= ~M;
+    for (uint64_t pat = 0; pat < (1ULL << n_touched); ++pat) {
+        uint64_t r = 0;
+        for (int j = 0; j < n_touched; ++j) if ((pat >> j) & 1) r |= 1ULL << touched[j];
+        uint64_t occ = r;
+        cplx v = scalar;
+        int alive = 1;
+        for (int q = nf - 1; q >= 0 && alive; --q) { /* written left to right, acting right to left */
+            uint64_t const bit = 1ULL << mode[q];
+            if (f[q].kind == 'n') { alive = (occ & bit) != 0; continue; }
+            if ((f[q].kind == '+') == ((occ & bit) != 0)) { alive = 0; continue; }
+            if (__builtin_popcountll(occ & M & (bit - 1)) & 1) { v.re = -v.re; v.im = -v.im; }
+            occ ^= bit;
+        }
+        if (alive && (v.re != 0.0 || v.im != 0.0)) terms_push(out, v, M, r, r ^ occ, smask);
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------------------------------------ */
 /* document -> objects                                                                              */
 /* ------------------------------------------------------------------------------------------------ */
@@ -555,18 +647,50 @@ static int y_int(ynode const *n, char const *what, long *out) {
     *out = v;
     return 0;
 }
+/* a key that is absent, null, 0 or an empty collection (what the Python mirror's truth test lets through) */
+static int y_is_unset(ynode const *n) {
+    if (y_is_null(n)) return 1;
+    if (n->kind == Y_SCALAR) return n->str && strcmp(n->str, "0") == 0;
+    return n->n == 0;
+}
+/* particle: spinless-fermion | spinful-fermion -- number_sites, number_particles (null: unrestricted), number_up (spinful; null:
+ * only number_particles fixed); no symmetries */
+static ls_hs_basis *fermion_basis_from(ynode const *b, char const *particle) {
+    int const spinful = strcmp(particle, "spinful-fermion") == 0;
+    if (y_get(b, "number_spins")) {
+        ls_amd_internal_error("number_spins is a key of spin-1/2 bases, not of particle '%s' (use number_sites)", particle); return NULL;
+    }
+    static char const *const unsupported[] = {"hamming_weight", "spin_inversion", "symmetries"};
+    for (int k = 0; k < 3; ++k)
+        if (!y_is_unset(y_get(b, unsupported[k]))) { ls_amd_internal_error("%s is not supported for particle '%s'", unsupported[k], particle); return NULL; }
+    long L, n = -1, nup = -1;
+    if (!y_get(b, "number_sites")) { ls_amd_internal_error("particle '%s' needs number_sites", particle); return NULL; }
+    if (y_int(y_get(b, "number_sites"), "basis.number_sites", &L) != 0) return NULL;
+    if (!y_is_null(y_get(b, "number_particles")) && y_int(y_get(b, "number_particles"), "basis.number_particles", &n) != 0) return NULL;
+    if (!y_is_null(y_get(b, "number_up"))) {
+        if (!spinful) { ls_amd_internal_error("number_up is a key of spinful-fermion bases"); return NULL; }
+        if (y_int(y_get(b, "number_up"), "basis.number_up", &nup) != 0) return NULL;
+        if (n < 0) { ls_amd_internal_error("a fixed number_up needs a fixed number_particles"); return NULL; }
+    }
+    return ls_hs_create_basis(spinful ? LS_HS_SPINFUL_FERMION : LS_HS_SPINLESS_FERMION, (int)L, (int)n, (int)nup);
+}
 static ls_hs_basis *basis_from(ynode const *b) {
     if (!b || b->kind != Y_MAP) { ls_amd_internal_error("the config has no `basis` section"); return NULL; }
+    ynode const *particle = y_get(b, "particle");
+    if (particle && !y_is_null(particle)) {
+        if (particle->kind != Y_SCALAR || !particle->str ||
+            (strcmp(particle->str, "spin-1/2") != 0 && strcmp(particle->str, "spinless-fermion") != 0 && strcmp(particle->str, "spinful-fermion") != 0)) {
+            ls_amd_internal_error("unknown particle '%s' (spin-1/2, spinful-fermion or spinless-fermion)",
+                                  particle->kind == Y_SCALAR && particle->str ? particle->str : "<a collection>");
+            return NULL;
+        }
+        if (strcmp(particle->str, "spin-1/2") != 0) return fermion_basis_from(b, particle->str);
+    }
     long L, hw = -1, inv = 0;
     if (y_int(y_get(b, "number_spins"), "basis.number_spins", &L) != 0) return NULL;
     if (L < 1 || L > 64) { ls_amd_internal_error("basis.number_spins = %ld: 1 .. 64 sites are supported", L); return NULL; }
     if (!y_is_null(y_get(b, "hamming_weight")) && y_int(y_get(b, "hamming_weight"), "basis.hamming_weight", &hw) != 0) return NULL;
     if (!y_is_null(y_get(b, "spin_inversion")) && y_int(y_get(b, "spin_inversion"), "basis.spin_inversion", &inv) != 0) return NULL;
-    ynode const *particle = y_get(b, "particle");
-    if (particle && !y_is_null(particle) && (particle->kind != Y_SCALAR || !particle->str || strcmp(particle->str, "spin-1/2") != 0)) {
-        ls_amd_internal_error("only spin-1/2 bases are supported, got '%s'", particle->kind == Y_SCALAR && particle->str ? particle->str : "<a collection>");
-        return NULL;
-    }
     ynode const *syms = y_get(b, "symmetries");
     int ng = 0;
     int *perms = NULL, *sectors = NULL;
@@ -619,7 +743,10 @@ static ls_hs_operator *operator_from(ls_hs_basis const *basis, ynode const *sect
                 bad = y_int(tuple->vals[i], "sites", &v) != 0;
                 idx[i] = (int)v;
             }
-            if (bad || monomial_terms(expr->str, idx, tuple->n, basis->number_sites, &tl) != 0) {
+            int const fermionic = basis->particle_type != LS_HS_SPIN;
+            if (bad || (fermionic ? fermion_monomial_terms(expr->str, idx, tuple->n, basis->number_sites,
+                                                           basis->particle_type == LS_HS_SPINFUL_FERMION, &tl)
+                                  : monomial_terms(expr->str, idx, tuple->n, basis->number_sites, &tl)) != 0) {
                 if (bad) ls_amd_internal_error("%s.terms[%d].sites[%d]: expected a tuple of site indices", what, t, q);
                 terms_free(&tl);
                 return NULL;

@@ -102,6 +102,19 @@ void ls_hs_exit(void);  /* FFI.chpl:129 */
 ls_hs_basis *ls_hs_create_spin_basis(int number_sites, int hamming_weight, int spin_inversion,
                                      int number_generators, int const *permutations,
                                      int const *sectors);
+/* FFI.chpl:143-144 (declared there, commented out).  Any particle type, no symmetries:
+ *   LS_HS_SPIN               number_up = Hamming weight or -1 (number_particles ignored)
+ *   LS_HS_SPINLESS_FERMION   L <= 64 modes, mode i = bit i; number_particles fixed or -1; number_up must be -1
+ *   LS_HS_SPINFUL_FERMION    L <= 32 sites, 2 L modes: mode (i, up) = bit i, mode (i, down) = bit i + L
+ *                            (number_particles, number_up) both fixed: the product basis, N_up bits set in the low half and
+ *                            N - N_up in the high half; number_up = -1: every word of number_particles bits (or -1: all words)
+ * Fermionic sign convention (what the expression compilers -- csrc/yaml.c and its mirror distributed-matvec_amd/config.py -- emit): modes are ordered by bit
+ * position and
+ *   c+_k |n> = (-1)^{sum_{k' < k} n_k'} |n + e_k>,    c_k |n> = (-1)^{sum_{k' < k} n_k'} |n - e_k>,
+ * so a monomial is ONE term (v, m, r, x, s) per projector pattern whose sign mask s is the XOR of the "modes below k" masks of its
+ * factors with the modes the monomial itself touches removed (their occupations are fixed by m / r and folded into v).  For
+ * c+_i c_j that makes s the modes strictly between i and j. */
+ls_hs_basis *ls_hs_create_basis(ls_hs_particle_type particle_type, int number_sites, int number_particles, int number_up);
 ls_hs_basis *ls_hs_clone_basis(ls_hs_basis const *basis);       /* FFI.chpl:141 */
 void ls_hs_destroy_basis(ls_hs_basis *basis);                   /* FFI.chpl:142 */
 
@@ -124,7 +137,8 @@ typedef struct ls_hs_yaml_config {
 } ls_hs_yaml_config;
 /* /root/reference/src/FFI.chpl:208-209.  The YAML subset of the YAML files under /root/reference/data (basis: number_spins, hamming_weight,
  * spin_inversion, symmetries; hamiltonian / observables: terms of `expression` + `sites`; anchors and aliases, block and
- * flow collections).  NULL on failure, with the reason in ls_amd_last_error(). */
+ * flow collections), and fermionic bases (particle: spinless-fermion | spinful-fermion, number_sites, number_particles,
+ * number_up; expressions of c+ / c / n, see ls_hs_create_basis).  NULL on failure, with the reason in ls_amd_last_error(). */
 ls_hs_yaml_config *ls_hs_load_yaml_config(char const *filename);
 void ls_hs_destroy_yaml_config(ls_hs_yaml_config *config);
 /* the same from a NUL-terminated YAML text in memory (not in the reference's ABI) */
