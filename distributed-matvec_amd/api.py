@@ -442,6 +442,37 @@ class MatvecPlan:
         if check:
             self.check()
 
+    def matvec_block(self, x, y, check: bool = True):
+        """Y[:, k] <- H X[:, k] for the K columns of the (N, K) device tensors x and y (ls_amd_matvec_block): any strides -- (K, 1)
+        interleaved is the fast layout, a transposed (K, N) tensor the column-major one -- and the plan's dtype.  One-partition
+        plans, 1 <= K <= 64; y is assigned.  LS_AMD_BLOCK=auto|kernel|columns picks the path (block_kernel(K) names it)."""
+        torch = _torch()
+        if self.P != 1 or self.me >= 0:
+            raise _lib.LsAmdError(f"matvec_block: one-partition plans only (this plan has P = {self.P}, my_partition = {self.me})")
+        want = torch.complex128 if self.cplx else torch.float64
+        for name, t in (("x", x), ("y", y)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise _lib.LsAmdError(f"matvec_block: {name} must be a 2-D (N, K) tensor")
+            if t.dtype != want:
+                raise _lib.LsAmdError(f"matvec_block: {name} is {t.dtype}, the plan computes in {want}")
+            if t.device.type != "cuda":
+                raise _lib.LsAmdError(f"matvec_block: {name} must be a device tensor")
+        n = self.reps[0].numel()
+        if tuple(x.shape) != tuple(y.shape) or x.shape[0] != n:
+            raise _lib.LsAmdError(f"matvec_block: x {tuple(x.shape)} and y {tuple(y.shape)} must both be ({n}, K)")
+        K = int(x.shape[1])
+        _lib.check(_lib.load().ls_amd_matvec_block(self.h, K, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
+                                                   C.c_void_p(y.data_ptr()), y.stride(0), y.stride(1), _stream_ptr()))
+        if check:
+            self.check()
+
+    def block_kernel(self, K: int) -> str:
+        """path a block of K columns takes on this plan: "k_direct_blk", "k_pull_gather_blk" or "columns" """
+        name = _lib.load().ls_amd_plan_block_kernel_name(self.h, int(K))
+        if name is None:
+            _lib.check(-1)
+        return name.decode()
+
     def check(self):
         _lib.check(_lib.load().ls_amd_plan_check(self.h, _stream_ptr()))
 

@@ -1610,6 +1610,14 @@ struct ls_amd_plan {
      * HBM for one-amplitude operators, 13 / 21 with real / complex coefficients). */
     int slot_cache, slot_cache_valid;
     int64_t slot_cache_bytes;
+    /* block matvec (ls_amd_matvec_block): its own packet buffer of the projected path (chunks of blk_rows rows, allocated on first
+     * use), its own 256-row tile map for k_direct_blk when the plan's row kernel tiles otherwise, one column of x and of y for the
+     * strided columns of the `columns` path -- none of it touches the single-vector state above */
+    lsk_pullbuf blk_pbuf;
+    int64_t blk_rows;
+    lsk_tilemap blk_tilemap;
+    void *d_blk_tilemap;
+    void *d_blk_cols; /* [2][count] elements */
     void const *y_checked[2]; /* y pointers whose memory kind was looked at (push plans: ls_amd_internal_check_y) */
     int leaves_basis;         /* pull plan over a non-Hermitian operator whose row expansion leaves the basis (found at plan time) */
     /* kernel timing ring */
@@ -1905,6 +1913,19 @@ static void split_free(ls_amd_plan *pl) {
     memset(&pl->pbuf, 0, sizeof(pl->pbuf));
     pl->split_rows = 0;
     pl->slot_cache = pl->slot_cache_valid = 0;
+}
+static void block_free(ls_amd_plan *pl) {
+    if (pl->blk_pbuf.slots) lsk_free(pl->blk_pbuf.slots);
+    if (pl->blk_pbuf.rows) lsk_free(pl->blk_pbuf.rows);
+    if (pl->blk_pbuf.coefs) lsk_free(pl->blk_pbuf.coefs);
+    if (pl->blk_pbuf.counts) lsk_free(pl->blk_pbuf.counts);
+    memset(&pl->blk_pbuf, 0, sizeof(pl->blk_pbuf));
+    pl->blk_rows = 0;
+    if (pl->d_blk_tilemap) lsk_free(pl->d_blk_tilemap);
+    pl->d_blk_tilemap = NULL;
+    memset(&pl->blk_tilemap, 0, sizeof(pl->blk_tilemap));
+    if (pl->d_blk_cols) lsk_free(pl->d_blk_cols);
+    pl->d_blk_cols = NULL;
 }
 /* room for the packet streams of as many of the plan's rows as `max_bytes` allow (all of them if it can); returns the number
  * of rows covered (0: none -- the plan keeps the fused kernel) */
@@ -3240,6 +3261,7 @@ void ls_amd_plan_destroy(ls_amd_plan *pl) {
     if (pl->d_xs) lsk_free(pl->d_xs);
     if (pl->gtab) ls_amd_internal_gtab_release(pl->gtab);
     split_free(pl);
+    block_free(pl);
     if (pl->d_send) lsk_free(pl->d_send);
     if (pl->d_cursors) lsk_free(pl->d_cursors);
     if (pl->d_counts) lsk_free(pl->d_counts);
@@ -3949,6 +3971,182 @@ int ls_amd_matvec(ls_amd_plan *pl, void const *const *d_x, void *const *d_y, voi
             }
         }
     }
+    return 0;
+}
+
+/* ============================================================================================ */
+/* block matvec (ls_amd_matvec_block)                                                           */
+/* ============================================================================================ */
+enum { BLK_COLUMNS = 0, BLK_DIRECT = 1, BLK_PULL = 2 };
+static char const *const g_blk_names[3] = { "columns", "k_direct_blk", "k_pull_gather_blk" };
+/* the block kernel that can serve this plan, else BLK_COLUMNS: projected indexed pull plans (resolve + k_pull_gather_blk) and
+ * unprojected pull plans (k_direct_blk); push plans, inversion sectors, value-table projected plans and packet plans loop columns */
+static int block_kernel_of(ls_amd_plan const *pl) {
+    if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1) return BLK_COLUMNS;
+    if (pl->family == FAMILY_TILE_PULL && pl->idx_mode && pl->dbs.proj == LSK_PROJ_FULL)
+        return (!pl->cplx && lsk_pullbuf_coef_doubles(pl->dop, pl->dbs) == 2) ? BLK_COLUMNS : BLK_PULL;
+    if (pl->family == FAMILY_DIRECT_PULL && pl->dbs.proj == LSK_PROJ_NONE && !pl->has_push_staged) return BLK_DIRECT;
+    return BLK_COLUMNS;
+}
+/* LS_AMD_BLOCK: `columns`, `kernel`, anything else (`auto`) the fixed rule below ("Block matvec"):
+ *   projected indexed pull: k_pull_gather_blk from K = 2 on;
+ *   unprojected pull whose single-vector kernel is k_direct: k_direct_blk from K = 2 on;
+ *   unprojected pull on a staged row kernel (k_chain_t, k_pairs_*, k_hubbard): columns.
+ * K = 1 keeps the single-vector kernels. */
+static int block_path(ls_amd_plan const *pl, int K) {
+    int const kern = block_kernel_of(pl);
+    char const *e = getenv("LS_AMD_BLOCK");
+    if (kern == BLK_COLUMNS || (e && strcmp(e, "columns") == 0)) return BLK_COLUMNS;
+    if (e && strcmp(e, "kernel") == 0) return kern;
+    if (K < 2) return BLK_COLUMNS;
+    if (kern == BLK_DIRECT && (pl->has_chain || pl->has_pairs || pl->has_hubbard)) return BLK_COLUMNS;
+    return kern;
+}
+char const *ls_amd_plan_block_kernel_name(ls_amd_plan const *pl, int K) {
+    if (!pl) { set_error("ls_amd_plan_block_kernel_name: plan is NULL"); return NULL; }
+    if (K < 1 || K > 64) { set_error("ls_amd_plan_block_kernel_name: K = %d is outside [1, 64]", K); return NULL; }
+    return g_blk_names[block_path(pl, K)];
+}
+
+/* K columns, one ls_amd_matvec each; y is cleared first (the single-vector paths accumulate when the operator has no diagonal) */
+static int block_columns(ls_amd_plan *pl, int K, char const *x, int64_t xr, int64_t xc, char *y, int64_t yr, int64_t yc, void *stream) {
+    int64_t const n = pl->parts[0].count;
+    size_t const w = pl->cplx ? 16 : 8;
+    if ((xr != 1 || yr != 1) && !pl->d_blk_cols && lsk_malloc(&pl->d_blk_cols, 2 * w * (size_t)n) != 0) return dev_error();
+    char *const col_x = (char *)pl->d_blk_cols, *const col_y = col_x ? col_x + w * (size_t)n : NULL;
+    for (int k = 0; k < K; ++k) {
+        void const *xin = x + (size_t)k * (size_t)xc * w;
+        void *yk = y + (size_t)k * (size_t)yc * w;
+        void *yout = yr == 1 ? yk : (void *)col_y;
+        if (xr != 1) {
+            DEV(lsk_copy_strided(n, (int)w, xin, xr, col_x, 1, stream));
+            xin = col_x;
+        }
+        DEV(lsk_memset_async(yout, 0, w * (size_t)n, stream));
+        if (ls_amd_matvec(pl, &xin, &yout, stream) != 0) return -1;
+        if (yr != 1) DEV(lsk_copy_strided(n, (int)w, col_y, 1, yk, yr, stream));
+    }
+    return 0;
+}
+
+/* packet buffer of the projected block path: whole 256-row tiles, as many rows as LS_AMD_BLOCK_RESOLVE_BYTES (default 1 GiB) allow
+ * -- at least one tile -- and no more than the plan has */
+static int block_pbuf(ls_amd_plan *pl) {
+    if (pl->blk_rows > 0) return 0;
+    int64_t const cap = lsk_pullbuf_cap(pl->dop);
+    int const nc = lsk_pullbuf_coef_doubles(pl->dop, pl->dbs);
+    int64_t const per_stream = cap * (4 + 1 + 8 * nc) + 4;
+    char const *e = getenv("LS_AMD_BLOCK_RESOLVE_BYTES");
+    int64_t max_bytes = e ? atoll(e) : ((int64_t)1 << 30);
+    if (max_bytes <= 0) max_bytes = (int64_t)1 << 30;
+    int64_t streams = (pl->parts[0].count + 63) / 64;
+    streams = (streams + 3) & ~(int64_t)3;
+    if (streams * per_stream > max_bytes) streams = (max_bytes / per_stream) & ~(int64_t)3;
+    if (streams < 4) streams = 4;
+    for (;;) {
+        void *a = NULL, *b = NULL, *c = NULL, *d = NULL;
+        if (lsk_malloc(&a, (size_t)(streams * cap * 4)) == 0 && lsk_malloc(&b, (size_t)(streams * cap)) == 0 &&
+            (nc == 0 || lsk_malloc(&c, (size_t)(streams * cap * 8 * nc)) == 0) && lsk_malloc(&d, (size_t)(streams * 4)) == 0) {
+            pl->blk_pbuf.slots = (uint32_t *)a; pl->blk_pbuf.rows = (uint8_t *)b; pl->blk_pbuf.coefs = (double *)c;
+            pl->blk_pbuf.counts = (uint32_t *)d;
+            pl->blk_pbuf.cap = cap;
+            pl->blk_pbuf.offs = NULL;
+            pl->blk_rows = streams * 64;
+            return 0;
+        }
+        if (a) lsk_free(a);
+        if (b) lsk_free(b);
+        if (c) lsk_free(c);
+        if (d) lsk_free(d);
+        if (streams <= 4) return dev_error();
+        streams = (streams / 2 + 3) & ~(int64_t)3; /* no room: half as many rows */
+    }
+}
+
+int ls_amd_matvec_block(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col,
+                        void *stream) {
+    if (!pl) return set_error("ls_amd_matvec_block: plan is NULL");
+    if (K < 1 || K > 64) return set_error("ls_amd_matvec_block: K = %d is outside [1, 64]", K);
+    if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1)
+        return set_error("ls_amd_matvec_block: one-partition plans only (this plan has P = %d, my_partition = %d)", pl->P, pl->me);
+    int64_t const n = pl->parts[0].count;
+    if (n <= 0) return 0;
+    if (!d_x || !d_y) return set_error("ls_amd_matvec_block: X or Y is NULL");
+    if (K == 1) { x_col = 0; y_col = 0; }
+    /* no two (i, k) on one element: non-negative strides, one of the two nested in the other */
+    int64_t const sr[2] = { x_row, y_row }, sc[2] = { x_col, y_col };
+    for (int v = 0; v < 2; ++v) {
+        int64_t const r = sr[v], c = sc[v];
+        int ok = r >= 0 && c >= 0;
+        if (ok && K > 1 && n > 1) ok = (c >= 1 && r >= c * K) || (r >= 1 && c >= r * n);
+        else if (ok && K > 1) ok = c >= 1;
+        else if (ok && n > 1) ok = r >= 1;
+        if (!ok)
+            return set_error("ls_amd_matvec_block: strides (row %lld, column %lld) of %s make two elements of the %lld x %d block share "
+                             "storage (need non-negative strides with row >= K * column, or column >= N * row)", (long long)r,
+                             (long long)c, v ? "Y" : "X", (long long)n, K);
+    }
+    size_t const w = pl->cplx ? 16 : 8;
+    uintptr_t const x0 = (uintptr_t)d_x, x1 = x0 + w * (size_t)((n - 1) * x_row + (int64_t)(K - 1) * x_col + 1);
+    uintptr_t const y0 = (uintptr_t)d_y, y1 = y0 + w * (size_t)((n - 1) * y_row + (int64_t)(K - 1) * y_col + 1);
+    if (x0 < y1 && y0 < x1) return set_error("ls_amd_matvec_block: X and Y overlap");
+    if (ls_amd_internal_check_y(pl, d_y) != 0) return -1;
+    int const path = block_path(pl, K);
+    if (path == BLK_COLUMNS) return block_columns(pl, K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col, stream);
+    part_state *ps = &pl->parts[0];
+    ls_amd_internal_count_matvec(pl);
+    if (path == BLK_DIRECT) {
+        lsk_tilemap tm = pl->tilemap;
+        if (pl->has_chain || pl->has_pairs) { /* those tile by 512 / 1024 rows: k_direct_blk walks 256-row tiles of its own map */
+            if (!pl->d_blk_tilemap) {
+                uint64_t *flat = NULL;
+                int64_t slots = 0;
+                if (tilemap_host(n, 256, 0, &flat, &slots) < 0) return -1;
+                int const up = upload(&pl->d_blk_tilemap, flat, sizeof(uint64_t) * (size_t)(8 * slots > 0 ? 8 * slots : 1));
+                free(flat);
+                if (up) return -1;
+                pl->blk_tilemap.entries = (uint64_t const *)pl->d_blk_tilemap;
+                pl->blk_tilemap.slots_per_xcd = slots;
+            }
+            tm = pl->blk_tilemap;
+        }
+        int const st = stage_begin(pl, ST_ROWS, stream);
+        int const slot = timing_begin(pl, stream);
+        /* (a non-Hermitian operator's partners outside the basis go to the word nobody reads, as in lsk_direct) */
+        DEV(lsk_direct_blk(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, K, d_x, x_row, x_col, d_y, y_row, y_col,
+                           OEXT(pl->op)->is_hermitian ? pl->d_err : pl->d_err + 1, stream));
+        timing_end(pl, slot, stream);
+        stage_end(pl, st, stream);
+        return 0;
+    }
+    /* projected, indexed: rows a valid slot cache covers gather from it; the others are resolved chunk by chunk into the block's
+     * own buffer (never the plan's split / cache buffer) and gathered K columns at a time */
+    lsk_pullidx ix;
+    memset(&ix, 0, sizeof(ix));
+    ix.tab = pl->gtab->tab;
+    int64_t const cached = pl->slot_cache && pl->slot_cache_valid ? pl->split_rows : 0;
+    int const slot = timing_begin(pl, stream);
+    if (cached > 0) {
+        int const st = stage_begin(pl, ST_ROWS, stream);
+        DEV(lsk_pull_gather_blk(pl->dop, pl->dbs, pl->cplx, 0, cached, ps->d_reps, ps->d_norms, pl->pbuf, K, d_x, x_row, x_col, d_y, y_row,
+                                y_col, stream));
+        stage_end(pl, st, stream);
+    }
+    if (cached < n && block_pbuf(pl) != 0) return -1;
+    for (int64_t r0 = cached; r0 < n; r0 += pl->blk_rows) {
+        int64_t const r1 = r0 + pl->blk_rows < n ? r0 + pl->blk_rows : n;
+        lsk_pullbuf pb = pl->blk_pbuf;
+        pb.row0 = r0;
+        int st = stage_begin(pl, ST_GENERATE, stream);
+        DEV(lsk_tile_pull_resolve(pl->dop, pl->dbs, r0, r1, ps->d_reps, ps->d_norms, ix, ps->d_reps, ps->count, pl->pull_halo, pb, pl->d_err,
+                                  stream));
+        stage_end(pl, st, stream);
+        st = stage_begin(pl, ST_ROWS, stream);
+        DEV(lsk_pull_gather_blk(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, K, d_x, x_row, x_col, d_y, y_row, y_col,
+                                stream));
+        stage_end(pl, st, stream);
+    }
+    timing_end(pl, slot, stream);
     return 0;
 }
 

@@ -1107,5 +1107,128 @@ extern "C" int lsk_tile_pull_gather(lsk_operator op, lsk_basis bs, int cplx, int
     return 0;
 }
 
+// Block gather (k_pull_gather_blk): the packet stream of k_pull_t<..., SINK_RESOLVE> applied to K columns at once, one partition
+// (slot = global index).  Element (i, k) of X is at x[i * xr + k * xc] (doubles, or double pairs for c128), Y alike.  A wave reads
+// each (slot, row, coefficient) packet of its 64 rows ONCE per chunk of KB columns (8 f64 / 4 c128: one 64-byte row of an
+// interleaved block) and adds KB products into LDS accumulators [column][row]; y is written once per row and column, assigned.
+// The coefficient kind (COEF_*) is a run-time, wave-uniform argument rather than a template parameter (two instantiations in all).
+// Prescaling K4 modes (k4_mode != 0): the resolve kernel's coefficients expect x * norm(rep); the gather multiplies norms[slot]
+// in -- one 8-byte load per packet shared by the KB columns -- instead of scaling a K-wide copy of X.  The diagonal is fused.
+template <bool CPLX>
+__global__ __launch_bounds__(kBlock) void k_pull_gather_blk(lsk_runs runs, int n_diag, lsk_term const *__restrict__ diag, int k4_mode,
+                                                            int coef, int64_t row0, int64_t row1, uint64_t const *__restrict__ reps,
+                                                            double const *__restrict__ norms, double uni_v, lsk_pullbuf buf, int K,
+                                                            double const *__restrict__ x, int64_t xr, int64_t xc, double *__restrict__ y,
+                                                            int64_t yr, int64_t yc, int xcd_chunk) {
+    typedef typename ChainX<CPLX>::type X;
+    constexpr int KB = CPLX ? 4 : 8;
+    constexpr int GU = 2;
+    X const *__restrict__ xv = (X const *)x;
+    X *__restrict__ yv = (X *)y;
+    __shared__ X s_acc[KB * kBlock];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int64_t n_tiles = (row1 - row0 + kBlock - 1) / kBlock;
+    for (int64_t tb = blockIdx.x; tb < n_tiles; tb += gridDim.x) {
+        const int64_t t0 = row0 + pull_tile_of_block(tb, n_tiles, gridDim.x >= n_tiles ? xcd_chunk : 0) * kBlock;
+        if ((t0 + (wave << 6)) >= row1) continue; // wave-uniform
+        const int64_t i = t0 + tid;
+        const bool valid = i < row1;
+        const int64_t wg = ((t0 - buf.row0) >> 6) + wave;
+        const int64_t sbase = buf.offs ? buf.offs[wg] : wg * buf.cap;
+        const int n = (int)buf.counts[wg];
+        double inv_na = 0.0, dr = 0.0, di = 0.0;
+        if (valid) {
+            const double na = norms[i];
+            inv_na = na > 0.0 ? 1.0 / na : 0.0;
+            if (n_diag > 0) diag_coeff<uint64_t, !CPLX>(runs, n_diag, diag, reps[i], dr, di);
+        }
+        const double sc = coef == COEF_UNI ? uni_v * inv_na : 1.0;
+        for (int c0 = 0; c0 < K; c0 += KB) {
+            const int kb = min(KB, K - c0); // wave-uniform
+#pragma unroll
+            for (int k = 0; k < KB; ++k) s_acc[k * kBlock + tid] = cx_zero<X>();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int c = 0; c < n; c += 64 * GU) {
+                uint32_t slot[GU];
+                int r[GU];
+                double hr[GU], hi[GU], nb[GU];
+#pragma unroll
+                for (int u = 0; u < GU; ++u) {
+                    const int p = c + 64 * u + lane;
+                    slot[u] = kNoSlot; r[u] = 0; hr[u] = 1.0; hi[u] = 0.0; nb[u] = 1.0;
+                    if (p < n) {
+                        const int64_t o = sbase + p;
+                        slot[u] = buf.slots[o];
+                        r[u] = (int)buf.rows[o];
+                        if (coef == COEF_REAL) hr[u] = buf.coefs[o];
+                        else if (coef == COEF_CPLX) { hr[u] = buf.coefs[2 * o]; hi[u] = buf.coefs[2 * o + 1]; }
+                    }
+                    if (slot[u] != kNoSlot && k4_mode != 0) nb[u] = norms[slot[u]];
+                }
+                X v[GU][KB];
+#pragma unroll
+                for (int u = 0; u < GU; ++u) {
+                    X const *__restrict__ xp = xv + (int64_t)(slot[u] != kNoSlot ? slot[u] : 0) * xr + (int64_t)c0 * xc;
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) v[u][k] = (slot[u] != kNoSlot && k < kb) ? xp[(int64_t)k * xc] : cx_zero<X>();
+                }
+#pragma unroll
+                for (int u = 0; u < GU; ++u) {
+                    if (slot[u] == kNoSlot) continue;
+                    const int ra = (wave << 6) + r[u];
+                    const double cr = hr[u] * nb[u], ci = hi[u] * nb[u];
+#pragma unroll
+                    for (int k = 0; k < KB; ++k) {
+                        if (k >= kb) continue;
+                        double *const acc = (double *)&s_acc[k * kBlock + ra];
+                        if constexpr (CPLX) {
+                            atomicAdd(acc, cr * v[u][k].x - ci * v[u][k].y);
+                            atomicAdd(acc + 1, cr * v[u][k].y + ci * v[u][k].x);
+                        } else atomicAdd(acc, cr * v[u][k]);
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (valid) {
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    if (k >= kb) continue;
+                    const X xo = xv[i * xr + (int64_t)(c0 + k) * xc];
+                    const X s = s_acc[k * kBlock + tid];
+                    if constexpr (CPLX) yv[i * yr + (int64_t)(c0 + k) * yc] = make_double2(dr * xo.x - di * xo.y + sc * s.x, dr * xo.y + di * xo.x + sc * s.y);
+                    else yv[i * yr + (int64_t)(c0 + k) * yc] = dr * xo + sc * s;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // this wave's accumulators are free again
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+extern "C" int lsk_pull_gather_blk(lsk_operator op, lsk_basis bs, int cplx, int64_t row0, int64_t row1, uint64_t const *reps,
+                                   double const *norms, lsk_pullbuf buf, int K, void const *x, int64_t xr, int64_t xc, void *y,
+                                   int64_t yr, int64_t yc, void *stream) {
+    if (row1 <= row0 || K <= 0) return 0;
+    int k4m, coef;
+    pull_kinds(op, bs, k4m, coef);
+    if (coef == COEF_CPLX && !cplx) { snprintf(g_err, sizeof(g_err), "lsk_pull_gather_blk: complex coefficients need c128 vectors"); return -1; }
+    const int64_t work_blocks = (row1 - row0 + kBlock - 1) / kBlock;
+    hipStream_t s = (hipStream_t)stream;
+    if (cplx)
+        hipLaunchKernelGGL(k_pull_gather_blk<true>, dim3((unsigned)tile_grid(k_pull_gather_blk<true>, work_blocks)), dim3(kBlock), 0, s, op.runs,
+                           op.n_diag, op.diag, bs.k4_mode, coef, row0, row1, reps, norms, op.uni_v, buf, K, (double const *)x, xr, xc,
+                           (double *)y, yr, yc, pull_xcd_chunk());
+    else
+        hipLaunchKernelGGL(k_pull_gather_blk<false>, dim3((unsigned)tile_grid(k_pull_gather_blk<false>, work_blocks)), dim3(kBlock), 0, s, op.runs,
+                           op.n_diag, op.diag, bs.k4_mode, coef, row0, row1, reps, norms, op.uni_v, buf, K, (double const *)x, xr, xc,
+                           (double *)y, yr, yc, pull_xcd_chunk());
+    LSK_LAUNCH_CHECK();
+    return 0;
+}
+
 
 

@@ -403,6 +403,119 @@ extern "C" int lsk_direct(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx,
     // flag of a partner outside the basis lands in d_err[1], which nobody reads (d_err points at two ints)
     return direct_dispatch(op, bs, ix, cplx, pull != 0, tm, reps, x, y, pull == 2 ? d_err + 1 : d_err, stream, 0, nullptr);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Block pull (k_direct_blk): Y[:, k] = H X[:, k] for k < K on an unprojected basis, any operator -- the pull form of k_direct with
+// one row per lane, for K columns at once.  Element (i, k) of X is at x[i * xr + k * xc] (elements: doubles, or double pairs for
+// c128).  The columns go in chunks of KB (one 64-byte row of an interleaved f64 block, or of a c128 one of 4 columns): the
+// coefficient and the index of a partner are computed once per chunk and feed KB gathers into KB register accumulators.  Every
+// group takes the generic loop (no run tables, no directed instantiation: the exchange-run shortcuts of k_direct save ALU work the
+// gathers of a block hide).  Y is assigned, whatever n_diag.  Error flags as k_direct's.
+// ---------------------------------------------------------------------------------------------
+template <bool CPLX> struct BlkCols { static constexpr int KB = CPLX ? 4 : 8; };
+// (<= 80 SGPRs, as k_direct: the persistent grid is sized by the occupancy API, which over-reports the resident blocks from 81 on.
+// Uncapped, the KB unrolled column offsets took 106 and 7 blocks per CU.)
+template <bool CPLX, int INDEX>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_sgpr(80))) void k_direct_blk(lsk_runs runs, int n_groups, lsk_group const *__restrict__ groups,
+                                                       lsk_term const *__restrict__ off, int n_diag, lsk_term const *__restrict__ diag,
+                                                       lsk_index ix, int weight, uint64_t const *__restrict__ tilemap,
+                                                       int64_t slots_per_xcd, uint64_t const *__restrict__ reps, int K, double const *__restrict__ x,
+                                                       int64_t xr, int64_t xc, double *__restrict__ y, int64_t yr, int64_t yc, int *err) {
+    typedef typename ChainX<CPLX>::type X;
+    constexpr bool REAL = !CPLX; // (f64 vectors only ever meet real operators: the plan refuses the other combination)
+    constexpr int KB = BlkCols<CPLX>::KB;
+    constexpr bool BINOM = INDEX == LSK_INDEX_COMBINADIC || INDEX == LSK_INDEX_PRODUCT;
+    __shared__ uint64_t s_binom[BINOM ? 64 * LSK_BINOM_K : 1];
+    if (BINOM) {
+        for (int k = threadIdx.x; k < 64 * LSK_BINOM_K; k += blockDim.x) s_binom[k] = ix.binom[k];
+        __syncthreads();
+    }
+    X const *__restrict__ xv = (X const *)x;
+    X *__restrict__ yv = (X *)y;
+    const int xcd = blockIdx.x & 7;
+    const int64_t blocks_per_xcd = gridDim.x >> 3; // grid is a multiple of 8
+    tilemap += (int64_t)xcd * slots_per_xcd;
+    for (int64_t t = blockIdx.x >> 3; t < slots_per_xcd; t += blocks_per_xcd) {
+        const uint64_t slot = tilemap[t]; // (first row, number of rows <= kBlock)
+        if ((uint64_t)threadIdx.x >= (slot >> 48)) continue;
+        const int64_t i = (int64_t)(slot & 0xffffffffffffULL) + threadIdx.x;
+        const uint64_t a = __builtin_nontemporal_load(reps + i);
+        double dr = 0.0, di = 0.0;
+        if (n_diag > 0) diag_coeff<uint64_t, REAL>(runs, n_diag, diag, a, dr, di);
+        for (int c0 = 0; c0 < K; c0 += KB) {
+            const int kb = min(KB, K - c0); // wave-uniform
+            X acc[KB];
+#pragma unroll
+            for (int k = 0; k < KB; ++k) {
+                acc[k] = cx_zero<X>();
+                if (k < kb) {
+                    const X xo = xv[i * xr + (int64_t)(c0 + k) * xc];
+                    if constexpr (CPLX) acc[k] = make_double2(dr * xo.x - di * xo.y, dr * xo.y + di * xo.x);
+                    else acc[k] = dr * xo;
+                }
+            }
+            for (int g = 0; g < n_groups; ++g) {
+                lsk_group const G = groups[g];
+                double cr, ci;
+                // <i|H_g|i ^ x_g>: the coefficient of the PARTNER's row expansion (any operator, as k_direct's pull form)
+                const uint64_t beta = a ^ G.x;
+                group_coeff<REAL>(G, off, beta, cr, ci);
+                if (cr == 0.0 && (REAL || ci == 0.0)) continue;
+                int64_t idx;
+                if (INDEX == LSK_INDEX_IDENTITY) idx = (int64_t)beta;
+                else if (INDEX == LSK_INDEX_COMBINADIC) {
+                    if (__popcll(beta) != weight) { atomicExch(err, 1); continue; }
+                    idx = rank_combinadic_w<uint64_t, uint64_t>(beta, s_binom);
+                } else if constexpr (INDEX == LSK_INDEX_PRODUCT) idx = product_index(ix, beta, s_binom);
+                else idx = search_index(ix, beta);
+                if (idx < 0) { atomicExch(err, 1); continue; } // DMV:115-118
+                X v[KB];
+                X const *__restrict__ xp = xv + idx * xr;
+#pragma unroll
+                for (int k = 0; k < KB; ++k) v[k] = k < kb ? xp[(int64_t)(c0 + k) * xc] : cx_zero<X>();
+#pragma unroll
+                for (int k = 0; k < KB; ++k) {
+                    if constexpr (CPLX) {
+                        acc[k].x += cr * v[k].x - ci * v[k].y;
+                        acc[k].y += cr * v[k].y + ci * v[k].x;
+                    } else acc[k] = fma(cr, v[k], acc[k]);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                if (k < kb) yv[i * yr + (int64_t)(c0 + k) * yc] = acc[k];
+        }
+    }
+}
+template <bool CPLX, int INDEX>
+static int launch_direct_blk(lsk_operator const &op, lsk_index ix, int weight, lsk_tilemap tm, uint64_t const *reps, int K, void const *x, int64_t xr,
+                             int64_t xc, void *y, int64_t yr, int64_t yc, int *d_err, hipStream_t s) {
+    int64_t gb = tm.slots_per_xcd * 8;
+    int64_t cap = resident_grid(k_direct_blk<CPLX, INDEX>, gb) & ~(int64_t)7; // persistent, a multiple of 8 (XCD dealing)
+    if (cap < 8) cap = 8;
+    if (gb > cap) gb = cap;
+    hipLaunchKernelGGL((k_direct_blk<CPLX, INDEX>), dim3((unsigned)gb), dim3(kBlock), 0, s, op.runs, op.n_groups, op.groups, op.off, op.n_diag,
+                       op.diag, ix, weight, tm.entries, tm.slots_per_xcd, reps, K, (double const *)x, xr, xc, (double *)y, yr, yc, d_err);
+    LSK_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int lsk_direct_blk(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, lsk_tilemap tm, uint64_t const *reps, int K,
+                              void const *x, int64_t xr, int64_t xc, void *y, int64_t yr, int64_t yc, int *d_err, void *stream) {
+    if (tm.slots_per_xcd == 0 || K <= 0) return 0;
+    if (!tm.entries) { snprintf(g_err, sizeof(g_err), "lsk_direct_blk: no tile map"); return -1; }
+    if (bs.proj != LSK_PROJ_NONE) { snprintf(g_err, sizeof(g_err), "lsk_direct_blk: unprojected bases only"); return -1; }
+    if (!cplx && !op.is_real) { snprintf(g_err, sizeof(g_err), "lsk_direct_blk: complex operators need c128 vectors"); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+#define LSK_DB(IDX) (cplx ? launch_direct_blk<true, IDX>(op, ix, bs.hamming_weight, tm, reps, K, x, xr, xc, y, yr, yc, d_err, s) \
+                          : launch_direct_blk<false, IDX>(op, ix, bs.hamming_weight, tm, reps, K, x, xr, xc, y, yr, yc, d_err, s))
+    switch (ix.kind) {
+    case LSK_INDEX_IDENTITY: return LSK_DB(LSK_INDEX_IDENTITY);
+    case LSK_INDEX_COMBINADIC: return LSK_DB(LSK_INDEX_COMBINADIC);
+    case LSK_INDEX_PRODUCT: return LSK_DB(LSK_INDEX_PRODUCT);
+    default: return LSK_DB(LSK_INDEX_SEARCH);
+    }
+#undef LSK_DB
+}
 // replicated-x pull: `reps` = the n rows of one partition, `x` = whole vector in global order, `ix` = index
 // of the GLOBAL basis, row_gidx[i] = global index of row i (only read for SEARCH indices)
 // ---------------------------------------------------------------------------------------------

@@ -45,6 +45,12 @@ extern "C" int lsk_memset_async(void *p, int value, size_t bytes, void *stream) 
     if (bytes) LSK_CHECK(hipMemsetAsync(p, value, bytes, (hipStream_t)stream));
     return 0;
 }
+extern "C" int lsk_copy_strided(int64_t n, int elt_size, void const *src, int64_t src_stride, void *dst, int64_t dst_stride, void *stream) {
+    if (n > 0)
+        LSK_CHECK(hipMemcpy2DAsync(dst, (size_t)(dst_stride * elt_size), src, (size_t)(src_stride * elt_size), (size_t)elt_size, (size_t)n,
+                                   hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
 extern "C" int lsk_sync(void *stream) { LSK_CHECK(hipStreamSynchronize((hipStream_t)stream)); return 0; }
 extern "C" int lsk_device_sync(void) { LSK_CHECK(hipDeviceSynchronize()); return 0; }
 

@@ -209,6 +209,8 @@ int lsk_d2d_async(void *dst, void const *src, size_t bytes, void *stream);
 int lsk_memset_async(void *p, int value, size_t bytes, void *stream);
 int lsk_sync(void *stream);
 int lsk_device_sync(void);
+/* dst[i * dst_stride] = src[i * src_stride] for i < n, elements of elt_size bytes (strides in elements) */
+int lsk_copy_strided(int64_t n, int elt_size, void const *src, int64_t src_stride, void *dst, int64_t dst_stride, void *stream);
 
 /* host <-> HBM staging of the host-pointer entry points (stage.cpp) ---------------------------- */
 enum { LSK_PTR_PAGEABLE = 0, LSK_PTR_PINNED = 1, LSK_PTR_DEVICE = 2,
@@ -457,6 +459,16 @@ int lsk_tile_pull_resolve(lsk_operator op, lsk_basis bs, int64_t row0, int64_t r
                           lsk_pullbuf buf, int *d_err, void *stream);
 int lsk_tile_pull_gather(lsk_operator op, lsk_basis bs, int cplx, int64_t row0, int64_t row1, uint64_t const *reps,
                          double const *norms_local, lsk_pullidx ix, void const *xsrc, lsk_pullbuf buf, void *y, void *stream);
+/* ---- block matvec (ls_amd_matvec_block): K columns per pass, one partition.  Element (i, k) of x is at x[i * xr + k * xc], y alike
+ * (strides in elements of the vector type); y is assigned.
+ * k_direct_blk: the pull form of k_direct on an unprojected basis (any operator), u64 states, tile map of <= 256-row tiles */
+int lsk_direct_blk(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, lsk_tilemap tm, uint64_t const *reps, int K,
+                   void const *x, int64_t xr, int64_t xc, void *y, int64_t yr, int64_t yc, int *d_err, void *stream);
+/* k_pull_gather_blk: rows [row0, row1) of a projected one-partition plan from the packet streams lsk_tile_pull_resolve wrote into
+ * buf (slot = global index); norms = the per-row norms (multiplied in for the K4 modes that prescale) */
+int lsk_pull_gather_blk(lsk_operator op, lsk_basis bs, int cplx, int64_t row0, int64_t row1, uint64_t const *reps,
+                        double const *norms, lsk_pullbuf buf, int K, void const *x, int64_t xr, int64_t xc, void *y,
+                        int64_t yr, int64_t yc, void *stream);
 /* out[i] = x[i] * norms[i] (f64 / c128): the owner-side prescaling of the indexed mode */
 int lsk_scale(int cplx, int64_t n, void const *x, double const *norms, void *out, void *stream);
 /* dst[perm[g] - base] = src[g] for every g with base <= perm[g] < base + count (8-byte elements): the rows one owner holds,

@@ -282,6 +282,23 @@ int ls_amd_plan_slot_cache_rows(ls_amd_plan const *plan, int64_t *rows, int64_t 
  * Asynchronous on `stream`; call ls_amd_plan_check to synchronise and collect the
  * "invalid index" condition the reference halts on (DMV:115-118). */
 int ls_amd_matvec(ls_amd_plan *plan, void const *const *d_x, void *const *d_y, void *stream);
+
+/* Block matvec: Y[:, k] <- H X[:, k] for k < K (1 <= K <= 64).  Element (i, k) of X is at d_x[i*x_row + k*x_col] (elements of the
+ * plan's dtype, not bytes); the same for Y.  (x_row, x_col) = (K, 1): interleaved (torch (N, K) contiguous), the fast layout;
+ * (1, ld): column-major (PRIMME, orth_pass).  Strides are non-negative and nested -- row stride >= K * column stride, or column
+ * stride >= N * row stride -- so that no two (i, k) share an element.  One-partition plans only (ls_amd_plan_create with P = 1,
+ * my_partition = -1).  Y is assigned, not accumulated (DMV:1062-1063).  X and Y must not overlap.  Asynchronous on `stream`;
+ * ls_amd_plan_check collects the "invalid index" condition as after ls_amd_matvec.  The plan's single-vector state (slot cache,
+ * split form) is left as it is; a valid slot cache is read for the rows it covers.
+ * LS_AMD_BLOCK=auto|kernel|columns (read at every call): `columns` runs ls_amd_matvec once per column (a strided column goes
+ * through one column of scratch), `kernel` takes the block kernel wherever one applies, `auto` (default) the rule of
+ * ls_amd_plan_block_kernel_name.  LS_AMD_BLOCK_RESOLVE_BYTES caps the packet buffer of the projected block path (default 1 GiB;
+ * allocated on first use, freed with the plan). */
+int ls_amd_matvec_block(ls_amd_plan *plan, int K, void const *d_x, int64_t x_row, int64_t x_col,
+                        void *d_y, int64_t y_row, int64_t y_col, void *stream);
+/* which path a block of K columns takes on this plan now: "k_direct_blk", "k_pull_gather_blk" or "columns" (NULL plan or K out of
+ * range: NULL, with ls_amd_last_error set) */
+char const *ls_amd_plan_block_kernel_name(ls_amd_plan const *plan, int K);
 int ls_amd_plan_check(ls_amd_plan *plan, void *stream);
 
 /* ------------------------------------------------------------------------------------------
