@@ -6,6 +6,7 @@ import yaml
 import distributed_matvec_amd as D
 from distributed_matvec_amd import _lib, config
 from fermion_jw import hubbard_model, ring, square, yaml_terms
+from fermion_wide import hop, pair_hop, spinless_chain
 from helpers import product_terms
 
 
@@ -41,6 +42,15 @@ CASES = {
                         "hamiltonian": {"terms": yaml_terms(spinless_model(8), False)}},
     "spinless_unrestricted": {"basis": {"particle": "spinless-fermion", "number_sites": 7, "number_particles": None},
                               "hamiltonian": {"terms": yaml_terms(spinless_model(7), False)}},
+    # wide words: the down half at bits 32..63 (a pair hop onto 31 down reaches bit 63), strings across bit 32 and up to bit 62
+    "hubbard_32_peierls_pair_hop": {
+        "basis": {"particle": "spinful-fermion", "number_sites": 32, "number_particles": 3, "number_up": 1},
+        "hamiltonian": {"terms": yaml_terms(hubbard_model(32, ring(32) + [(0, 17), (5, 29)], t=1.0, U=2.0, V=0.3, phase=0.21)
+                                            + pair_hop(0, 31, 0.5), True)}},
+    "spinless_ring_64_long_hops": {
+        "basis": {"particle": "spinless-fermion", "number_sites": 64, "number_particles": 2},
+        "hamiltonian": {"terms": yaml_terms(spinless_chain(64, ring(64) + [(3, 60), (30, 33)], V=0.5)
+                                            + hop(1, 62, 0.2 + 0.3j), False)}},
 }
 
 
