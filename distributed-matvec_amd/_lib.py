@@ -117,6 +117,9 @@ def load():
         "ls_amd_orth_max_rows": (C.c_int, []),
         "ls_amd_orth_pass": (C.c_int, [C.c_int, C.c_int64, vp, C.c_int64, vp, vp, vp, vp]),
         "ls_amd_basis_rotate": (C.c_int, [C.c_int, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]),
+        "ls_amd_orth_block_max_rows": (C.c_int, []),
+        "ls_amd_orth_block_pass": (C.c_int, [C.c_int, C.c_int, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]),
+        "ls_amd_block_rotate": (C.c_int, [C.c_int, C.c_int, C.c_int64, vp, C.c_int64, vp, vp]),
         "ls_amd_pointer_kind": (C.c_int, [vp]),
         "ls_amd_host_register": (C.c_int, [vp, C.c_size_t]),
         "ls_amd_host_unregister": (C.c_int, [vp]),

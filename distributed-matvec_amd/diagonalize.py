@@ -63,6 +63,26 @@ class LocalOperator:
 
         return self.torch.cat([fillRandom(r, seed, self.dtype) for r in self.reps])
 
+    def matvec_block(self, x, y):
+        """Y[:, c] <- H X[:, c] for the K columns of the (n, K) views x and y (column-major views `V[s:s+K].T` of basis rows are
+        the layout of the block solver).  One-partition plans take ls_amd_matvec_block; with P > 1 the columns go through the
+        single-vector plan one by one."""
+        K = int(x.shape[1])
+        if len(self.sizes) == 1:
+            self.plan.matvec_block(x, y, check=False)
+        else:
+            for c in range(K):
+                yc = y[:, c] if y[:, c].is_contiguous() else self.new_vector()
+                yc.zero_()
+                self.plan.matvec(self._split(x[:, c].contiguous()), self._split(yc), check=False)
+                if yc.data_ptr() != y[:, c].data_ptr():
+                    y[:, c] = yc
+        self.matvecs += K
+
+    def block_kernel(self, K):
+        """path a block of K columns takes (\"columns\" for plans with P > 1: the loop of matvec_block)"""
+        return self.plan.block_kernel(K) if len(self.sizes) == 1 else "columns"
+
 
 class RankOperator:
     """H with one partition per process (wraps distributed.DistributedOperator)."""
@@ -260,13 +280,276 @@ def lanczos_smallest(op, num_evals: int = 1, eps: float = 1e-6, max_basis: int =
             print(f"[lanczos] profile after restart {restarts}: " + ", ".join(f"{k} {v:.2f} s" for k, v in prof.items()), flush=True)
 
 
+def _block_orth_ops(op, V, K):
+    """(sweep, rotate, fused) for lanczos_block_smallest on the basis array V [rows, n].
+    sweep(p, s, h): classical Gram-Schmidt sweep of the block V[s:s+K] against V[:p] -- if h (p x K) is given, first
+    V[s+c] -= sum_k h[k][c] V[k] -- returning (overlaps (p x K) = <V_k, W_c> and the Gram matrix (K x K) = <W_c, W_c'>) of the
+    updated block as host arrays.  rotate(m_in, m_out, S, r0): V[r0:r0+m_out] <- S^T V[r0:r0+m_in] in place.
+    Fused (real f64 on the device, LS_AMD_FUSED_ORTH != 0): ls_amd_orth_block_pass / ls_amd_block_rotate (csrc/orth_block.hip),
+    one read of V[:p] per sweep.  Otherwise torch products in column chunks: no temporary larger than one block."""
+    import numpy as np
+    import torch
+
+    n = V.shape[1]
+
+    def gsum(t):
+        return op.global_sum(t) if hasattr(op, "global_sum") else t
+
+    if V.is_cuda and V.dtype == torch.float64 and os.environ.get("LS_AMD_FUSED_ORTH", "1") != "0":
+        import ctypes as C
+
+        from . import _lib
+        from .api import _stream_ptr
+
+        lib = _lib.load()
+        rows = int(lib.ls_amd_orth_block_max_rows())
+        obuf = torch.zeros(rows * K + K * K, dtype=torch.float64, device=V.device)
+        ld = V.stride(0)
+
+        def sweep(p, s, h):
+            hd = torch.as_tensor(np.ascontiguousarray(h), dtype=torch.float64, device=V.device) if h is not None else None
+            _lib.check(lib.ls_amd_orth_block_pass(p, K, n, C.c_void_p(V.data_ptr()), ld, C.c_void_p(V[s].data_ptr()), ld,
+                                                  C.c_void_p(hd.data_ptr()) if hd is not None else None, C.c_void_p(obuf.data_ptr()),
+                                                  _stream_ptr()))
+            o = gsum(obuf[: p * K + K * K].clone()).cpu().numpy()
+            return o[: p * K].reshape(p, K), o[p * K:].reshape(K, K)
+
+        def rotate(m_in, m_out, S, r0=0):
+            Sd = torch.as_tensor(np.ascontiguousarray(S), dtype=torch.float64, device=V.device)
+            _lib.check(lib.ls_amd_block_rotate(m_in, m_out, n, C.c_void_p(V[r0].data_ptr()), ld, C.c_void_p(Sd.data_ptr()), _stream_ptr()))
+
+        return sweep, rotate, rows
+
+    cplx = V.is_complex()
+    step = max(1, (1 << 24) // max(K, 1))
+
+    def sweep(p, s, h):
+        W = V[s:s + K]
+        if h is not None:
+            Ht = torch.as_tensor(np.ascontiguousarray(h), dtype=V.dtype, device=V.device).t()  # K x p
+            for c0 in range(0, n, step):
+                c1 = min(n, c0 + step)
+                W[:, c0:c1] -= torch.mm(Ht, V[:p, c0:c1])
+        o = torch.zeros((p, K), dtype=V.dtype, device=V.device)
+        g = torch.zeros((K, K), dtype=V.dtype, device=V.device)
+        for c0 in range(0, n, step):
+            c1 = min(n, c0 + step)
+            Wc = W[:, c0:c1]
+            if p:
+                o += torch.mm(V[:p, c0:c1].conj() if cplx else V[:p, c0:c1], Wc.t())
+            g += torch.mm(Wc.conj() if cplx else Wc, Wc.t())
+        return gsum(o).cpu().numpy(), gsum(g).cpu().numpy()
+
+    def rotate(m_in, m_out, S, r0=0):
+        St = torch.as_tensor(np.ascontiguousarray(S), dtype=V.dtype, device=V.device).t()
+        for c0 in range(0, n, step):
+            c1 = min(n, c0 + step)
+            V[r0:r0 + m_out, c0:c1] = torch.mm(St, V[r0:r0 + m_in, c0:c1])
+
+    return sweep, rotate, None
+
+
+def lanczos_block_smallest(op, num_evals: int = 1, block_size: int = 4, eps: float = 1e-6, max_basis: int | None = None,
+                           max_restarts: int = 500, seed: int = 1234, verbose: bool = False) -> EigenResult:
+    """Smallest `num_evals` eigenpairs of the Hermitian operator `op` by block thick-restart Lanczos (block Krylov-Schur, Zhou &
+    Saad 2008) with blocks of K = `block_size` vectors -- the reference's kMaxBlockSize, handed to PRIMME as maxBlockSize
+    (Diagonalize.chpl:172,192).  A Krylov space grown from one vector holds one vector per eigenspace; a block of K start vectors
+    finds a degenerate level with its multiplicity (up to K).
+    Step: W = H V_j (op.matvec_block, one pass over the plan for K columns); classical Gram-Schmidt of W against the basis twice
+    (one sweep of the basis each, csrc/orth_block.hip), a third sweep only when the overlaps left exceed 1e-11 of the remaining
+    norm (lanczos_smallest's rule); Cholesky-QR from the Gram matrix of the last sweep, repeated once when ||Q^T Q - I|| > 1e-12.
+    A column whose norm falls below 1e-10 of its norm before the orthogonalisation (or that makes the Gram matrix singular) is
+    deflated: replaced by a fresh random vector orthogonalised against the basis, with zero coupling in T; when even that has
+    nothing left, the basis spans an invariant subspace and the Ritz pairs are exact.
+    The basis holds max(max_basis, 2 num_evals + 3 K) vectors (<= 128 on the fused path) plus one block.  Residuals,
+    convergence test, `history` and EigenResult fields as lanczos_smallest; `matvecs` counts columns."""
+    import numpy as np
+    import torch
+
+    t0 = time.perf_counter()
+    K = int(block_size)
+    k = num_evals
+    if not 1 <= K <= 16:
+        raise ValueError(f"block_size = {K}: the block solver takes 1 <= block_size <= 16")
+    if op.n_local < K and not hasattr(op, "global_sum"):
+        raise ValueError(f"block_size = {K} exceeds the dimension {op.n_local}")
+    mb = max(max_basis if max_basis is not None else 0, 2 * k + 3 * K)
+    x0 = op.random_vector(seed)
+    n, dt, dev = x0.numel(), x0.dtype, x0.device
+    cplx = x0.is_complex()
+    # the basis: mb vectors and one block (the next block W = H V_j is computed into the rows after the basis it joins)
+    V = torch.empty((mb + K, n), dtype=dt, device=dev)
+    sweep, rotate, fused_rows = _block_orth_ops(op, V, K)
+    if fused_rows is not None and mb > fused_rows:
+        raise ValueError(f"lanczos_block_smallest: a basis of {mb} vectors exceeds the {fused_rows} rows of the fused "
+                         f"orthogonalisation (ls_amd_orth_block_max_rows); lower max_basis, num_evals or block_size")
+    T = np.zeros((mb + K, mb + K), dtype=complex if cplx else float)
+    restarts = 0
+    history = []
+    rng_seed = [seed + K]
+    prof = {"matvec": 0.0, "orth": 0.0, "restart": 0.0} if os.environ.get("LS_AMD_LANCZOS_PROFILE") else None
+
+    def tick():
+        if prof is None:
+            return 0.0
+        torch.cuda.synchronize()
+        return time.perf_counter()
+
+    def orthogonalise(p, s):
+        """CGS twice (three times when needed) of V[s:s+K] against V[:p]: (coefficients p x K, Gram of the result, Gram before)"""
+        h, G = sweep(p, s, None)
+        G0 = G
+        if p == 0:
+            return np.zeros((0, K), dtype=T.dtype), G, G0
+        h2, G = sweep(p, s, h)
+        left = np.sqrt((np.abs(h2) ** 2).sum(axis=0))
+        if np.any(left > 1e-11 * np.sqrt(np.maximum(np.diag(G).real, 0.0))):
+            _, G = sweep(p, s, h2)
+            h = h + h2
+        return h, G, G0
+
+    def cholesky_deflate(G, G0):
+        """upper R with R^H R = G over the columns that keep a norm; the deflated columns are returned separately: norm below
+        1e-10 of the norm before, or a pivot that is not positive at the precision a Gram matrix resolves (below 1e-12 of the
+        column's squared norm: the cancellation in G[c, c] - sum R[:, c]^2 is 1e-16 of it, so dependence inside the block shows
+        there, not at 1e-20)"""
+        G = 0.5 * (G + G.conj().T)
+        R = np.zeros((K, K), dtype=T.dtype)
+        dead = []
+        for c in range(K):
+            d = G[c, c].real - float(np.sum(np.abs(R[:c, c]) ** 2))
+            before = max(G0[c, c].real, 0.0)
+            if not d > (1e-10) ** 2 * before or not d > 1e-12 * G[c, c].real:
+                dead.append(c)
+                continue
+            R[c, c] = math.sqrt(d)
+            for c2 in range(c + 1, K):
+                R[c, c2] = (G[c, c2] - np.dot(R[:c, c].conj(), R[:c, c2])) / R[c, c]
+        return R, dead
+
+    def normalise(s, G, G0):
+        """Cholesky-QR of V[s:s+K] in place: returns (R, None), R the coupling (W = Q R).  Deflated columns are replaced by random
+        vectors orthogonalised against V[:s] and the block, which the coupling does not reach.  When such a vector has nothing left, V[:s] and
+        the block's live columns span the whole space: returns (R over all columns, the live columns), nothing normalised."""
+        R, dead = cholesky_deflate(G, G0)
+        if dead:
+            # what is left of a deflated column is a combination W_live x of the live ones (x = 0 when its norm vanished): its
+            # coupling is carried by them, and the column itself is free for a new direction
+            live = [c for c in range(K) if c not in dead]
+            X = np.linalg.solve(R[np.ix_(live, live)], R[np.ix_(live, dead)]) if live else None
+            for c in dead:
+                V[s + c] = op.random_vector(rng_seed[0])
+                rng_seed[0] += 1
+            # the surviving columns are orthogonal to V[:s] already: the new ones go through the same sweeps (whole block)
+            _, G1, G10 = orthogonalise(s, s)
+            R_all, dead_n = cholesky_deflate(G1, G10)
+            R = R_all.copy()
+            R[:, dead] = R_all[:, live] @ X if live else 0.0
+            if dead_n:
+                return R, ([c for c in range(K) if c not in dead_n], R_all)
+        else:
+            R_all = R
+        rotate(K, K, np.linalg.inv(R_all), s)
+        # ||Q^T Q - I|| by one m = 0 sweep; one more Cholesky-QR when it is not at rounding level
+        _, Gq = sweep(0, s, None)
+        if np.abs(Gq - np.eye(K)).max() > 1e-12:
+            R2 = np.linalg.cholesky(0.5 * (Gq + Gq.conj().T)).conj().T
+            rotate(K, K, np.linalg.inv(R2), s)
+            R = R2 @ R
+        return R, None
+
+    def complete(p, q, live, R, R_all):
+        """the space is exhausted at V[:p] + the live columns of V[p:p+K]: orthonormalise those (R_all over them is their Cholesky
+        factor), apply H to them (the whole dimension is at most the basis size here) and fill T: V[:p + len(live)] spans an
+        invariant subspace.  Returns its size."""
+        s_ = len(live)
+        if s_ == 0:
+            return p
+        Rl = R_all[np.ix_(live, live)]
+        Wl = V[p:p + K][live].clone()
+        V[p:p + s_] = torch.as_tensor(np.linalg.inv(Rl), dtype=V.dtype, device=V.device).t() @ Wl
+        T[p:p + s_, q:q + K] = R[live, :]
+        Y = torch.empty((s_, n), dtype=V.dtype, device=V.device)
+        op.matvec_block(V[p:p + s_].t(), Y.t())
+        T[:p + s_, p:p + s_] = (V[:p + s_].conj() @ Y.t()).cpu().numpy()
+        return p + s_
+
+    # start block: K random vectors, orthonormalised
+    for c in range(K):
+        V[c] = x0 if c == 0 else op.random_vector(seed + c)
+    del x0
+    _, G = sweep(0, 0, None)
+    _, exhausted = normalise(0, G, G)
+    if exhausted is not None:
+        raise ValueError(f"lanczos_block_smallest: no {K} independent start vectors (dimension {n})")
+    q, p = 0, K  # T columns [0, q) are known; V[q:p] is the block to be multiplied next
+    while True:
+        invariant = False
+        while p + K <= mb + K:
+            t_a = tick()
+            op.matvec_block(V[q:p].t(), V[p:p + K].t())
+            t_b = tick()
+            h, G, G0 = orthogonalise(p, p)
+            T[:p, q:p] = h
+            R, exhausted = normalise(p, G, G0)
+            if prof is not None:
+                prof["matvec"] += t_b - t_a
+                prof["orth"] += tick() - t_b
+            if exhausted is not None:
+                q = complete(p, q, exhausted[0], R, exhausted[1])
+                invariant = True
+                break
+            q = p
+            T[p:p + K, q - K:q] = R
+            p += K
+        # the projected matrix: block tridiagonal (arrow-shaped after a restart); the residual block is R_last = T[q:q+K, q-K:q]
+        m_eff = q
+        Tm = T[:m_eff, :m_eff]
+        Tm = 0.5 * (Tm + Tm.conj().T)
+        theta, S = np.linalg.eigh(Tm)
+        Rl = np.zeros((K, K), dtype=T.dtype) if invariant else T[q:q + K, q - K:q]
+        kk = min(k, m_eff)
+        coup = Rl @ S[m_eff - K:m_eff, :]  # K x m_eff: residual of Ritz pair i = ||coup[:, i]||
+        res = [float(np.linalg.norm(coup[:, i])) for i in range(kk)]
+        scale = max(float(np.abs(theta).max()), 1e-300)
+        history.append((op.matvecs, [float(t) for t in theta[:kk]], res))
+        if verbose:
+            print(f"[lanczos-block K={K}] restart {restarts}: matvecs={op.matvecs} theta={theta[:kk]} res={res}", flush=True)
+        done = all(r <= eps * scale for r in res) or invariant
+        if done or restarts >= max_restarts:
+            St = torch.as_tensor(S[:, :kk], dtype=V.dtype, device=V.device)
+            Y = torch.mm(St.t(), V[:m_eff])  # Ritz vectors, [kk, n]
+            vecs = [Y[i].clone() for i in range(kk)]
+            op.check()
+            if prof is not None:
+                print(f"[lanczos-block] profile: " + ", ".join(f"{a} {b:.2f} s" for a, b in prof.items()), flush=True)
+            return EigenResult([float(t) for t in theta[:kk]], vecs, res, op.matvecs, restarts, bool(done),
+                               time.perf_counter() - t0, history)
+        # thick restart: the `keep` lowest Ritz vectors, then the residual block
+        t_a = tick()
+        keep = min(m_eff - 2 * K, kk + max(K, (m_eff - kk) // 3))
+        rotate(m_eff, keep, S[:, :keep])
+        V[keep:keep + K] = V[q:q + K]
+        T[:, :] = 0
+        for i in range(keep):
+            T[i, i] = theta[i]
+        T[keep:keep + K, :keep] = coup[:, :keep]
+        T[:keep, keep:keep + K] = coup[:, :keep].conj().T
+        q, p = keep, keep + K
+        restarts += 1
+        if prof is not None:
+            prof["restart"] += tick() - t_a
+
+
 def diagonalize(config, num_evals: int = 1, eps: float = 1e-6, num_partitions: int = 1, dtype=None, output: str | None = None,
-                max_basis: int = 24, verbose: bool = False):
+                max_basis: int = 24, verbose: bool = False, block_size: int = 1):
     """`Diagonalize.main` (Diagonalize.chpl:258-332) on one device: config (dict or YAML path) ->
     representatives (enumerated on the GPU; an existing HDF5 `output` that already holds basis/representatives is
     reused and extended, like makeBasisStates :227-246) ->
     eigenpairs; `output` (.npz) receives what the reference writes to its HDF5 groups:
-    basis/representatives, hamiltonian/eigenvalues, hamiltonian/eigenvectors, hamiltonian/residuals."""
+    basis/representatives, hamiltonian/eigenvalues, hamiltonian/eigenvectors, hamiltonian/residuals.
+    block_size (the reference's kMaxBlockSize, Diagonalize.chpl:172,192): 1 = lanczos_smallest; 2..16 = lanczos_block_smallest,
+    which finds degenerate levels with their multiplicity (up to block_size)."""
     import os
 
     import numpy as np
@@ -274,6 +557,8 @@ def diagonalize(config, num_evals: int = 1, eps: float = 1e-6, num_partitions: i
 
     from . import api
 
+    if isinstance(block_size, bool) or not isinstance(block_size, int) or not 1 <= block_size <= 16:
+        raise ValueError(f"block_size = {block_size!r}: 1 <= block_size <= 16")
     if isinstance(config, str):
         basis, h = api.loadConfigFromYaml(config, hamiltonian=True)
     else:
@@ -304,16 +589,31 @@ def diagonalize(config, num_evals: int = 1, eps: float = 1e-6, num_partitions: i
         reps, masks = api.enumerateStates(basis, num_partitions)
     # one plan, hundreds of matvecs: what is left of HBM after the Krylov basis may hold the resolved packet streams
     # (ls_amd_plan_cache_slots; LS_AMD_SLOT_CACHE=0 keeps the solver matrix-free)
+    n_total = sum(int(r_.numel()) for r_ in reps)
+    if block_size > n_total:
+        raise ValueError(f"block_size = {block_size} exceeds the dimension {n_total} of the basis")
     cache_bytes = 0
     # (LS_AMD_SLOT_CACHE has one meaning everywhere: bytes; 0 = off; set = the C plan applies it at creation, nothing to add here)
     if num_partitions == 1 and os.environ.get("LS_AMD_SLOT_CACHE") is None:
         n_states = int(reps[0].numel())
         free, _total = torch.cuda.mem_get_info()
-        cache_bytes = max(0, int(free) - (max_basis + 6) * n_states * (16 if dtype == torch.complex128 else 8) - (4 << 30))
+        if block_size == 1:
+            reserve = (max_basis + 6) * n_states * (16 if dtype == torch.complex128 else 8) + (4 << 30)
+        else:
+            # the block basis (max(max_basis, 2 num_evals + 3 K) vectors), its extra block and one block of slack, the margin of the
+            # single-vector solver, and the packet buffer of the block matvec (used for the rows the cache leaves out)
+            mb = max(max_basis, 2 * num_evals + 3 * block_size)
+            resolve = int(os.environ.get("LS_AMD_BLOCK_RESOLVE_BYTES", "0") or 0)
+            resolve = resolve if resolve > 0 else (1 << 30)
+            reserve = (mb + 2 * block_size + 6) * n_states * (16 if dtype == torch.complex128 else 8) + (4 << 30) + resolve
+        cache_bytes = max(0, int(free) - reserve)
     op = LocalOperator(h, reps, dtype, slot_cache_bytes=cache_bytes)
     if verbose and op.cached_rows:
         print(f"[diagonalize] slot cache: {op.cached_rows} rows, {op.plan.slot_cache[1] / 1e9:.2f} GB", flush=True)
-    r = lanczos_smallest(op, num_evals=num_evals, eps=eps, max_basis=max_basis, verbose=verbose)
+    if block_size == 1:
+        r = lanczos_smallest(op, num_evals=num_evals, eps=eps, max_basis=max_basis, verbose=verbose)
+    else:
+        r = lanczos_block_smallest(op, num_evals=num_evals, block_size=block_size, eps=eps, max_basis=max_basis, verbose=verbose)
     if output and output.endswith((".h5", ".hdf5")):
         # same groups/datasets as the reference's output file (Diagonalize.chpl:241,248-256)
         from . import hdf5

@@ -72,6 +72,21 @@ int ls_amd_orth_max_rows(void);
 int ls_amd_orth_pass(int m, int64_t n, double const *d_V, int64_t ldv, double *d_w, double const *d_h_in, double *d_out, void *stream);
 /* thick restart of such a solver: V[:m_out] <- S^T V[:m_in] in place (d_S: m_in x m_out, row-major; m_out <= m_in <= max rows) */
 int ls_amd_basis_rotate(int m_in, int m_out, int64_t n, double *d_V, int64_t ldv, double const *d_S, void *stream);
+/* Block eigensolvers (block Lanczos: diagonalize.py lanczos_block_smallest; the reference's kMaxBlockSize, Diagonalize.chpl:172,192).
+ * One sweep over the basis V (m rows of n f64, row stride ldv) and a block W (K rows, row stride ldw):
+ *     if d_H_in (m x K, row-major):  W_c <- W_c - sum_k H_in[k][c] V_k
+ *     d_out[k*K + c] = <V_k, W_c>  (k < m, over the updated W);    d_out[m*K + c*K + c'] = <W_c, W_c'>
+ * d_out: device [m*K + K*K].  m = 0 returns the Gram matrix of W alone (d_V may then be NULL).  One launch reads V once and W once,
+ * and writes W once when updating.  Limits: 0 <= m <= ls_amd_orth_block_max_rows() (128), 1 <= K <= 16, ldv >= n (m > 0),
+ * ldw >= n.  Requirements (not validated): W shares no element with V, d_out / d_H_in alias neither.  Bad arguments return -1
+ * with a message in ls_amd_last_error() and launch nothing. */
+int ls_amd_orth_block_max_rows(void);
+int ls_amd_orth_block_pass(int m, int K, int64_t n, double const *d_V, int64_t ldv, double *d_W, int64_t ldw, double const *d_H_in,
+                           double *d_out, void *stream);
+/* V[:m_out] <- S^T V[:m_in] in place (d_S: m_in x m_out, row-major, device; 1 <= m_out <= m_in <= ls_amd_orth_block_max_rows()):
+ * the thick restart of a block solver and the normalisation W <- W R^-1 of its Cholesky-QR.  Reads m_in rows once and writes m_out
+ * rows once, with no temporary in HBM. */
+int ls_amd_block_rotate(int m_in, int m_out, int64_t n, double *d_V, int64_t ldv, double const *d_S, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The host-pointer boundary: ls_chpl_matrix_vector_product (DMV:1095-1110) and ls_chpl_primme_matvec (Diagonalize.chpl:134-162)
