@@ -240,7 +240,7 @@ def parse_basis(cfg: dict) -> BasisSpec:
         if "number_spins" in b:
             raise ValueError(f"number_spins is a key of spin-1/2 bases, not of particle {particle!r} (use number_sites)")
         for key in ("hamming_weight", "spin_inversion", "symmetries"):
-            if b.get(key):
+            if b.get(key) and not (key == "symmetries" and particle == "spinless-fermion"):
                 raise ValueError(f"{key} is not supported for particle {particle!r}")
         if "number_sites" not in b:
             raise ValueError(f"particle {particle!r} needs number_sites")
@@ -249,7 +249,9 @@ def parse_basis(cfg: dict) -> BasisSpec:
             raise ValueError("number_up is a key of spinful-fermion bases")
         if nup is not None and npart is None:
             raise ValueError("a fixed number_up needs a fixed number_particles")
-        return BasisSpec(number_sites=int(b["number_sites"]), particle=particle,
+        L = int(b["number_sites"])
+        perms, sectors = _parse_symmetries(syms, L)
+        return BasisSpec(number_sites=L, particle=particle, permutations=perms, sectors=sectors,
                          number_particles=-1 if npart is None else int(npart), number_up=-1 if nup is None else int(nup))
     return BasisSpec(
         number_sites=int(b["number_spins"]),
@@ -258,6 +260,18 @@ def parse_basis(cfg: dict) -> BasisSpec:
         permutations=[[int(v) for v in s["permutation"]] for s in syms],
         sectors=[int(s["sector"]) for s in syms],
     )
+
+
+def _parse_symmetries(syms, L):
+    """`symmetries:` of a spinless-fermion basis: permutations of the number_sites modes (csrc/yaml.c checks the same)"""
+    perms, sectors = [], []
+    for g, s in enumerate(syms):
+        p = s.get("permutation") if isinstance(s, dict) else None
+        if not isinstance(p, list) or len(p) != L or "sector" not in s:
+            raise ValueError(f"basis.symmetries[{g}]: expected {{permutation: [{L} sites], sector: int}}")
+        perms.append([int(v) for v in p])
+        sectors.append(int(s["sector"]))
+    return perms, sectors
 
 
 def parse_operator(section: dict, basis: BasisSpec = None) -> OperatorSpec:

@@ -263,6 +263,10 @@ struct ls_amd_basis_ext {
     lsk_group_elem d4_transpose; /* the transpose network (the only compiled network of mode 5) */
     lsk_group_elem *d_d4_net;
     uint64_t *d_trow2;   /* mode 5: row table with the reversed row's fields in the high half */
+    /* projected spinless-fermion basis: the permutation sign of every element (lsk_fermi.hpp) -- fsign[g][i] = the modes j < i that
+     * element g puts above mode i -- and its device copy (lsk_basis.fsign) */
+    int fermi;
+    uint64_t *fsign, *d_fsign;
     int owns_representatives;
     uint64_t *d_reps_cache; /* device copy of `representatives` for the host-pointer entry points */
     uint64_t d_reps_count;
@@ -576,9 +580,41 @@ ls_hs_basis *ls_hs_create_basis(ls_hs_particle_type particle_type, int number_si
     return b;
 }
 
+/* The sign table of a projected spinless-fermion basis: with q = p^-1 (q[j] = the position mode j goes to, (g.a)[i] = a[p_i]),
+ * fsign[g][i] = { j < i : q[j] > q[i] }, so that sign(g, a) = parity(a & XOR_{i in occ(a)} fsign[g][i]) (include/ls_hs.h) */
+static void fermi_sign_table(struct ls_amd_basis_ext *e, int L) {
+    e->fsign = (uint64_t *)calloc((size_t)e->order * (size_t)L, sizeof(uint64_t));
+    int q[64];
+    for (int g = 0; g < e->order; ++g) {
+        int const *p = e->perms + (size_t)g * L;
+        for (int i = 0; i < L; ++i) q[p[i]] = i;
+        for (int i = 0; i < L; ++i)
+            for (int j = 0; j < i; ++j)
+                if (q[j] > q[i]) e->fsign[(size_t)g * L + i] |= 1ULL << j;
+    }
+    e->fermi = 1;
+}
+
+ls_hs_basis *ls_hs_create_spinless_fermion_basis(int number_sites, int number_particles, int number_generators, int const *permutations,
+                                                 int const *sectors) {
+    if (number_sites < 1 || number_sites > 64) { set_error("spinless fermions: number_sites must be in [1, 64]"); return NULL; }
+    if (number_particles < -1 || number_particles > number_sites) { set_error("spinless fermions: number_particles must be in [0, number_sites] or -1"); return NULL; }
+    ls_hs_basis *b = ls_hs_create_spin_basis(number_sites, number_particles, 0, number_generators, permutations, sectors);
+    if (!b) return NULL;
+    b->particle_type = LS_HS_SPINLESS_FERMION;
+    b->number_particles = number_particles;
+    b->number_up = -1;
+    struct ls_amd_basis_ext *e = BEXT(b);
+    if (e->order > 1) fermi_sign_table(e, number_sites);
+    return b;
+}
+
 ls_hs_basis *ls_hs_clone_basis(ls_hs_basis const *basis) {
     struct ls_amd_basis_ext const *e = BEXT(basis);
-    ls_hs_basis *b = basis->particle_type != LS_HS_SPIN
+    ls_hs_basis *b = basis->particle_type == LS_HS_SPINLESS_FERMION
+                         ? ls_hs_create_spinless_fermion_basis(basis->number_sites, basis->number_particles, e->n_generators, e->gen_perms,
+                                                               e->gen_sectors)
+                     : basis->particle_type != LS_HS_SPIN
                          ? ls_hs_create_basis(basis->particle_type, basis->number_sites, basis->number_particles, basis->number_up)
                          : ls_hs_create_spin_basis(basis->number_sites, e->hamming_weight, basis->spin_inversion,
                                                    e->n_generators, e->gen_perms, e->gen_sectors);
@@ -659,8 +695,9 @@ void ls_hs_destroy_basis(ls_hs_basis *b) {
     if (e->d_trow) lsk_free(e->d_trow);
     if (e->d_d4_net) lsk_free(e->d_d4_net);
     if (e->d_trow2) lsk_free(e->d_trow2);
+    if (e->d_fsign) lsk_free(e->d_fsign);
     if (e->owns_representatives && b->representatives.elts) free(b->representatives.elts);
-    free(e->gen_perms); free(e->gen_sectors); free(e->perms); free(e->elems); free(e->coset_ids);
+    free(e->gen_perms); free(e->gen_sectors); free(e->perms); free(e->elems); free(e->coset_ids); free(e->fsign);
     reg_del(b);
     int const adopted = e->adopted;
     free(e);
@@ -703,6 +740,14 @@ void ls_hs_unchecked_set_representatives(ls_hs_basis *b, chpl_external_array con
 }
 
 int ls_amd_basis_group_order(ls_hs_basis const *b) { return BEXT(b)->order; }
+int ls_amd_basis_fermion_signs(ls_hs_basis const *b) { return BEXT(b)->fermi; }
+/* test hook (no device): sign(g, state) of group element `element` of a projected spinless-fermion basis by the device code's host
+ * mirror -- closed form for rotations and reflections, or (table != 0) the sign table for every element; 0 on bad arguments */
+int ls_amd_test_fermion_sign(ls_hs_basis const *b, int element, uint64_t state, int table) {
+    struct ls_amd_basis_ext const *e = BEXT(b);
+    if (!e->fermi || element < 0 || element >= e->order) return 0;
+    return lsk_test_fermi_parity(e->elems[element], e->fsign + (size_t)element * NBITS(b), state, NBITS(b), table) ? -1 : 1;
+}
 uint64_t ls_amd_basis_apply_group_element(ls_hs_basis const *b, int element, uint64_t state) {
     return host_apply_elem(BEXT(b)->elems + element, state, NBITS(b));
 }
@@ -919,6 +964,19 @@ static int basis_device_unlocked(ls_hs_basis const *b, lsk_basis *out) {
     out->trow = NULL;
     out->d4_mask = 0;
     out->trow2 = NULL;
+    out->fermi = e->fermi;
+    if (e->fermi) {
+        /* signed characters: the norm of an orbit can vanish in any sector, so never a mode that assumes it does not (modes 1-5 only
+         * deliver the orbit minimum) -- the element loop of mode 0, with the sign table in place of mode 5's row table */
+        if (!e->d_fsign) {
+            size_t const bytes = sizeof(uint64_t) * (size_t)e->order * (size_t)NBITS(b);
+            void *p = NULL;
+            if (lsk_malloc(&p, bytes) != 0 || lsk_h2d(p, e->fsign, bytes) != 0) { if (p) lsk_free(p); return dev_error(); }
+            e->d_fsign = (uint64_t *)p;
+        }
+        out->fsign = e->d_fsign;
+        return 0;
+    }
     /* LS_AMD_K4 (test hook): general = the element loop with characters and norms even in trivial sectors; brute = trivial
      * sectors by the plain loop over every element (no run pruning, no translation cosets) */
     char const *k4env = getenv("LS_AMD_K4");
@@ -1304,9 +1362,13 @@ int ls_amd_adopt_basis(ls_hs_basis const *basis, int number_generators, int cons
     if (!basis) return set_error("null basis");
     if (reg_get(basis)) return set_error("basis %p is already registered", (void const *)basis);
     ls_hs_basis *tmp;
-    if (basis->particle_type != LS_HS_SPIN) {
-        /* fermionic prefixes: number_sites, number_particles, number_up, particle_type; no symmetries (fermionic permutation signs
-         * are not implemented) */
+    if (basis->particle_type == LS_HS_SPINLESS_FERMION) {
+        /* spinless-fermion prefix: number_sites, number_particles, particle_type; site permutations with their signs on the modes */
+        if (basis->spin_inversion != 0 || basis->number_up != -1) return set_error("spinless-fermion bases have no spin inversion and no number_up");
+        tmp = ls_hs_create_spinless_fermion_basis(basis->number_sites, basis->number_particles, number_generators, permutations, sectors);
+    } else if (basis->particle_type != LS_HS_SPIN) {
+        /* spinful prefixes: number_sites, number_particles, number_up, particle_type; no symmetries (the lift of site permutations to
+         * both species is not implemented) */
         if (number_generators != 0 || basis->spin_inversion != 0 || basis->requires_projection)
             return set_error("fermionic bases with symmetries are not supported");
         tmp = ls_hs_create_basis(basis->particle_type, basis->number_sites, basis->number_particles, basis->number_up);
@@ -2999,6 +3061,18 @@ int ls_amd_plan_create(ls_amd_plan **out, ls_hs_operator const *op, ls_amd_dtype
     pl->me = my_partition;
     pl->n_local = my_partition < 0 ? num_partitions : 1;
     if (operator_device(op, &pl->dop) != 0 || basis_device(op->basis, &pl->dbs) != 0) { free(pl); return -1; }
+    if (pl->dbs.fermi) {
+        /* projected spinless fermions: the signed K4 exists in the indexed pull kernel of one partition (fused, or resolve + gather) and
+         * nowhere else -- every other path would run without the signs, so it is refused here, before anything launches */
+        char const *why = NULL, *ev = getenv("LS_AMD_PULL_VALUES"), *ei = getenv("LS_AMD_PULL_INDEXED"), *em = getenv("LS_AMD_MODE");
+        if (my_partition >= 0) why = "one partition per process";
+        else if (num_partitions != 1) why = "more than one partition";
+        else if (mode == LS_AMD_MODE_PUSH || (mode == LS_AMD_MODE_AUTO && em && strcmp(em, "push") == 0)) why = "push mode";
+        else if (!OEXT(op)->is_hermitian) why = "a non-Hermitian operator";
+        else if (ev && atoi(ev) != 0) why = "LS_AMD_PULL_VALUES=1";
+        else if (ei && atoi(ei) == 0) why = "LS_AMD_PULL_INDEXED=0";
+        if (why) { free(pl); return set_error("projected fermionic bases run the indexed pull kernel of one partition only: %s is not supported", why); }
+    }
     if (dtype == LS_AMD_F64) {
         /* f64 vectors: characters must be real as well (the reference casts c128 -> f64, DMV:91,109) */
         for (int g = 0; g < BEXT(op->basis)->order; ++g)
@@ -3198,7 +3272,7 @@ int ls_amd_plan_create(ls_amd_plan **out, ls_hs_operator const *op, ls_amd_dtype
              * c128 vectors, of the replicated-x exchange -- no rank may do O(N) work per matvec there -- and of the slot cache). */
             e = getenv("LS_AMD_PULL_VALUES");
             int const want_values = e ? atoi(e) != 0 : LS_AMD_PULL_VALUES_DEFAULT;
-            if (want_values && !pl->cplx && !pl->slot_cache && pl->split_rows == 0) {
+            if (want_values && !pl->cplx && !pl->slot_cache && pl->split_rows == 0 && !pl->dbs.fermi) { /* (no signs in the value-table kernel) */
                 size_t fr = 0, tot = 0;
                 size_t const need = (size_t)32 << pl->gtab->tab.bbits;
                 void *vt = NULL;
@@ -3208,6 +3282,10 @@ int ls_amd_plan_create(ls_amd_plan **out, ls_hs_operator const *op, ls_amd_dtype
                 }
             }
         }
+    }
+    if (pl->dbs.fermi && (!pl->idx_mode || pl->d_vtab)) {
+        ls_amd_plan_destroy(pl);
+        return set_error("projected fermionic bases run the indexed pull kernel of one partition only: no static index table for this basis");
     }
     if (lsk_sync(stream) != 0) { ls_amd_plan_destroy(pl); return dev_error(); }
     *out = pl;
@@ -3304,6 +3382,7 @@ static int plan_create_replicated_impl(ls_amd_plan **out, ls_hs_operator const *
     if (!op || !op->basis) return set_error("null operator");
     if (ls_hs_basis_number_words(op->basis) != 1) return set_error("bases with more than 64 bits are not yet implemented");
     if (!OEXT(op)->is_hermitian) return set_error("replicated-x (pull) plans need a Hermitian operator");
+    if (BEXT(op->basis)->fermi) return set_error("projected fermionic bases: replicated-x plans are not supported (one partition only)");
     if (num_partitions < 1 || num_partitions > LSK_MAX_PARTS || my_partition < 0 || my_partition >= num_partitions)
         return set_error("bad partition arguments");
     if (dtype == LS_AMD_F64 && !OEXT(op)->is_real) return set_error("an operator with complex coefficients needs dtype c128");

@@ -156,6 +156,7 @@ extern "C" int lsk_tile(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, i
                         int64_t row0, int64_t row1, uint64_t const *reps, double const *norms, void const *x,
                         void *y, unsigned long long *d_cursors, lsk_round_layout const *d_layout, void *d_send,
                         unsigned long long *d_counts, int *d_err, void *stream) {
+    if (bs.fermi) { snprintf(g_err, sizeof(g_err), "%s: no permutation signs on this path (projected fermionic bases: lsk_fermi_pull)", __func__); return -1; }
     if (row1 <= row0 || op.n_groups == 0) return 0;
     if (P > LSK_MAX_PARTS || P < 1) { snprintf(g_err, sizeof(g_err), "lsk_tile: bad partition count %d", P); return -1; }
     if (!count_only && ix.kind != LSK_INDEX_SEARCH) { snprintf(g_err, sizeof(g_err), "lsk_tile needs a SEARCH index"); return -1; }
@@ -395,6 +396,7 @@ extern "C" int lsk_tile_wv_max_parts(void) { return 64; }
 extern "C" int lsk_tile_wv(lsk_operator op, lsk_basis bs, lsk_index ix, lsk_gdir gd, int cplx, int count_only, int P, int me,
                            int64_t row0, int64_t row1, uint64_t const *reps, double const *norms, void const *x, void *y,
                            uint32_t *d_wtab, lsk_round_layout const *d_layout, void *d_send, int *d_err, lsk_gtab own_gt, void *stream) {
+    if (bs.fermi) { snprintf(g_err, sizeof(g_err), "%s: no permutation signs on this path (projected fermionic bases: lsk_fermi_pull)", __func__); return -1; }
     if (row1 <= row0 || op.n_groups == 0) return 0;
     if (P > lsk_tile_wv_max_parts() || P < 1 || !d_wtab) { snprintf(g_err, sizeof(g_err), "lsk_tile_wv: bad partition count %d or no wave table", P); return -1; }
     const bool pk12 = !count_only && gd.entries != nullptr;

@@ -180,6 +180,7 @@ __global__ __launch_bounds__(kBlock) void k_norms(lsk_basis bs, lsk_group_elem c
 }
 extern "C" int lsk_norms(lsk_basis bs, int64_t n, uint64_t const *reps, double *norms, void *stream) {
     if (n == 0) return 0;
+    if (bs.fermi) return lsk_fermi_norms(bs, n, reps, norms, stream);
     hipLaunchKernelGGL(k_norms, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, bs, bs.elems, n, reps, norms);
     LSK_LAUNCH_CHECK();
     return 0;
@@ -285,6 +286,7 @@ __global__ __launch_bounds__(kBlock) void k_state_info(lsk_basis bs, lsk_group_e
 extern "C" int lsk_state_info(lsk_basis bs, int64_t n, uint64_t const *alphas, uint64_t *betas, double *characters,
                               double *norms, void *stream) {
     if (n == 0) return 0;
+    if (bs.fermi) return lsk_fermi_state_info(bs, n, alphas, betas, characters, norms, stream);
     hipLaunchKernelGGL(k_state_info, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, bs, bs.elems, n, alphas, betas, characters, norms);
     LSK_LAUNCH_CHECK();
     return 0;
@@ -721,8 +723,12 @@ extern "C" int lsk_enumerate(lsk_basis bs, uint64_t const *d_binom, int64_t n_ca
     LSK_CHECK(hipMalloc((void **)&flags, 8 * n_threads));
     LSK_CHECK(hipMalloc((void **)&counts, 8 * n_threads));
     LSK_CHECK(hipMalloc((void **)&offsets, 8 * n_threads));
-    hipLaunchKernelGGL(k_enum_flags, dim3(grid_for(n_threads)), dim3(kBlock), 0, s, bs, bs.elems, d_binom, n_cand, n_threads, flags, counts);
-    LSK_LAUNCH_CHECK();
+    if (bs.fermi) { // signed stabiliser sums (k_fermi.hip)
+        if (lsk_fermi_enum_flags(bs, d_binom, n_cand, n_threads, kEnumChunk, flags, counts, s) != 0) return -1;
+    } else {
+        hipLaunchKernelGGL(k_enum_flags, dim3(grid_for(n_threads)), dim3(kBlock), 0, s, bs, bs.elems, d_binom, n_cand, n_threads, flags, counts);
+        LSK_LAUNCH_CHECK();
+    }
     if (lsk_internal_exclusive_scan_i64(n_threads, counts, offsets, s) != 0) return -1;
     int64_t last_off = 0, last_cnt = 0;
     LSK_CHECK(hipMemcpy(&last_off, offsets + (n_threads - 1), 8, hipMemcpyDeviceToHost));

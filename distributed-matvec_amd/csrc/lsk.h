@@ -93,7 +93,14 @@ typedef struct lsk_basis {
      *    in its high half (torus_min_d2, lsk_dev.hpp). */
     int k4_mode, reflect;
     int d4_mask;                    /* mode 5 */
-    uint64_t const *trow2;          /* mode 5: device [2^tw] */
+    /* projected spinless-fermion basis: every group element carries the permutation sign of the Fock state (include/ls_hs.h);
+     * always K4 mode 0, so the mode-5 row table is never read and its pointer slot holds the sign table instead (the layout of
+     * this struct, which every kernel receives by value, stays as it was) */
+    int fermi;
+    union {
+        uint64_t const *trow2;      /* mode 5: device [2^tw] */
+        uint64_t const *fsign;      /* fermi: device [n_elems][number_sites] -- B_g[i] = the modes j < i that g puts above i */
+    };
     int tw, n_cosets;               /* mode 4 / 5 */
     uint64_t tcol0;                 /* mode 4: the bits of column x = 0 */
     lsk_group_elem const *cosets;   /* mode 4: device [n_cosets] */
@@ -497,6 +504,20 @@ int lsk_bench_k4(int L, int inv, int reflect, int variant, int64_t n, uint64_t c
 int lsk_scatter(lsk_index ix, int cplx, int64_t n, uint64_t const *betas, void const *vals, void *y,
                 double const *norms /* NULL, or per-row norms multiplied in (K4 modes 1, 2) */, int *d_err,
                 void *stream);
+
+/* projected spinless-fermion bases (k_fermi.hip): the sign-aware K4 of enumeration, norms, state_info and the pull kernel ----- */
+/* parity of sign(g, a) for element e with sign-table row tab[number_sites] (host mirror of the device code; table != 0 forces the
+ * table form for ROT / REVROT elements as well) */
+int lsk_test_fermi_parity(lsk_group_elem e, uint64_t const *tab, uint64_t a, int L, int table);
+int lsk_fermi_enum_flags(lsk_basis bs, uint64_t const *d_binom, int64_t n_cand, int64_t n_threads, int chunk, uint64_t *flags,
+                         int64_t *counts, void *stream);
+int lsk_fermi_norms(lsk_basis bs, int64_t n, uint64_t const *reps, double *norms, void *stream);
+int lsk_fermi_state_info(lsk_basis bs, int64_t n, uint64_t const *alphas, uint64_t *betas, double *characters, double *norms,
+                         void *stream);
+/* k_pull_t for bs.fermi: wide = 64-bit words, sink = 0 fused / 1 resolve (the value table is refused) */
+int lsk_fermi_pull(lsk_operator op, lsk_basis bs, int wide, int cplx, int sink, int64_t row0, int64_t row1, uint64_t const *reps,
+                   double const *norms_local, lsk_pullidx ix, uint64_t const *reps_global, int64_t n_global, void const *xsrc, int halo,
+                   void *y, lsk_pullbuf buf, int *d_err, void *stream);
 
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */

@@ -653,8 +653,39 @@ static int y_is_unset(ynode const *n) {
     if (n->kind == Y_SCALAR) return n->str && strcmp(n->str, "0") == 0;
     return n->n == 0;
 }
+/* basis.symmetries: ng generators of L sites each ({permutation, sector}); the arrays are the caller's to free */
+static int symmetries_from(ynode const *b, long L, int *ng_out, int **perms_out, int **sectors_out) {
+    ynode const *syms = y_get(b, "symmetries");
+    int ng = 0;
+    int *perms = NULL, *sectors = NULL;
+    if (syms && !y_is_null(syms)) {
+        if (syms->kind != Y_SEQ) return ls_amd_internal_error("basis.symmetries: expected a sequence");
+        ng = syms->n;
+        perms = (int *)calloc((size_t)(ng > 0 ? ng : 1) * (size_t)L, sizeof(int));
+        sectors = (int *)calloc((size_t)(ng > 0 ? ng : 1), sizeof(int));
+        for (int g = 0; g < ng; ++g) {
+            ynode const *perm = y_get(syms->vals[g], "permutation");
+            long sec = 0;
+            int bad = !perm || perm->kind != Y_SEQ || perm->n != L || y_int(y_get(syms->vals[g], "sector"), "symmetries[].sector", &sec) != 0;
+            for (int i = 0; i < L && !bad; ++i) {
+                long v = 0;
+                bad = y_int(perm->vals[i], "symmetries[].permutation", &v) != 0;
+                perms[(size_t)g * (size_t)L + i] = (int)v;
+            }
+            if (bad) {
+                free(perms); free(sectors);
+                return ls_amd_internal_error("basis.symmetries[%d]: expected {permutation: [%ld sites], sector: int}", g, L);
+            }
+            sectors[g] = (int)sec;
+        }
+    }
+    *ng_out = ng;
+    *perms_out = perms;
+    *sectors_out = sectors;
+    return 0;
+}
 /* particle: spinless-fermion | spinful-fermion -- number_sites, number_particles (null: unrestricted), number_up (spinful; null:
- * only number_particles fixed); no symmetries */
+ * only number_particles fixed); symmetries for spinless fermions only (permutations of the number_sites modes) */
 static ls_hs_basis *fermion_basis_from(ynode const *b, char const *particle) {
     int const spinful = strcmp(particle, "spinful-fermion") == 0;
     if (y_get(b, "number_spins")) {
@@ -662,7 +693,10 @@ static ls_hs_basis *fermion_basis_from(ynode const *b, char const *particle) {
     }
     static char const *const unsupported[] = {"hamming_weight", "spin_inversion", "symmetries"};
     for (int k = 0; k < 3; ++k)
-        if (!y_is_unset(y_get(b, unsupported[k]))) { ls_amd_internal_error("%s is not supported for particle '%s'", unsupported[k], particle); return NULL; }
+        if (!y_is_unset(y_get(b, unsupported[k])) && (spinful || k != 2)) {
+            ls_amd_internal_error("%s is not supported for particle '%s'", unsupported[k], particle);
+            return NULL;
+        }
     long L, n = -1, nup = -1;
     if (!y_get(b, "number_sites")) { ls_amd_internal_error("particle '%s' needs number_sites", particle); return NULL; }
     if (y_int(y_get(b, "number_sites"), "basis.number_sites", &L) != 0) return NULL;
@@ -672,7 +706,14 @@ static ls_hs_basis *fermion_basis_from(ynode const *b, char const *particle) {
         if (y_int(y_get(b, "number_up"), "basis.number_up", &nup) != 0) return NULL;
         if (n < 0) { ls_amd_internal_error("a fixed number_up needs a fixed number_particles"); return NULL; }
     }
-    return ls_hs_create_basis(spinful ? LS_HS_SPINFUL_FERMION : LS_HS_SPINLESS_FERMION, (int)L, (int)n, (int)nup);
+    if (spinful) return ls_hs_create_basis(LS_HS_SPINFUL_FERMION, (int)L, (int)n, (int)nup);
+    if (L < 1 || L > 64) { ls_amd_internal_error("spinless fermions: number_sites must be in [1, 64]"); return NULL; }
+    int ng = 0;
+    int *perms = NULL, *sectors = NULL;
+    if (symmetries_from(b, L, &ng, &perms, &sectors) != 0) return NULL;
+    ls_hs_basis *basis = ls_hs_create_spinless_fermion_basis((int)L, (int)n, ng, perms, sectors);
+    free(perms); free(sectors);
+    return basis;
 }
 static ls_hs_basis *basis_from(ynode const *b) {
     if (!b || b->kind != Y_MAP) { ls_amd_internal_error("the config has no `basis` section"); return NULL; }
@@ -691,31 +732,9 @@ static ls_hs_basis *basis_from(ynode const *b) {
     if (L < 1 || L > 64) { ls_amd_internal_error("basis.number_spins = %ld: 1 .. 64 sites are supported", L); return NULL; }
     if (!y_is_null(y_get(b, "hamming_weight")) && y_int(y_get(b, "hamming_weight"), "basis.hamming_weight", &hw) != 0) return NULL;
     if (!y_is_null(y_get(b, "spin_inversion")) && y_int(y_get(b, "spin_inversion"), "basis.spin_inversion", &inv) != 0) return NULL;
-    ynode const *syms = y_get(b, "symmetries");
     int ng = 0;
     int *perms = NULL, *sectors = NULL;
-    if (syms && !y_is_null(syms)) {
-        if (syms->kind != Y_SEQ) { ls_amd_internal_error("basis.symmetries: expected a sequence"); return NULL; }
-        ng = syms->n;
-        perms = (int *)calloc((size_t)(ng > 0 ? ng : 1) * (size_t)L, sizeof(int));
-        sectors = (int *)calloc((size_t)(ng > 0 ? ng : 1), sizeof(int));
-        for (int g = 0; g < ng; ++g) {
-            ynode const *perm = y_get(syms->vals[g], "permutation");
-            long sec = 0;
-            int bad = !perm || perm->kind != Y_SEQ || perm->n != L || y_int(y_get(syms->vals[g], "sector"), "symmetries[].sector", &sec) != 0;
-            for (int i = 0; i < L && !bad; ++i) {
-                long v = 0;
-                bad = y_int(perm->vals[i], "symmetries[].permutation", &v) != 0;
-                perms[(size_t)g * (size_t)L + i] = (int)v;
-            }
-            if (bad) {
-                free(perms); free(sectors);
-                ls_amd_internal_error("basis.symmetries[%d]: expected {permutation: [%ld sites], sector: int}", g, L);
-                return NULL;
-            }
-            sectors[g] = (int)sec;
-        }
-    }
+    if (symmetries_from(b, L, &ng, &perms, &sectors) != 0) return NULL;
     ls_hs_basis *basis = ls_hs_create_spin_basis((int)L, (int)hw, (int)inv, ng, perms, sectors);
     free(perms); free(sectors);
     return basis;

@@ -129,7 +129,9 @@ int ls_amd_locale_idx_of(uint64_t basis_state, int num_locales);
  * address, never in the struct: a foreign ls_hs_basis / ls_hs_operator only has to be registered once.
  *   ls_amd_adopt_basis     reads number_sites, number_up (Hamming weight or -1), spin_inversion, requires_projection and
  *                          `representatives` from the prefix; the symmetry generators are not part of the prefix and are
- *                          passed in the convention of ls_hs_create_spin_basis (0 generators for an unsymmetrised basis)
+ *                          passed in the convention of ls_hs_create_spin_basis (0 generators for an unsymmetrised basis);
+ *                          spinless-fermion prefixes (particle_type, number_sites, number_particles) take generators too, with
+ *                          the permutation signs of ls_hs_create_spinless_fermion_basis; spinful ones take none
  *   ls_amd_adopt_operator  rebuilds the term / flip-mask-group tables from off_diag_terms / diag_terms
  *                          (ls_hs_nonbranching_terms with number_bits <= 64); its basis must be known
  *   ls_amd_release         forgets an adopted object and frees its tables (the foreign struct is left alone)
@@ -422,6 +424,11 @@ int ls_amd_hashed_to_block(int64_t n, uint8_t const *d_masks, int num_locales, i
 
 /* test hooks: evaluate compiled host-side tables on the CPU (no device work) ------------------ */
 int ls_amd_basis_group_order(ls_hs_basis const *basis);
+/* 1 when the basis is a projected spinless-fermion basis, i.e. its group elements carry permutation signs (include/ls_hs.h) */
+int ls_amd_basis_fermion_signs(ls_hs_basis const *basis);
+/* test hook, no device: sign(g, state) = +-1 of group element `element` of such a basis, by the closed forms of rotations and
+ * reflections or (table != 0) by the sign table for every element; 0 on bad arguments */
+int ls_amd_test_fermion_sign(ls_hs_basis const *basis, int element, uint64_t state, int table);
 uint64_t ls_amd_basis_apply_group_element(ls_hs_basis const *basis, int element, uint64_t state);
 int ls_amd_basis_group_character(ls_hs_basis const *basis, int element, double *re, double *im);
 

@@ -102,7 +102,8 @@ void ls_hs_exit(void);  /* FFI.chpl:129 */
 ls_hs_basis *ls_hs_create_spin_basis(int number_sites, int hamming_weight, int spin_inversion,
                                      int number_generators, int const *permutations,
                                      int const *sectors);
-/* FFI.chpl:143-144 (declared there, commented out).  Any particle type, no symmetries:
+/* FFI.chpl:143-144 (declared there, commented out).  Any particle type, no symmetries (spinless fermions with symmetries:
+ * ls_hs_create_spinless_fermion_basis below):
  *   LS_HS_SPIN               number_up = Hamming weight or -1 (number_particles ignored)
  *   LS_HS_SPINLESS_FERMION   L <= 64 modes, mode i = bit i; number_particles fixed or -1; number_up must be -1
  *   LS_HS_SPINFUL_FERMION    L <= 32 sites, 2 L modes: mode (i, up) = bit i, mode (i, down) = bit i + L
@@ -115,6 +116,22 @@ ls_hs_basis *ls_hs_create_spin_basis(int number_sites, int hamming_weight, int s
  * factors with the modes the monomial itself touches removed (their occupations are fixed by m / r and folded into v).  For
  * c+_i c_j that makes s the modes strictly between i and j. */
 ls_hs_basis *ls_hs_create_basis(ls_hs_particle_type particle_type, int number_sites, int number_particles, int number_up);
+/* Spinless fermions with site permutations (not in the reference's ABI): number_sites <= 64 modes, number_particles fixed or -1,
+ * generators and sectors in the convention and with the errors of ls_hs_create_spin_basis.  Fermionic permutation signs:
+ *   a permutation acts on the modes as on spins, (g.a)[i] = a[p_i]; on operators U_g c+_j U_g+ = c+_{q_j} with q = p^-1, so
+ *   U_g |a> = sign(g, a) |g.a>,  sign(g, a) = (-1)^(number of occupied pairs j < j' with q_j > q_j'),
+ * and U is a representation of the group (U_g U_h = U_gh): closure, orders and sector characters are those of the spins.  The
+ * projected basis vector of a representative r is P|r> / ||P|r>||, P = (1/|G|) sum_g conj(chi(g)) U_g; with the signs
+ *   norm(r)^2 = (1/|G|) sum_{g in Stab(r)} chi(g) sign(g, r),
+ * which can vanish in any sector (4-site ring, N = 2: T^2 fixes 0101 with sign -1, so 0101 has no state in k = 0), and such
+ * orbits are not enumerated; ls_hs_state_info returns conj(chi(g0) sign(g0, a)) as the character of a minimising element g0.
+ * Matvecs of these bases run the indexed pull kernel of one partition (fused, resolve + gather, block, slot cache) and need a
+ * Hermitian operator; other plans are refused at creation.  That kernel's static index table has 2^bb buckets of 16 bytes with
+ * bb >= number_sites - 24 whatever the number of representatives (the tag of a key has at most 24 bits), so it costs 16 MB at
+ * 44 modes, 4 GB at 52 and 64 GB at 56, and above 60 modes (2^40 buckets) no plan can be built: bases of 61-64 modes are created,
+ * enumerated and answer ls_hs_state_info, but ls_amd_plan_create refuses them ("no static index table"). */
+ls_hs_basis *ls_hs_create_spinless_fermion_basis(int number_sites, int number_particles, int number_generators, int const *permutations,
+                                                 int const *sectors);
 ls_hs_basis *ls_hs_clone_basis(ls_hs_basis const *basis);       /* FFI.chpl:141 */
 void ls_hs_destroy_basis(ls_hs_basis *basis);                   /* FFI.chpl:142 */
 
@@ -138,7 +155,7 @@ typedef struct ls_hs_yaml_config {
 /* /root/reference/src/FFI.chpl:208-209.  The YAML subset of the YAML files under /root/reference/data (basis: number_spins, hamming_weight,
  * spin_inversion, symmetries; hamiltonian / observables: terms of `expression` + `sites`; anchors and aliases, block and
  * flow collections), and fermionic bases (particle: spinless-fermion | spinful-fermion, number_sites, number_particles,
- * number_up; expressions of c+ / c / n, see ls_hs_create_basis).  NULL on failure, with the reason in ls_amd_last_error(). */
+ * number_up, and symmetries for spinless fermions; expressions of c+ / c / n, see ls_hs_create_basis).  NULL on failure, with the reason in ls_amd_last_error(). */
 ls_hs_yaml_config *ls_hs_load_yaml_config(char const *filename);
 void ls_hs_destroy_yaml_config(ls_hs_yaml_config *config);
 /* the same from a NUL-terminated YAML text in memory (not in the reference's ABI) */
