@@ -157,7 +157,10 @@ def load():
         "ls_amd_plan_packet_index_bytes": (C.c_int64, [vp]),
         "ls_amd_scatter_round": (C.c_int, [vp, C.c_int, c_i64p, c_i64p, vp, vp, vp]),
         "ls_amd_adopt_basis": (C.c_int, [bp, C.c_int, c_intp, c_intp]),
+        "ls_amd_adopt_spinful_fermion_basis": (C.c_int, [bp, C.c_int, C.c_int, c_intp, c_intp]),
         "ls_amd_basis_fermion_signs": (C.c_int, [bp]),
+        "ls_amd_basis_spin_flip": (C.c_int, [bp]),
+        "ls_amd_test_group_element_kind": (C.c_int, [bp, C.c_int]),
         "ls_amd_test_fermion_sign": (C.c_int, [bp, C.c_int, C.c_uint64, C.c_int]),
         "ls_amd_adopt_operator": (C.c_int, [op]),
         "ls_amd_release": (None, [vp]),
@@ -227,6 +230,7 @@ def load():
         "ls_hs_create_spin_basis": (bp, [C.c_int, C.c_int, C.c_int, C.c_int, c_intp, c_intp]),
         "ls_hs_create_basis": (bp, [C.c_int, C.c_int, C.c_int, C.c_int]),
         "ls_hs_create_spinless_fermion_basis": (bp, [C.c_int, C.c_int, C.c_int, c_intp, c_intp]),
+        "ls_hs_create_spinful_fermion_basis": (bp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_intp, c_intp]),
         "ls_hs_clone_basis": (bp, [bp]),
         "ls_hs_destroy_basis": (None, [bp]),
         "ls_hs_create_operator_from_terms": (op, [bp, C.c_int, c_f64p, c_u64p, c_u64p, c_u64p, c_u64p]),

@@ -77,7 +77,9 @@ class Basis:
         sectors = (C.c_int * max(1, ng))(*spec.sectors)
         if spec.particle == "spinless-fermion" and ng > 0:  # with the permutation signs of the modes (parse_basis: number_up unset)
             p = L.ls_hs_create_spinless_fermion_basis(spec.number_sites, spec.number_particles, ng, perms, sectors)
-        elif spec.is_fermionic:  # no symmetries (parse_basis refuses them for spinful bases)
+        elif spec.particle == "spinful-fermion" and (ng > 0 or spec.spin_flip):  # site permutations lifted to both species, ↑↔↓ flip
+            p = L.ls_hs_create_spinful_fermion_basis(spec.number_sites, spec.number_particles, spec.number_up, spec.spin_flip, ng, perms, sectors)
+        elif spec.is_fermionic:  # no symmetries: the unprojected bases (closed-form index, k_hubbard)
             p = L.ls_hs_create_basis(_config.PARTICLES[spec.particle], spec.number_sites, spec.number_particles, spec.number_up)
         else:
             p = L.ls_hs_create_spin_basis(spec.number_sites, spec.hamming_weight, spec.spin_inversion, ng, perms, sectors)
@@ -106,7 +108,8 @@ class Basis:
     def isHammingWeightFixed(self): return bool(_lib.load().ls_hs_basis_has_fixed_hamming_weight(self.payload))
     def hasSpinInversionSymmetry(self): return bool(_lib.load().ls_hs_basis_has_spin_inversion_symmetry(self.payload))
     def hasPermutationSymmetries(self): return bool(_lib.load().ls_hs_basis_has_permutation_symmetries(self.payload))
-    def hasFermionSigns(self): return bool(_lib.load().ls_amd_basis_fermion_signs(self.payload))  # projected spinless fermions
+    def hasFermionSigns(self): return bool(_lib.load().ls_amd_basis_fermion_signs(self.payload))  # projected fermions
+    def spinFlip(self): return int(_lib.load().ls_amd_basis_spin_flip(self.payload))  # spinful fermions: ↑↔↓ character, 0 = none
     def minStateEstimate(self): return int(_lib.load().ls_hs_min_state_estimate(self.payload))
     def maxStateEstimate(self): return int(_lib.load().ls_hs_max_state_estimate(self.payload))
     def groupOrder(self): return int(_lib.load().ls_amd_basis_group_order(self.payload))

@@ -217,6 +217,7 @@ class BasisSpec:
     particle: str = "spin-1/2"
     number_particles: int = -1  # fermions: -1 unrestricted
     number_up: int = -1  # spinful fermions: -1 = only number_particles fixed
+    spin_flip: int = 0  # spinful fermions with number_up: the up <-> down flip's character (+1 / -1), 0 = none
 
     @property
     def is_fermionic(self) -> bool:
@@ -239,9 +240,18 @@ def parse_basis(cfg: dict) -> BasisSpec:
     if particle != "spin-1/2":
         if "number_spins" in b:
             raise ValueError(f"number_spins is a key of spin-1/2 bases, not of particle {particle!r} (use number_sites)")
+        # symmetries: spinless fermions (mode permutations), and the spinful (N, N_up) product basis (site permutations lifted to both
+        # species, spin_flip); the N-only spinful basis with symmetries is a spinless one on 2 L modes and stays refused
+        lifted = particle == "spinful-fermion" and b.get("number_up", None) is not None
         for key in ("hamming_weight", "spin_inversion", "symmetries"):
-            if b.get(key) and not (key == "symmetries" and particle == "spinless-fermion"):
-                raise ValueError(f"{key} is not supported for particle {particle!r}")
+            if b.get(key) and not (key == "symmetries" and (particle == "spinless-fermion" or lifted)):
+                raise ValueError(f"{key} is not supported for particle {particle!r}" + (" without number_up" if key == "symmetries" else ""))
+        flip = b.get("spin_flip", None) or 0
+        if flip and not lifted:
+            raise ValueError(f"spin_flip is a key of spinful-fermion bases with number_up, not of particle {particle!r}"
+                             + (" without number_up" if particle == "spinful-fermion" else ""))
+        if flip not in (0, 1, -1):
+            raise ValueError("spin_flip must be 1 or -1")
         if "number_sites" not in b:
             raise ValueError(f"particle {particle!r} needs number_sites")
         npart, nup = b.get("number_particles", None), b.get("number_up", None)
@@ -251,7 +261,9 @@ def parse_basis(cfg: dict) -> BasisSpec:
             raise ValueError("a fixed number_up needs a fixed number_particles")
         L = int(b["number_sites"])
         perms, sectors = _parse_symmetries(syms, L)
-        return BasisSpec(number_sites=L, particle=particle, permutations=perms, sectors=sectors,
+        if flip and 2 * int(nup) != int(npart):
+            raise ValueError("spin_flip requires number_up == number_particles - number_up")
+        return BasisSpec(number_sites=L, particle=particle, permutations=perms, sectors=sectors, spin_flip=int(flip),
                          number_particles=-1 if npart is None else int(npart), number_up=-1 if nup is None else int(nup))
     return BasisSpec(
         number_sites=int(b["number_spins"]),
@@ -263,7 +275,8 @@ def parse_basis(cfg: dict) -> BasisSpec:
 
 
 def _parse_symmetries(syms, L):
-    """`symmetries:` of a spinless-fermion basis: permutations of the number_sites modes (csrc/yaml.c checks the same)"""
+    """`symmetries:` of a fermionic basis: permutations of the number_sites modes (spinless) or sites (spinful); csrc/yaml.c checks
+    the same"""
     perms, sectors = [], []
     for g, s in enumerate(syms):
         p = s.get("permutation") if isinstance(s, dict) else None
@@ -311,9 +324,11 @@ def heisenberg_chain_config(L: int, symm: bool = False, spin_inversion=None) -> 
     return {"basis": basis, "hamiltonian": {"name": "Heisenberg Hamiltonian", "terms": terms}}
 
 
-def hubbard_config(sites: int, bonds, t=1.0, U=4.0, number_up=None, number_down=None, V=0.0, peierls=0.0) -> dict:
+def hubbard_config(sites: int, bonds, t=1.0, U=4.0, number_up=None, number_down=None, V=0.0, peierls=0.0, symmetries=None,
+                   spin_flip=None) -> dict:
     """Spinful Hubbard model -t sum_<ij>,s (e^{i phi} c+_is c_js + h.c.) + U sum_i n_i↑ n_i↓ + V sum_<ij> n_i n_j over `bonds`
-    (pairs (i, j)); half filling with N↑ = N↓ by default."""
+    (pairs (i, j)); half filling with N↑ = N↓ by default.  `symmetries` ([{permutation: sites, sector}]) and `spin_flip` (±1) go into
+    the basis section as they are: the sector of the (N↑, N↓) basis the model is projected on."""
     nu = sites // 2 if number_up is None else number_up
     nd = sites // 2 if number_down is None else number_down
     bonds = [[int(i), int(j)] for i, j in bonds]
@@ -328,8 +343,12 @@ def hubbard_config(sites: int, bonds, t=1.0, U=4.0, number_up=None, number_down=
         for s1 in ("↑", "↓"):
             for s2 in ("↑", "↓"):
                 terms.append({"expression": f"{V!r} × n₀{s1} n₁{s2}", "sites": bonds})
-    return {"basis": {"particle": "spinful-fermion", "number_sites": sites, "number_particles": nu + nd, "number_up": nu},
-            "hamiltonian": {"name": "Hubbard", "terms": terms}}
+    basis = {"particle": "spinful-fermion", "number_sites": sites, "number_particles": nu + nd, "number_up": nu}
+    if symmetries:
+        basis["symmetries"] = [{"permutation": [int(v) for v in s["permutation"]], "sector": int(s["sector"])} for s in symmetries]
+    if spin_flip:
+        basis["spin_flip"] = int(spin_flip)
+    return {"basis": basis, "hamiltonian": {"name": "Hubbard", "terms": terms}}
 
 
 def _c(z: complex) -> str:

@@ -267,6 +267,9 @@ struct ls_amd_basis_ext {
      * element g puts above mode i -- and its device copy (lsk_basis.fsign) */
     int fermi;
     uint64_t *fsign, *d_fsign;
+    /* projected spinful-fermion basis (ls_hs_create_spinful_fermion_basis): gen_perms holds the generators LIFTED to the 2 L modes
+     * (the n_generators - 1 site generators, then the half swap, when spin_flip != 0) */
+    int spin_flip;
     int owns_representatives;
     uint64_t *d_reps_cache; /* device copy of `representatives` for the host-pointer entry points */
     uint64_t d_reps_count;
@@ -387,6 +390,7 @@ static uint64_t host_delta_swap(uint64_t x, uint64_t m, int d) {
 static uint64_t host_apply_elem(lsk_group_elem const *e, uint64_t x, int L) {
     static int const dist[LSK_BENES_STAGES] = {32, 16, 8, 4, 2, 1, 2, 4, 8, 16, 32};
     uint64_t const mask = L >= 64 ? ~0ULL : ((1ULL << L) - 1);
+    if (e->kind & LSK_ELEM_LIFT) return lsk_test_fermi_apply_lift(*e, x, L); /* the fermionic kinds: the device code's own host mirror */
     if (e->kind == LSK_ELEM_BENES) {
         for (int s = 0; s < LSK_BENES_STAGES; ++s)
             if (e->masks[s]) x = host_delta_swap(x, e->masks[s], dist[s]);
@@ -609,9 +613,94 @@ ls_hs_basis *ls_hs_create_spinless_fermion_basis(int number_sites, int number_pa
     return b;
 }
 
+/* A lifted ring element of a spinful basis gets its closed-form kind (LSK_ELEM_LIFT, lsk.h): p over 2 L modes is s + s, or s + s
+ * followed by the half swap, with s a rotation or reflection of the L sites.  Everything else (tori, other lattices) keeps the
+ * network that compile_elem built; so does every element under LS_AMD_FERMI_LIFT=0 (A/B of the closed forms against the table). */
+static void classify_lifted_elem(int const *p, int L, lsk_group_elem *e) {
+    int s[32];
+    int const swap = p[0] >= L;
+    for (int i = 0; i < L; ++i) {
+        s[i] = p[i] - (swap ? L : 0);
+        if (s[i] < 0 || s[i] >= L || p[i + L] != s[i] + (swap ? 0 : L)) return;
+    }
+    lsk_group_elem site;
+    compile_elem(s, L, 0.0, 0.0, &site);
+    if (site.kind != LSK_ELEM_ROT && site.kind != LSK_ELEM_REVROT) return;
+    e->kind = LSK_ELEM_LIFT | (site.kind == LSK_ELEM_REVROT ? LSK_ELEM_LIFT_REV : 0) | (swap ? LSK_ELEM_LIFT_SWAP : 0);
+    e->k = site.k;
+}
+
+/* Spinful fermions with fixed (N_up, N_down) and site permutations (include/ls_hs.h): the product basis of ls_hs_create_basis with
+ * the group closed over the 2 L modes -- every site generator lifted as p + p, the up <-> down flip as the half swap i <-> i + L --
+ * and the sign table of those mode permutations.  The prefix keeps spin_inversion == 0 (that field means the bit complement). */
+ls_hs_basis *ls_hs_create_spinful_fermion_basis(int number_sites, int number_particles, int number_up, int spin_flip, int number_generators,
+                                                int const *permutations, int const *sectors) {
+    if (number_up == -1) { set_error("spinful fermions with symmetries need a fixed number_up (the (N, N_up) product basis)"); return NULL; }
+    if (spin_flip != 0 && spin_flip != 1 && spin_flip != -1) { set_error("spin_flip must be 0, 1 or -1"); return NULL; }
+    if (number_generators < 0 || (number_generators > 0 && (!permutations || !sectors))) { set_error("spinful fermions: bad generators"); return NULL; }
+    if (number_sites >= 1 && number_sites <= 32)
+        for (int g = 0; g < number_generators; ++g) {
+            uint64_t seen = 0;
+            for (int i = 0; i < number_sites; ++i) {
+                int v = permutations[g * number_sites + i];
+                if (v < 0 || v >= number_sites || ((seen >> v) & 1)) { set_error("generator %d is not a permutation", g); return NULL; }
+                seen |= 1ULL << v;
+            }
+        }
+    ls_hs_basis *b = ls_hs_create_basis(LS_HS_SPINFUL_FERMION, number_sites, number_particles, number_up);
+    if (!b) return NULL;
+    if (spin_flip != 0 && 2 * number_up != number_particles) {
+        ls_hs_destroy_basis(b);
+        set_error("spin_flip requires number_up == number_particles - number_up");
+        return NULL;
+    }
+    struct ls_amd_basis_ext *e = BEXT(b);
+    int const L = number_sites, M = 2 * L, ng = number_generators + (spin_flip != 0 ? 1 : 0);
+    e->spin_flip = spin_flip;
+    if (ng == 0) return b;
+    free(e->gen_perms); free(e->gen_sectors); free(e->perms); free(e->elems);
+    e->perms = NULL; e->elems = NULL;
+    e->n_generators = ng;
+    e->gen_perms = (int *)malloc(sizeof(int) * (size_t)ng * M);
+    e->gen_sectors = (int *)malloc(sizeof(int) * (size_t)ng);
+    for (int g = 0; g < number_generators; ++g) {
+        for (int i = 0; i < L; ++i) {
+            e->gen_perms[(size_t)g * M + i] = permutations[g * L + i];
+            e->gen_perms[(size_t)g * M + L + i] = permutations[g * L + i] + L;
+        }
+        e->gen_sectors[g] = sectors[g];
+    }
+    if (spin_flip != 0) {
+        for (int i = 0; i < L; ++i) { e->gen_perms[(size_t)(ng - 1) * M + i] = i + L; e->gen_perms[(size_t)(ng - 1) * M + L + i] = i; }
+        e->gen_sectors[ng - 1] = spin_flip > 0 ? 0 : 1; /* an element of order 2: sector 0 = character +1, 1 = -1 */
+    }
+    if (close_group(e, M) != 0) { ls_hs_destroy_basis(b); return NULL; }
+    b->requires_projection = e->order > 1;
+    if (e->order > 1) {
+        char const *env = getenv("LS_AMD_FERMI_LIFT");
+        if (!(env && atoi(env) == 0))
+            for (int g = 0; g < e->order; ++g) classify_lifted_elem(e->perms + (size_t)g * M, L, e->elems + g);
+        fermi_sign_table(e, M);
+    }
+    return b;
+}
+/* the site generators of such a basis, read back off the lifted ones (clone) */
+static ls_hs_basis *clone_spinful_projected(ls_hs_basis const *basis) {
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    int const L = basis->number_sites, ng = e->n_generators - (e->spin_flip != 0 ? 1 : 0);
+    int *perms = (int *)malloc(sizeof(int) * (size_t)(ng > 0 ? ng : 1) * L);
+    for (int g = 0; g < ng; ++g)
+        for (int i = 0; i < L; ++i) perms[g * L + i] = e->gen_perms[(size_t)g * 2 * L + i];
+    ls_hs_basis *b = ls_hs_create_spinful_fermion_basis(L, basis->number_particles, basis->number_up, e->spin_flip, ng, perms, e->gen_sectors);
+    free(perms);
+    return b;
+}
+
 ls_hs_basis *ls_hs_clone_basis(ls_hs_basis const *basis) {
     struct ls_amd_basis_ext const *e = BEXT(basis);
-    ls_hs_basis *b = basis->particle_type == LS_HS_SPINLESS_FERMION
+    ls_hs_basis *b = basis->particle_type == LS_HS_SPINFUL_FERMION && (e->n_generators > 0 || e->spin_flip != 0)
+                         ? clone_spinful_projected(basis)
+                     : basis->particle_type == LS_HS_SPINLESS_FERMION
                          ? ls_hs_create_spinless_fermion_basis(basis->number_sites, basis->number_particles, e->n_generators, e->gen_perms,
                                                                e->gen_sectors)
                      : basis->particle_type != LS_HS_SPIN
@@ -741,7 +830,13 @@ void ls_hs_unchecked_set_representatives(ls_hs_basis *b, chpl_external_array con
 
 int ls_amd_basis_group_order(ls_hs_basis const *b) { return BEXT(b)->order; }
 int ls_amd_basis_fermion_signs(ls_hs_basis const *b) { return BEXT(b)->fermi; }
-/* test hook (no device): sign(g, state) of group element `element` of a projected spinless-fermion basis by the device code's host
+int ls_amd_basis_spin_flip(ls_hs_basis const *b) { return BEXT(b)->spin_flip; }
+/* test hook: how element `element` was compiled (LSK_ELEM_* of lsk.h: 0 network, 1 rotation, 2 reflection, 4-7 lifted ring elements) */
+int ls_amd_test_group_element_kind(ls_hs_basis const *b, int element) {
+    struct ls_amd_basis_ext const *e = BEXT(b);
+    return element < 0 || element >= e->order ? -1 : e->elems[element].kind;
+}
+/* test hook (no device): sign(g, state) of group element `element` of a projected fermionic basis by the device code's host
  * mirror -- closed form for rotations and reflections, or (table != 0) the sign table for every element; 0 on bad arguments */
 int ls_amd_test_fermion_sign(ls_hs_basis const *b, int element, uint64_t state, int table) {
     struct ls_amd_basis_ext const *e = BEXT(b);
@@ -1358,7 +1453,7 @@ ls_hs_operator *ls_hs_create_operator_from_terms(ls_hs_basis const *basis, int n
  * (number_sites, number_up = Hamming weight or -1, spin_inversion, representatives; FFI.chpl:94-105).  The symmetry
  * group is not part of that prefix, so the caller passes the generators it built the basis from (the YAML's
  * `symmetries`), in the convention of ls_hs_create_spin_basis. */
-int ls_amd_adopt_basis(ls_hs_basis const *basis, int number_generators, int const *permutations, int const *sectors) {
+static int adopt_basis(ls_hs_basis const *basis, int spin_flip, int number_generators, int const *permutations, int const *sectors) {
     if (!basis) return set_error("null basis");
     if (reg_get(basis)) return set_error("basis %p is already registered", (void const *)basis);
     ls_hs_basis *tmp;
@@ -1366,10 +1461,15 @@ int ls_amd_adopt_basis(ls_hs_basis const *basis, int number_generators, int cons
         /* spinless-fermion prefix: number_sites, number_particles, particle_type; site permutations with their signs on the modes */
         if (basis->spin_inversion != 0 || basis->number_up != -1) return set_error("spinless-fermion bases have no spin inversion and no number_up");
         tmp = ls_hs_create_spinless_fermion_basis(basis->number_sites, basis->number_particles, number_generators, permutations, sectors);
+    } else if (basis->particle_type == LS_HS_SPINFUL_FERMION && basis->number_up != -1 && (number_generators != 0 || spin_flip != 0)) {
+        /* spinful (N, N_up) prefix: SITE generators, lifted to both species, and the up <-> down flip */
+        if (basis->spin_inversion != 0) return set_error("spinful-fermion bases have no spin inversion (the up <-> down flip is spin_flip)");
+        tmp = ls_hs_create_spinful_fermion_basis(basis->number_sites, basis->number_particles, basis->number_up, spin_flip, number_generators,
+                                                 permutations, sectors);
     } else if (basis->particle_type != LS_HS_SPIN) {
-        /* spinful prefixes: number_sites, number_particles, number_up, particle_type; no symmetries (the lift of site permutations to
-         * both species is not implemented) */
-        if (number_generators != 0 || basis->spin_inversion != 0 || basis->requires_projection)
+        /* other fermionic prefixes: number_sites, number_particles, number_up, particle_type; no symmetries (on the N-only spinful
+         * basis they are not supported: it is a spinless basis on 2 L modes) */
+        if (number_generators != 0 || spin_flip != 0 || basis->spin_inversion != 0 || basis->requires_projection)
             return set_error("fermionic bases with symmetries are not supported");
         tmp = ls_hs_create_basis(basis->particle_type, basis->number_sites, basis->number_particles, basis->number_up);
     } else
@@ -1388,6 +1488,14 @@ int ls_amd_adopt_basis(ls_hs_basis const *basis, int number_generators, int cons
     e->owns_representatives = 0;
     reg_put(basis, e, REG_BASIS);
     return 0;
+}
+int ls_amd_adopt_basis(ls_hs_basis const *basis, int number_generators, int const *permutations, int const *sectors) {
+    return adopt_basis(basis, 0, number_generators, permutations, sectors);
+}
+int ls_amd_adopt_spinful_fermion_basis(ls_hs_basis const *basis, int spin_flip, int number_generators, int const *permutations,
+                                       int const *sectors) {
+    if (basis && basis->particle_type != LS_HS_SPINFUL_FERMION) return set_error("ls_amd_adopt_spinful_fermion_basis: not a spinful-fermion basis");
+    return adopt_basis(basis, spin_flip, number_generators, permutations, sectors);
 }
 /* An operator struct somebody else owns: the term tables are rebuilt from its off_diag_terms / diag_terms
  * (ls_hs_nonbranching_terms, number_words == 1) and kept in the side table. */
@@ -2761,7 +2869,7 @@ static int plan_setup_part(ls_amd_plan *pl, part_state *ps, int part_id, int num
         }
     }
     if (!closed_form && pl->P == 1 && !pl->global_index && (pl->family == FAMILY_DIRECT_PULL || pl->family == FAMILY_DIRECT_PUSH) &&
-        BEXT(b)->product && ps->count > 0) {
+        BEXT(b)->product && !BEXT(b)->fermi && ps->count > 0) {
         /* the spinful product basis in its own order: two closed-form ranks (LSK_INDEX_PRODUCT), verified on the device */
         lsk_index pix = ps->index;
         pix.kind = LSK_INDEX_PRODUCT;
@@ -3062,7 +3170,7 @@ int ls_amd_plan_create(ls_amd_plan **out, ls_hs_operator const *op, ls_amd_dtype
     pl->n_local = my_partition < 0 ? num_partitions : 1;
     if (operator_device(op, &pl->dop) != 0 || basis_device(op->basis, &pl->dbs) != 0) { free(pl); return -1; }
     if (pl->dbs.fermi) {
-        /* projected spinless fermions: the signed K4 exists in the indexed pull kernel of one partition (fused, or resolve + gather) and
+        /* projected fermions: the signed K4 exists in the indexed pull kernel of one partition (fused, or resolve + gather) and
          * nowhere else -- every other path would run without the signs, so it is refused here, before anything launches */
         char const *why = NULL, *ev = getenv("LS_AMD_PULL_VALUES"), *ei = getenv("LS_AMD_PULL_INDEXED"), *em = getenv("LS_AMD_MODE");
         if (my_partition >= 0) why = "one partition per process";
@@ -4258,7 +4366,9 @@ int ls_amd_enumerate_states(ls_hs_basis const *basis, int num_locales, uint64_t 
     uint64_t const *d_binom;
     if (basis_device(basis, &dbs) != 0 || device_binom(&d_binom) != 0) return -1;
     struct ls_amd_basis_ext const *e = BEXT(basis);
-    if (e->product) {
+    if (e->product && e->fermi) { /* projected: the product candidates through the signed representative test */
+        DEV(lsk_fermi_enumerate_product(dbs, e->prod_up, e->prod_dn, d_binom, d_states, count, stream));
+    } else if (e->product) {
         DEV(lsk_enumerate_product(basis->number_sites, e->prod_up, e->prod_dn, d_binom, d_states, count, stream));
     } else {
         int64_t ncand = candidate_count(basis);
@@ -4576,7 +4686,7 @@ void ls_hs_state_index(ls_hs_basis const *basis_c, ptrdiff_t n, uint64_t const *
     ix.reps = e->d_reps_cache;
     ix.binom = d_binom;
     if (b->state_index_is_identity) ix.kind = LSK_INDEX_IDENTITY;
-    if (e->product && e->index_kind != LSK_INDEX_SEARCH) {
+    if (e->product && !e->fermi && e->index_kind != LSK_INDEX_SEARCH) {
         /* the spinful product basis: two closed-form ranks, once the representatives are known to be the whole basis in order */
         ix.prod_sites = b->number_sites; ix.prod_up = e->prod_up; ix.prod_dn = e->prod_dn;
         ix.prod_na = (int64_t)binom(b->number_sites, e->prod_up);

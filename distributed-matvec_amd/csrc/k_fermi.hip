@@ -1,12 +1,17 @@
-// k_fermi.hip -- projected spinless-fermion bases: the K4 of every group element carries the permutation sign of the Fock state
-// (lsk_fermi.hpp).  Enumeration flags, norms, state_info, and the fermionic instantiations of the indexed pull kernel k_pull_t
-// (k_pull_t.hpp) for one-partition plans: fused f64 / c128 and the resolve half of the split matvec, 32- and 64-bit words.  The
-// gather kernels (k_pull_gather, k_pull_gather_blk) need nothing new: the sign is folded into each packet's coefficient.
+// k_fermi.hip -- projected fermionic bases (spinless; spinful with fixed (N_up, N_down) over their 2 L modes): the K4 of every group
+// element carries the permutation sign of the Fock state (lsk_fermi.hpp).  Enumeration flags (the spinful product candidates are in
+// k_fermi_product.hip), norms, state_info, and the fermionic instantiations of the indexed pull kernel k_pull_t (k_pull_t.hpp) for
+// one-partition plans: fused f64 / c128 and the resolve half of the split matvec, 32- and 64-bit words.  The gather kernels
+// (k_pull_gather, k_pull_gather_blk) need nothing new: the sign is folded into each packet's coefficient.
 // A translation unit of its own so that the hot units (scripts/kernel_resources.py) keep their device-function budget.
 #include "k_pull_t.hpp"
 
 extern "C" int lsk_test_fermi_parity(lsk_group_elem e, uint64_t const *tab, uint64_t a, int L, int table) {
     return fermi_parity<uint64_t>(e, tab, a, L, table != 0);
+}
+// host mirror of fermi_apply_elem_w for the LIFT kinds (host_apply_elem, host.c, has the others)
+extern "C" uint64_t lsk_test_fermi_apply_lift(lsk_group_elem e, uint64_t x, int L) {
+    return fermi_apply_lift<uint64_t>(e, x, L, L >= 64 ? ~0ULL : ((1ULL << L) - 1));
 }
 
 // k_enum_flags (k_plan.hip) with the signed test: a candidate is kept when it is its orbit minimum AND its norm does not vanish
@@ -31,7 +36,7 @@ __global__ __launch_bounds__(kBlock) void k_fermi_enum_flags(lsk_basis bs, lsk_g
 extern "C" int lsk_fermi_enum_flags(lsk_basis bs, uint64_t const *d_binom, int64_t n_cand, int64_t n_threads, int chunk, uint64_t *flags,
                                     int64_t *counts, void *stream) {
     if (!bs.fermi || !bs.fsign || bs.spin_inversion != 0 || chunk < 1 || chunk > 64) {
-        snprintf(g_err, sizeof(g_err), "lsk_fermi_enum_flags: not a projected spinless-fermion basis");
+        snprintf(g_err, sizeof(g_err), "lsk_fermi_enum_flags: not a projected fermionic basis");
         return -1;
     }
     if (n_threads <= 0) return 0;
@@ -60,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void k_fermi_state_info(lsk_basis bs, lsk_g
 }
 static int fermi_args_ok(lsk_basis const &bs, char const *who) {
     if (bs.fermi && bs.fsign && bs.spin_inversion == 0 && bs.k4_mode == 0 && bs.proj == LSK_PROJ_FULL) return 0;
-    snprintf(g_err, sizeof(g_err), "%s: not a projected spinless-fermion basis in K4 mode 0", who);
+    snprintf(g_err, sizeof(g_err), "%s: not a projected fermionic basis in K4 mode 0", who);
     return -1;
 }
 extern "C" int lsk_fermi_state_info(lsk_basis bs, int64_t n, uint64_t const *alphas, uint64_t *betas, double *characters, double *norms,

@@ -63,6 +63,12 @@ typedef struct lsk_operator {
 } lsk_operator;
 
 enum { LSK_ELEM_BENES = 0, LSK_ELEM_ROT = 1, LSK_ELEM_REVROT = 2 };
+/* Elements of a projected spinful-fermion basis that are a ring rotation / reflection of the sites lifted to both species (the
+ * state word has 2 h bits: up half = bits 0..h-1, down half = bits h..2h-1): kind = LSK_ELEM_LIFT | flags, k = the site
+ * element's rotate-right amount within h bits.  REV: every half is reversed first (as REVROT); SWAP: the halves are exchanged
+ * afterwards (the up <-> down flip).  Only the fermionic code knows these kinds (fermi_apply_elem_w / fermi_parity, lsk_fermi.hpp;
+ * host_apply_elem, host.c): apply_elem and the spin kernels never see them, and the element keeps its compiled network in `masks`. */
+enum { LSK_ELEM_LIFT = 4, LSK_ELEM_LIFT_REV = 1, LSK_ELEM_LIFT_SWAP = 2 };
 
 typedef struct lsk_group_elem {
     int32_t kind;
@@ -93,7 +99,8 @@ typedef struct lsk_basis {
      *    in its high half (torus_min_d2, lsk_dev.hpp). */
     int k4_mode, reflect;
     int d4_mask;                    /* mode 5 */
-    /* projected spinless-fermion basis: every group element carries the permutation sign of the Fock state (include/ls_hs.h);
+    /* projected fermionic basis (spinless, or spinful over its 2 L modes): every group element carries the permutation sign of the
+     * Fock state (include/ls_hs.h);
      * always K4 mode 0, so the mode-5 row table is never read and its pointer slot holds the sign table instead (the layout of
      * this struct, which every kernel receives by value, stays as it was) */
     int fermi;
@@ -505,15 +512,20 @@ int lsk_scatter(lsk_index ix, int cplx, int64_t n, uint64_t const *betas, void c
                 double const *norms /* NULL, or per-row norms multiplied in (K4 modes 1, 2) */, int *d_err,
                 void *stream);
 
-/* projected spinless-fermion bases (k_fermi.hip): the sign-aware K4 of enumeration, norms, state_info and the pull kernel ----- */
+/* projected fermionic bases (k_fermi.hip): the sign-aware K4 of enumeration, norms, state_info and the pull kernel ----- */
 /* parity of sign(g, a) for element e with sign-table row tab[number_sites] (host mirror of the device code; table != 0 forces the
  * table form for ROT / REVROT elements as well) */
 int lsk_test_fermi_parity(lsk_group_elem e, uint64_t const *tab, uint64_t a, int L, int table);
+/* host mirror of the device code's application of a LSK_ELEM_LIFT element to a word of L = 2 h modes */
+uint64_t lsk_test_fermi_apply_lift(lsk_group_elem e, uint64_t x, int L);
 int lsk_fermi_enum_flags(lsk_basis bs, uint64_t const *d_binom, int64_t n_cand, int64_t n_threads, int chunk, uint64_t *flags,
                          int64_t *counts, void *stream);
 int lsk_fermi_norms(lsk_basis bs, int64_t n, uint64_t const *reps, double *norms, void *stream);
 int lsk_fermi_state_info(lsk_basis bs, int64_t n, uint64_t const *alphas, uint64_t *betas, double *characters, double *norms,
                          void *stream);
+/* enumeration of a projected spinful (N_up, N_down) basis: the candidates are the product set in the order of lsk_enumerate_product,
+ * kept by the signed test of lsk_fermi_enum_flags; bs.number_sites = 2 L */
+int lsk_fermi_enumerate_product(lsk_basis bs, int n_up, int n_dn, uint64_t const *d_binom, uint64_t **d_states, int64_t *count, void *stream);
 /* k_pull_t for bs.fermi: wide = 64-bit words, sink = 0 fused / 1 resolve (the value table is refused) */
 int lsk_fermi_pull(lsk_operator op, lsk_basis bs, int wide, int cplx, int sink, int64_t row0, int64_t row1, uint64_t const *reps,
                    double const *norms_local, lsk_pullidx ix, uint64_t const *reps_global, int64_t n_global, void const *xsrc, int halo,

@@ -1,4 +1,5 @@
-// lsk_fermi.hpp -- K4 of projected spinless-fermion bases: the permutation sign of a Fock state (convention: include/ls_hs.h).
+// lsk_fermi.hpp -- K4 of projected fermionic bases (spinless, and spinful over their 2 L modes): the permutation sign of a Fock
+// state (convention: include/ls_hs.h).
 //
 // An element g with (g.a)[i] = a[p_i] acts as U_g c+_j U_g+ = c+_{p^-1(j)}, so U_g |a> = sign(g, a) |g.a> with
 // sign = (-1)^(number of occupied pairs j < j' with p^-1(j) > p^-1(j')).  U is a representation (U_g U_h = U_gh), so
@@ -7,7 +8,10 @@
 //     still yields the stabiliser sum  sum_{s in Stab(a)} chi(s) sign(s, a)  once multiplied by conj(chi(g0) sign(g0, a));
 //   - that sum may vanish in any sector (4-site ring, N = 2: T^2 fixes 0101 with sign -1), so the fermionic K4 never skips the
 //     norm: these bases always run K4 mode 0.
-// The sign is written over MODES (the bits of the state word); a spinful basis would only lift its site permutations on the host.
+// The sign is written over MODES (the bits of the state word).  A spinful basis lifts its site permutations to both species on the
+// host (p + p over the 2 L modes, and the half swap for the up <-> down flip): nothing here changes for them, but a lifted ring
+// rotation / reflection has a closed form per half (the LSK_ELEM_LIFT kinds of lsk.h) instead of a network and one table load per
+// particle.
 // Everything here is a template or __host__ __device__: k_fermi.hip uses it, k_pull_t.hpp compiles it into the fermionic
 // k_pull_t instantiations, and lsk_test_fermi_parity runs the same code on the host.
 #pragma once
@@ -26,6 +30,10 @@ template <typename W> __host__ __device__ __forceinline__ int fermi_ctz(W v) {
 //     the reversed word;
 //   BENES (any permutation): the GF(2) quadratic form  parity(a & XOR_{i in occ(a)} tab[i]),  tab[i] = the modes j < i that
 //     the permutation puts above i -- one table load per particle.
+//   LIFT kinds (word of 2 h modes, h = L / 2; u = up half, d = down half): the site element acts inside each half, and no pair
+//     with one mode in each half changes its order, so the sign is the product of the two halves' ROT / REVROT signs over h
+//     modes.  The reversed word is not formed: its low k bits are the top k bits of the half.  With SWAP every (up, down) pair
+//     changes its order as well: (-1)^(N_up N_down).
 // table != 0 takes the table form for every kind (the host mirror's check of the closed forms).
 template <typename W>
 __host__ __device__ __forceinline__ int fermi_parity(lsk_group_elem const &e, uint64_t const *__restrict__ tab, W a, int L, bool table) {
@@ -33,6 +41,19 @@ __host__ __device__ __forceinline__ int fermi_parity(lsk_group_elem const &e, ui
         W x = 0;
         for (W m = a; m != 0; m &= m - 1) x ^= (W)tab[fermi_ctz<W>(m)];
         return fermi_popc<W>(a & x) & 1;
+    }
+    if (e.kind & LSK_ELEM_LIFT) {
+        const int h = L >> 1, k = e.k; // 0 <= k < h, 2 h <= 8 sizeof(W)
+        const W hm = (W)(((W)1 << h) - 1);
+        const W u = a & hm, d = (W)(a >> h);
+        const bool rev = (e.kind & LSK_ELEM_LIFT_REV) != 0;
+        const W mk = rev ? (W)(hm & ~(hm >> k)) : (W)(((W)1 << k) - 1); // the k modes that the rotation carries past the others
+        const int nu = fermi_popc<W>(u), nd = fermi_popc<W>(d);
+        const int au = fermi_popc<W>(u & mk), ad = fermi_popc<W>(d & mk);
+        int par = (au & (nu - au)) ^ (ad & (nd - ad));
+        if (rev) par ^= (nu >> 1) ^ (nd >> 1); // (-1)^(n (n - 1) / 2) per half
+        if (e.kind & LSK_ELEM_LIFT_SWAP) par ^= nu & nd;
+        return par & 1;
     }
     int par = 0;
     W w = a;
@@ -50,7 +71,29 @@ __host__ __device__ __forceinline__ int fermi_parity(lsk_group_elem const &e, ui
     return par ^ (lo & hi & 1);
 }
 
+// apply_elem_w with the LIFT kinds: rotate / reverse both h-bit halves in registers, optionally exchange them.  Reversing the
+// whole 2 h-bit word reverses each half AND exchanges them, so REV costs one bit reversal and REV + SWAP no exchange at all.
+template <typename W> __host__ __device__ __forceinline__ W fermi_apply_lift(lsk_group_elem const &e, W x, int L, W mask) {
+    const int h = L >> 1, k = e.k;
+    bool swap = (e.kind & LSK_ELEM_LIFT_SWAP) != 0;
+    if (e.kind & LSK_ELEM_LIFT_REV) {
+        if (sizeof(W) == 4) x = (W)(__builtin_bitreverse32((uint32_t)x) >> (32 - L));
+        else x = (W)(__builtin_bitreverse64((uint64_t)x) >> (64 - L));
+        swap = !swap;
+    }
+    if (k) {
+        const W hm = (W)(((W)1 << h) - 1);
+        const W m1 = (W)((hm >> k) | ((W)(hm >> k) << h)); // where x >> k stays inside its half
+        x = (W)(((x >> k) & m1) | ((W)(x << (h - k)) & mask & ~m1));
+    }
+    if (swap) x = (W)(((x >> h) | (W)(x << h)) & mask);
+    return x;
+}
 #ifdef __HIPCC__
+template <typename W> __device__ __forceinline__ W fermi_apply_elem_w(lsk_group_elem const &e, W x, int L, W mask) {
+    if (e.kind & LSK_ELEM_LIFT) return fermi_apply_lift<W>(e, x, L, mask);
+    return apply_elem_w<W>(e, x, L, mask);
+}
 // state_info_w (lsk_dev.hpp) with the signed characters chi(g) sign(g, a): orbit minimum, conj(chi(g0) sign(g0, a)) of the first
 // minimising element, stabiliser sum.  No spin inversion (fermionic bases have none).  PM1: every character is +-1.
 template <typename W, bool PM1>
@@ -63,7 +106,7 @@ __device__ __forceinline__ void fermi_state_info_w(lsk_basis const &bs, lsk_grou
     const W mask = (W)bs.site_mask;
     for (int g = 0; g < bs.n_elems; ++g) {
         lsk_group_elem const &e = elems[g];
-        const W t = apply_elem_w<W>(e, a, L, mask);
+        const W t = fermi_apply_elem_w<W>(e, a, L, mask);
         const int par = fermi_parity<W>(e, bs.fsign + (size_t)g * L, a, L, false);
         const bool less = t < best, eq = t == best;
         if (PM1) {
@@ -92,7 +135,7 @@ __device__ __forceinline__ bool fermi_is_representative(lsk_basis const &bs, lsk
     double st = 0.0;
     for (int g = 0; g < bs.n_elems; ++g) {
         lsk_group_elem const &e = elems[g];
-        const uint64_t t = apply_elem(e, a, bs.number_sites, bs.site_mask);
+        const uint64_t t = fermi_apply_elem_w<uint64_t>(e, a, bs.number_sites, bs.site_mask);
         if (t < a) return false;
         if (t == a) st += fermi_parity<uint64_t>(e, bs.fsign + (size_t)g * bs.number_sites, a, bs.number_sites, false) ? -e.ch_re : e.ch_re;
     }

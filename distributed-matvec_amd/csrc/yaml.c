@@ -685,19 +685,31 @@ static int symmetries_from(ynode const *b, long L, int *ng_out, int **perms_out,
     return 0;
 }
 /* particle: spinless-fermion | spinful-fermion -- number_sites, number_particles (null: unrestricted), number_up (spinful; null:
- * only number_particles fixed); symmetries for spinless fermions only (permutations of the number_sites modes) */
+ * only number_particles fixed); symmetries for spinless fermions (permutations of the number_sites modes) and for spinful ones with
+ * number_up (permutations of the sites, lifted to both species; spin_flip: +-1 adds the up <-> down flip).  config.parse_basis is
+ * the Python mirror: same checks, same messages. */
 static ls_hs_basis *fermion_basis_from(ynode const *b, char const *particle) {
     int const spinful = strcmp(particle, "spinful-fermion") == 0;
     if (y_get(b, "number_spins")) {
         ls_amd_internal_error("number_spins is a key of spin-1/2 bases, not of particle '%s' (use number_sites)", particle); return NULL;
     }
     static char const *const unsupported[] = {"hamming_weight", "spin_inversion", "symmetries"};
+    int const lifted = spinful && !y_is_null(y_get(b, "number_up"));
     for (int k = 0; k < 3; ++k)
-        if (!y_is_unset(y_get(b, unsupported[k])) && (spinful || k != 2)) {
-            ls_amd_internal_error("%s is not supported for particle '%s'", unsupported[k], particle);
+        if (!y_is_unset(y_get(b, unsupported[k])) && !(k == 2 && (!spinful || lifted))) {
+            ls_amd_internal_error("%s is not supported for particle '%s'%s", unsupported[k], particle, k == 2 ? " without number_up" : "");
             return NULL;
         }
-    long L, n = -1, nup = -1;
+    long L, n = -1, nup = -1, flip = 0;
+    if (!y_is_unset(y_get(b, "spin_flip"))) {
+        if (!lifted) {
+            ls_amd_internal_error("spin_flip is a key of spinful-fermion bases with number_up, not of particle '%s'%s", particle,
+                                  spinful ? " without number_up" : "");
+            return NULL;
+        }
+        if (y_int(y_get(b, "spin_flip"), "basis.spin_flip", &flip) != 0) return NULL;
+        if (flip != 1 && flip != -1) { ls_amd_internal_error("spin_flip must be 1 or -1"); return NULL; }
+    }
     if (!y_get(b, "number_sites")) { ls_amd_internal_error("particle '%s' needs number_sites", particle); return NULL; }
     if (y_int(y_get(b, "number_sites"), "basis.number_sites", &L) != 0) return NULL;
     if (!y_is_null(y_get(b, "number_particles")) && y_int(y_get(b, "number_particles"), "basis.number_particles", &n) != 0) return NULL;
@@ -706,12 +718,20 @@ static ls_hs_basis *fermion_basis_from(ynode const *b, char const *particle) {
         if (y_int(y_get(b, "number_up"), "basis.number_up", &nup) != 0) return NULL;
         if (n < 0) { ls_amd_internal_error("a fixed number_up needs a fixed number_particles"); return NULL; }
     }
-    if (spinful) return ls_hs_create_basis(LS_HS_SPINFUL_FERMION, (int)L, (int)n, (int)nup);
+    if (spinful && !lifted) return ls_hs_create_basis(LS_HS_SPINFUL_FERMION, (int)L, (int)n, (int)nup);
+    if (spinful && (L < 1 || L > 32)) { ls_amd_internal_error("spinful fermions: number_sites must be in [1, 32] (2 number_sites modes in one word)"); return NULL; }
     if (L < 1 || L > 64) { ls_amd_internal_error("spinless fermions: number_sites must be in [1, 64]"); return NULL; }
     int ng = 0;
     int *perms = NULL, *sectors = NULL;
     if (symmetries_from(b, L, &ng, &perms, &sectors) != 0) return NULL;
-    ls_hs_basis *basis = ls_hs_create_spinless_fermion_basis((int)L, (int)n, ng, perms, sectors);
+    if (flip != 0 && 2 * nup != n) {
+        free(perms); free(sectors);
+        ls_amd_internal_error("spin_flip requires number_up == number_particles - number_up");
+        return NULL;
+    }
+    /* (without generators and flip the spinful creator returns the unprojected product basis of ls_hs_create_basis) */
+    ls_hs_basis *basis = spinful ? ls_hs_create_spinful_fermion_basis((int)L, (int)n, (int)nup, (int)flip, ng, perms, sectors)
+                                 : ls_hs_create_spinless_fermion_basis((int)L, (int)n, ng, perms, sectors);
     free(perms); free(sectors);
     return basis;
 }

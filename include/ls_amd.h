@@ -131,7 +131,10 @@ int ls_amd_locale_idx_of(uint64_t basis_state, int num_locales);
  *                          `representatives` from the prefix; the symmetry generators are not part of the prefix and are
  *                          passed in the convention of ls_hs_create_spin_basis (0 generators for an unsymmetrised basis);
  *                          spinless-fermion prefixes (particle_type, number_sites, number_particles) take generators too, with
- *                          the permutation signs of ls_hs_create_spinless_fermion_basis; spinful ones take none
+ *                          the permutation signs of ls_hs_create_spinless_fermion_basis; spinful prefixes with a fixed
+ *                          number_up take SITE generators (ls_hs_create_spinful_fermion_basis), with number_up == -1 none
+ *   ls_amd_adopt_spinful_fermion_basis  the same for a spinful prefix, with the up <-> down flip (spin_flip = 0, +1, -1),
+ *                          which is not part of the prefix either
  *   ls_amd_adopt_operator  rebuilds the term / flip-mask-group tables from off_diag_terms / diag_terms
  *                          (ls_hs_nonbranching_terms with number_bits <= 64); its basis must be known
  *   ls_amd_release         forgets an adopted object and frees its tables (the foreign struct is left alone)
@@ -139,6 +142,8 @@ int ls_amd_locale_idx_of(uint64_t basis_state, int num_locales);
  * pointers.  An unknown pointer halts with a message naming these functions.
  */
 int ls_amd_adopt_basis(ls_hs_basis const *basis, int number_generators, int const *permutations, int const *sectors);
+int ls_amd_adopt_spinful_fermion_basis(ls_hs_basis const *basis, int spin_flip, int number_generators, int const *permutations,
+                                       int const *sectors);
 int ls_amd_adopt_operator(ls_hs_operator const *op);
 void ls_amd_release(void const *object);
 
@@ -424,11 +429,17 @@ int ls_amd_hashed_to_block(int64_t n, uint8_t const *d_masks, int num_locales, i
 
 /* test hooks: evaluate compiled host-side tables on the CPU (no device work) ------------------ */
 int ls_amd_basis_group_order(ls_hs_basis const *basis);
-/* 1 when the basis is a projected spinless-fermion basis, i.e. its group elements carry permutation signs (include/ls_hs.h) */
+/* 1 when the basis is a projected fermionic basis (spinless, or spinful with fixed number_up), i.e.
+ * its group elements carry permutation signs (include/ls_hs.h) */
 int ls_amd_basis_fermion_signs(ls_hs_basis const *basis);
 /* test hook, no device: sign(g, state) = +-1 of group element `element` of such a basis, by the closed forms of rotations and
  * reflections or (table != 0) by the sign table for every element; 0 on bad arguments */
 int ls_amd_test_fermion_sign(ls_hs_basis const *basis, int element, uint64_t state, int table);
+/* the up <-> down flip character of a spinful-fermion basis (ls_hs_create_spinful_fermion_basis): 0 none, +1, -1 */
+int ls_amd_basis_spin_flip(ls_hs_basis const *basis);
+/* test hook: the compiled kind of a group element -- 0 network, 1 rotation, 2 reflection, 4 | 1 (reflection) | 2 (half swap) for the
+ * ring elements of a spinful basis lifted to both species, -1 out of range */
+int ls_amd_test_group_element_kind(ls_hs_basis const *basis, int element);
 uint64_t ls_amd_basis_apply_group_element(ls_hs_basis const *basis, int element, uint64_t state);
 int ls_amd_basis_group_character(ls_hs_basis const *basis, int element, double *re, double *im);
 

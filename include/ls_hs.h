@@ -102,8 +102,8 @@ void ls_hs_exit(void);  /* FFI.chpl:129 */
 ls_hs_basis *ls_hs_create_spin_basis(int number_sites, int hamming_weight, int spin_inversion,
                                      int number_generators, int const *permutations,
                                      int const *sectors);
-/* FFI.chpl:143-144 (declared there, commented out).  Any particle type, no symmetries (spinless fermions with symmetries:
- * ls_hs_create_spinless_fermion_basis below):
+/* FFI.chpl:143-144 (declared there, commented out).  Any particle type, no symmetries (fermions with symmetries:
+ * ls_hs_create_spinless_fermion_basis and ls_hs_create_spinful_fermion_basis below):
  *   LS_HS_SPIN               number_up = Hamming weight or -1 (number_particles ignored)
  *   LS_HS_SPINLESS_FERMION   L <= 64 modes, mode i = bit i; number_particles fixed or -1; number_up must be -1
  *   LS_HS_SPINFUL_FERMION    L <= 32 sites, 2 L modes: mode (i, up) = bit i, mode (i, down) = bit i + L
@@ -132,6 +132,21 @@ ls_hs_basis *ls_hs_create_basis(ls_hs_particle_type particle_type, int number_si
  * enumerated and answer ls_hs_state_info, but ls_amd_plan_create refuses them ("no static index table"). */
 ls_hs_basis *ls_hs_create_spinless_fermion_basis(int number_sites, int number_particles, int number_generators, int const *permutations,
                                                  int const *sectors);
+/* Spinful fermions with site permutations and the up <-> down flip (not in the reference's ABI), on the (N, N_up) product basis
+ * only: number_sites <= 32, number_up fixed (not -1), `permutations` = number_generators x number_sites SITE permutations in the
+ * convention of ls_hs_create_spinless_fermion_basis, spin_flip = 0, or +1 / -1 for the flip with that character (it needs
+ * number_up == number_particles - number_up).  Modes are ordered as everywhere: (i, up) = bit i, (i, down) = bit i + L.  A site
+ * permutation p acts on the 2 L modes as p + p (both species alike), the flip as the half swap i <-> i + L, and every element of the
+ * group they generate carries the sign of ls_hs_create_spinless_fermion_basis over the 2 L modes (the inversion count of the
+ * occupied modes): U_g |a> = sign(g, a) |g.a> is a representation, p + p produces no sign between the species, and the flip alone
+ * gives (-1)^(N_up N_down).  Closure, characters, sector compatibility and their errors are those of the mode group; norms,
+ * enumeration (candidates: the product set in ascending order), ls_hs_state_info and the restrictions on plans (one partition, the
+ * indexed pull kernel, a Hermitian operator, at most 60 modes = 30 sites) are those of the spinless projected bases.  The struct
+ * prefix keeps spin_inversion == 0 (that field is the bit complement of spin bases); ls_amd_basis_spin_flip returns the flip.
+ * Without generators and flip the result is the basis of ls_hs_create_basis.  Symmetries on the spinful basis with number_up
+ * unset are not supported: that basis is a spinless one on 2 L modes. */
+ls_hs_basis *ls_hs_create_spinful_fermion_basis(int number_sites, int number_particles, int number_up, int spin_flip, int number_generators,
+                                                int const *permutations, int const *sectors);
 ls_hs_basis *ls_hs_clone_basis(ls_hs_basis const *basis);       /* FFI.chpl:141 */
 void ls_hs_destroy_basis(ls_hs_basis *basis);                   /* FFI.chpl:142 */
 
@@ -155,7 +170,7 @@ typedef struct ls_hs_yaml_config {
 /* /root/reference/src/FFI.chpl:208-209.  The YAML subset of the YAML files under /root/reference/data (basis: number_spins, hamming_weight,
  * spin_inversion, symmetries; hamiltonian / observables: terms of `expression` + `sites`; anchors and aliases, block and
  * flow collections), and fermionic bases (particle: spinless-fermion | spinful-fermion, number_sites, number_particles,
- * number_up, and symmetries for spinless fermions; expressions of c+ / c / n, see ls_hs_create_basis).  NULL on failure, with the reason in ls_amd_last_error(). */
+ * number_up, symmetries for spinless fermions, symmetries and spin_flip for spinful ones with number_up; expressions of c+ / c / n, see ls_hs_create_basis).  NULL on failure, with the reason in ls_amd_last_error(). */
 ls_hs_yaml_config *ls_hs_load_yaml_config(char const *filename);
 void ls_hs_destroy_yaml_config(ls_hs_yaml_config *config);
 /* the same from a NUL-terminated YAML text in memory (not in the reference's ABI) */
