@@ -25,7 +25,7 @@ __all__ = [
     "Basis", "Operator", "LsAmdError", "loadConfigFromYaml", "loadConfigFromDict", "enumerateStates",
     "arrFromBlockToHashed", "arrFromHashedToBlock", "matrixVectorProduct", "localMatrixVector",
     "localeIdxOf", "hash64_01", "MatvecPlan", "ReplicatedPlan", "build_library", "fillRandom",
-    "Communicator", "DistMatvec", "ReplMatvec",
+    "Communicator", "DistMatvec", "ReplMatvec", "block_axpby_dots",
 ]
 
 
@@ -359,6 +359,38 @@ def arrFromHashedToBlock(parts, masks):
     return out
 
 
+def _dots_ptr(dots, K, who):
+    """device pointer of the 2K float64 dots of a Chebyshev step (None: NULL)"""
+    if dots is None:
+        return None
+    torch = _torch()
+    if (not isinstance(dots, torch.Tensor) or dots.dtype != torch.float64 or dots.device.type != "cuda" or not dots.is_contiguous()
+            or dots.numel() != 2 * K):
+        raise _lib.LsAmdError(f"{who}: dots must be a contiguous float64 device tensor of 2K = {2 * K} elements")
+    return C.c_void_p(dots.data_ptr())
+
+
+def block_axpby_dots(w, x, y, alpha, beta, gamma, dots=None):
+    """Y <- alpha W + beta X + gamma Y on (N, K) device tensors of one dtype (float64 or complex128), any nested strides, and the two
+    dots of matvec_block_axpby (ls_amd_block_axpby_dots): the epilogue pass of the Chebyshev step on its own, no plan.  gamma == 0:
+    y is not read."""
+    torch = _torch()
+    for name, t in (("w", w), ("x", x), ("y", y)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise _lib.LsAmdError(f"block_axpby_dots: {name} must be a 2-D (N, K) tensor")
+        if t.dtype != x.dtype or t.dtype not in (torch.float64, torch.complex128):
+            raise _lib.LsAmdError(f"block_axpby_dots: {name} is {t.dtype}; w, x and y must all be float64 or all complex128")
+        if t.device.type != "cuda":
+            raise _lib.LsAmdError(f"block_axpby_dots: {name} must be a device tensor")
+    if tuple(w.shape) != tuple(x.shape) or tuple(y.shape) != tuple(x.shape):
+        raise _lib.LsAmdError(f"block_axpby_dots: w {tuple(w.shape)}, x {tuple(x.shape)} and y {tuple(y.shape)} must have one shape")
+    n, K = int(x.shape[0]), int(x.shape[1])
+    _lib.check(_lib.load().ls_amd_block_axpby_dots(int(x.dtype == torch.complex128), n, K, C.c_void_p(w.data_ptr()), w.stride(0), w.stride(1),
+                                                   C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), C.c_void_p(y.data_ptr()), y.stride(0),
+                                                   y.stride(1), float(alpha), float(beta), float(gamma),
+                                                   _dots_ptr(dots, K, "block_axpby_dots"), _stream_ptr()))
+
+
 class MatvecPlan:
     """ls_amd_plan: binds an Operator to a partition layout (include/ls_amd.h)."""
 
@@ -473,6 +505,39 @@ class MatvecPlan:
     def block_kernel(self, K: int) -> str:
         """path a block of K columns takes on this plan: "k_direct_blk", "k_pull_gather_blk" or "columns" """
         name = _lib.load().ls_amd_plan_block_kernel_name(self.h, int(K))
+        if name is None:
+            _lib.check(-1)
+        return name.decode()
+
+    def matvec_block_axpby(self, x, y, alpha, beta, gamma, dots=None, check: bool = True):
+        """Y[:, k] <- alpha (H X)[:, k] + beta X[:, k] + gamma Y[:, k] for the K columns of the (N, K) device tensors x and y
+        (ls_amd_matvec_block_axpby; alpha, beta, gamma real): the Chebyshev / Lanczos step.  dots: None, or a contiguous float64
+        device tensor of 2K elements, assigned [k] = <X_k|X_k>, [K + k] = Re <X_k|Y_k> with the new Y.  gamma == 0: y is not read.
+        Tensors, strides and LS_AMD_BLOCK as matvec_block; axpby_kernel(K) names the path."""
+        torch = _torch()
+        if self.P != 1 or self.me >= 0:
+            raise _lib.LsAmdError(f"matvec_block_axpby: one-partition plans only (this plan has P = {self.P}, my_partition = {self.me})")
+        want = torch.complex128 if self.cplx else torch.float64
+        for name, t in (("x", x), ("y", y)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise _lib.LsAmdError(f"matvec_block_axpby: {name} must be a 2-D (N, K) tensor")
+            if t.dtype != want:
+                raise _lib.LsAmdError(f"matvec_block_axpby: {name} is {t.dtype}, the plan computes in {want}")
+            if t.device.type != "cuda":
+                raise _lib.LsAmdError(f"matvec_block_axpby: {name} must be a device tensor")
+        n = self.reps[0].numel()
+        if tuple(x.shape) != tuple(y.shape) or x.shape[0] != n:
+            raise _lib.LsAmdError(f"matvec_block_axpby: x {tuple(x.shape)} and y {tuple(y.shape)} must both be ({n}, K)")
+        K = int(x.shape[1])
+        _lib.check(_lib.load().ls_amd_matvec_block_axpby(self.h, K, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
+                                                         C.c_void_p(y.data_ptr()), y.stride(0), y.stride(1), float(alpha), float(beta),
+                                                         float(gamma), _dots_ptr(dots, K, "matvec_block_axpby"), _stream_ptr()))
+        if check:
+            self.check()
+
+    def axpby_kernel(self, K: int) -> str:
+        """path matvec_block_axpby takes for K columns on this plan: "k_direct_cheb", "k_pull_gather_cheb" or "epilogue" """
+        name = _lib.load().ls_amd_plan_axpby_kernel_name(self.h, int(K))
         if name is None:
             _lib.check(-1)
         return name.decode()

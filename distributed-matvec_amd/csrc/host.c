@@ -4250,6 +4250,25 @@ static int block_pbuf(ls_amd_plan *pl) {
     }
 }
 
+/* the tile map k_direct_blk / k_direct_cheb walk: the plan's own, or -- chain and pair plans tile by 512 / 1024 rows -- a 256-row
+ * map of the block path's own, made on first use */
+static int block_tilemap(ls_amd_plan *pl, lsk_tilemap *tm) {
+    *tm = pl->tilemap;
+    if (!(pl->has_chain || pl->has_pairs)) return 0;
+    if (!pl->d_blk_tilemap) {
+        uint64_t *flat = NULL;
+        int64_t slots = 0;
+        if (tilemap_host(pl->parts[0].count, 256, 0, &flat, &slots) < 0) return -1;
+        int const up = upload(&pl->d_blk_tilemap, flat, sizeof(uint64_t) * (size_t)(8 * slots > 0 ? 8 * slots : 1));
+        free(flat);
+        if (up) return -1;
+        pl->blk_tilemap.entries = (uint64_t const *)pl->d_blk_tilemap;
+        pl->blk_tilemap.slots_per_xcd = slots;
+    }
+    *tm = pl->blk_tilemap;
+    return 0;
+}
+
 int ls_amd_matvec_block(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col,
                         void *stream) {
     if (!pl) return set_error("ls_amd_matvec_block: plan is NULL");
@@ -4283,20 +4302,8 @@ int ls_amd_matvec_block(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, 
     part_state *ps = &pl->parts[0];
     ls_amd_internal_count_matvec(pl);
     if (path == BLK_DIRECT) {
-        lsk_tilemap tm = pl->tilemap;
-        if (pl->has_chain || pl->has_pairs) { /* those tile by 512 / 1024 rows: k_direct_blk walks 256-row tiles of its own map */
-            if (!pl->d_blk_tilemap) {
-                uint64_t *flat = NULL;
-                int64_t slots = 0;
-                if (tilemap_host(n, 256, 0, &flat, &slots) < 0) return -1;
-                int const up = upload(&pl->d_blk_tilemap, flat, sizeof(uint64_t) * (size_t)(8 * slots > 0 ? 8 * slots : 1));
-                free(flat);
-                if (up) return -1;
-                pl->blk_tilemap.entries = (uint64_t const *)pl->d_blk_tilemap;
-                pl->blk_tilemap.slots_per_xcd = slots;
-            }
-            tm = pl->blk_tilemap;
-        }
+        lsk_tilemap tm;
+        if (block_tilemap(pl, &tm) != 0) return -1;
         int const st = stage_begin(pl, ST_ROWS, stream);
         int const slot = timing_begin(pl, stream);
         /* (a non-Hermitian operator's partners outside the basis go to the word nobody reads, as in lsk_direct) */
@@ -4331,6 +4338,148 @@ int ls_amd_matvec_block(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, 
         st = stage_begin(pl, ST_ROWS, stream);
         DEV(lsk_pull_gather_blk(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, K, d_x, x_row, x_col, d_y, y_row, y_col,
                                 stream));
+        stage_end(pl, st, stream);
+    }
+    timing_end(pl, slot, stream);
+    return 0;
+}
+
+/* ============================================================================================ */
+/* Chebyshev step (ls_amd_matvec_block_axpby): Y <- alpha H X + beta X + gamma Y and two dots    */
+/* ============================================================================================ */
+static char const *const g_axpby_names[3] = { "epilogue", "k_direct_cheb", "k_pull_gather_cheb" };
+char const *ls_amd_plan_axpby_kernel_name(ls_amd_plan const *pl, int K) {
+    if (!pl) { set_error("ls_amd_plan_axpby_kernel_name: plan is NULL"); return NULL; }
+    if (K < 1 || K > 64) { set_error("ls_amd_plan_axpby_kernel_name: K = %d is outside [1, 64]", K); return NULL; }
+    return g_axpby_names[block_path(pl, K)];
+}
+
+/* no two (i, k) on one element: non-negative strides, one of the two nested in the other (the rule of ls_amd_matvec_block) */
+static int axpby_strides(char const *who, int64_t n, int K, int64_t r, int64_t c, char const *name) {
+    int ok = r >= 0 && c >= 0;
+    if (ok && K > 1 && n > 1) ok = (c >= 1 && r >= c * K) || (r >= 1 && c >= r * n);
+    else if (ok && K > 1) ok = c >= 1;
+    else if (ok && n > 1) ok = r >= 1;
+    if (!ok)
+        return set_error("%s: strides (row %lld, column %lld) of %s make two elements of the %lld x %d block share "
+                         "storage (need non-negative strides with row >= K * column, or column >= N * row)", who, (long long)r,
+                         (long long)c, name, (long long)n, K);
+    return 0;
+}
+static int axpby_overlap(size_t w, int64_t n, int K, void const *a, int64_t ar, int64_t ac, void const *b, int64_t br, int64_t bc) {
+    uintptr_t const a0 = (uintptr_t)a, a1 = a0 + w * (size_t)((n - 1) * ar + (int64_t)(K - 1) * ac + 1);
+    uintptr_t const b0 = (uintptr_t)b, b1 = b0 + w * (size_t)((n - 1) * br + (int64_t)(K - 1) * bc + 1);
+    return a0 < b1 && b0 < a1;
+}
+
+int ls_amd_block_axpby_dots(int cplx, int64_t n, int K, void const *d_w, int64_t w_row, int64_t w_col, void const *d_x, int64_t x_row,
+                            int64_t x_col, void *d_y, int64_t y_row, int64_t y_col, double alpha, double beta, double gamma,
+                            double *d_dots, void *stream) {
+    char const *const who = "ls_amd_block_axpby_dots";
+    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
+    if (n < 0) return set_error("%s: n = %lld is negative", who, (long long)n);
+    if (n == 0) {
+        if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+        return 0;
+    }
+    if (!d_w || !d_x || !d_y) return set_error("%s: W, X or Y is NULL", who);
+    if (K == 1) { w_col = 0; x_col = 0; y_col = 0; }
+    if (axpby_strides(who, n, K, w_row, w_col, "W") != 0 || axpby_strides(who, n, K, x_row, x_col, "X") != 0 ||
+        axpby_strides(who, n, K, y_row, y_col, "Y") != 0)
+        return -1;
+    size_t const w = cplx ? 16 : 8;
+    if (axpby_overlap(w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
+    if (axpby_overlap(w, n, K, d_w, w_row, w_col, d_y, y_row, y_col)) return set_error("%s: W and Y overlap", who);
+    if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+    DEV(lsk_axpby_dots(cplx != 0, n, K, d_w, w_row, w_col, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta, gamma, d_dots,
+                       d_dots ? d_dots + K : NULL, stream));
+    return 0;
+}
+
+/* the path of every plan without a block kernel (and of K = 1 under `auto`): column k through ls_amd_matvec into the plan's
+ * one-column scratch (a strided column of X is gathered into the other scratch column first), then k_axpby_dots on that column */
+static int axpby_columns(ls_amd_plan *pl, int K, char const *x, int64_t xr, int64_t xc, char *y, int64_t yr, int64_t yc, double alpha,
+                         double beta, double gamma, double *d_dots, void *stream) {
+    int64_t const n = pl->parts[0].count;
+    size_t const w = pl->cplx ? 16 : 8;
+    if (!pl->d_blk_cols && lsk_malloc(&pl->d_blk_cols, 2 * w * (size_t)n) != 0) return dev_error();
+    char *const col_x = (char *)pl->d_blk_cols, *const col_w = col_x + w * (size_t)n;
+    for (int k = 0; k < K; ++k) {
+        void const *xk = x + (size_t)k * (size_t)xc * w;
+        void const *xin = xk;
+        void *wout = col_w;
+        if (xr != 1) {
+            DEV(lsk_copy_strided(n, (int)w, xk, xr, col_x, 1, stream));
+            xin = col_x;
+        }
+        DEV(lsk_memset_async(col_w, 0, w * (size_t)n, stream));
+        if (ls_amd_matvec(pl, &xin, &wout, stream) != 0) return -1;
+        DEV(lsk_axpby_dots(pl->cplx, n, 1, col_w, 1, 0, xk, xr, 0, y + (size_t)k * (size_t)yc * w, yr, 0, alpha, beta, gamma,
+                           d_dots ? d_dots + k : NULL, d_dots ? d_dots + K + k : NULL, stream));
+    }
+    return 0;
+}
+
+int ls_amd_matvec_block_axpby(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row,
+                              int64_t y_col, double alpha, double beta, double gamma, double *d_dots, void *stream) {
+    char const *const who = "ls_amd_matvec_block_axpby";
+    if (!pl) return set_error("%s: plan is NULL", who);
+    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
+    if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1)
+        return set_error("%s: one-partition plans only (this plan has P = %d, my_partition = %d)", who, pl->P, pl->me);
+    int64_t const n = pl->parts[0].count;
+    if (n <= 0) {
+        if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+        return 0;
+    }
+    if (!d_x || !d_y) return set_error("%s: X or Y is NULL", who);
+    if (K == 1) { x_col = 0; y_col = 0; }
+    if (axpby_strides(who, n, K, x_row, x_col, "X") != 0 || axpby_strides(who, n, K, y_row, y_col, "Y") != 0) return -1;
+    size_t const w = pl->cplx ? 16 : 8;
+    if (axpby_overlap(w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
+    if (ls_amd_internal_check_y(pl, d_y) != 0) return -1;
+    if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+    int const path = block_path(pl, K);
+    if (path == BLK_COLUMNS)
+        return axpby_columns(pl, K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col, alpha, beta, gamma, d_dots, stream);
+    part_state *ps = &pl->parts[0];
+    ls_amd_internal_count_matvec(pl);
+    if (path == BLK_DIRECT) {
+        lsk_tilemap tm;
+        if (block_tilemap(pl, &tm) != 0) return -1;
+        int const st = stage_begin(pl, ST_ROWS, stream);
+        int const slot = timing_begin(pl, stream);
+        DEV(lsk_direct_cheb(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, K, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta,
+                            gamma, d_dots, OEXT(pl->op)->is_hermitian ? pl->d_err : pl->d_err + 1, stream));
+        timing_end(pl, slot, stream);
+        stage_end(pl, st, stream);
+        return 0;
+    }
+    /* projected, indexed: slot-cache rows first, the others resolved chunk by chunk, exactly as ls_amd_matvec_block; every gather
+     * launch adds its rows' share to the dots */
+    lsk_pullidx ix;
+    memset(&ix, 0, sizeof(ix));
+    ix.tab = pl->gtab->tab;
+    int64_t const cached = pl->slot_cache && pl->slot_cache_valid ? pl->split_rows : 0;
+    int const slot = timing_begin(pl, stream);
+    if (cached > 0) {
+        int const st = stage_begin(pl, ST_ROWS, stream);
+        DEV(lsk_pull_gather_cheb(pl->dop, pl->dbs, pl->cplx, 0, cached, ps->d_reps, ps->d_norms, pl->pbuf, K, d_x, x_row, x_col, d_y, y_row,
+                                 y_col, alpha, beta, gamma, d_dots, stream));
+        stage_end(pl, st, stream);
+    }
+    if (cached < n && block_pbuf(pl) != 0) return -1;
+    for (int64_t r0 = cached; r0 < n; r0 += pl->blk_rows) {
+        int64_t const r1 = r0 + pl->blk_rows < n ? r0 + pl->blk_rows : n;
+        lsk_pullbuf pb = pl->blk_pbuf;
+        pb.row0 = r0;
+        int st = stage_begin(pl, ST_GENERATE, stream);
+        DEV(lsk_tile_pull_resolve(pl->dop, pl->dbs, r0, r1, ps->d_reps, ps->d_norms, ix, ps->d_reps, ps->count, pl->pull_halo, pb, pl->d_err,
+                                  stream));
+        stage_end(pl, st, stream);
+        st = stage_begin(pl, ST_ROWS, stream);
+        DEV(lsk_pull_gather_cheb(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, K, d_x, x_row, x_col, d_y, y_row, y_col,
+                                 alpha, beta, gamma, d_dots, stream));
         stage_end(pl, st, stream);
     }
     timing_end(pl, slot, stream);

@@ -483,6 +483,19 @@ int lsk_direct_blk(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, lsk_ti
 int lsk_pull_gather_blk(lsk_operator op, lsk_basis bs, int cplx, int64_t row0, int64_t row1, uint64_t const *reps,
                         double const *norms, lsk_pullbuf buf, int K, void const *x, int64_t xr, int64_t xc, void *y,
                         int64_t yr, int64_t yc, void *stream);
+/* ---- Chebyshev step (ls_amd_matvec_block_axpby; k_cheb.hip): Y <- alpha H X + beta X + gamma Y, K <= 64 columns, strides as above;
+ * <X_k|X_k> is ADDED to d_dots[k] and Re <X_k|Y_k> (the new Y) to d_dots[K + k] (NULL: no dots); gamma == 0: Y is not read.
+ * lsk_direct_cheb / lsk_pull_gather_cheb: the row loops of the two block kernels with that update where they store Y */
+int lsk_direct_cheb(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, lsk_tilemap tm, uint64_t const *reps, int K,
+                    void const *x, int64_t xr, int64_t xc, void *y, int64_t yr, int64_t yc, double alpha, double beta, double gamma,
+                    double *d_dots, int *d_err, void *stream);
+int lsk_pull_gather_cheb(lsk_operator op, lsk_basis bs, int cplx, int64_t row0, int64_t row1, uint64_t const *reps,
+                         double const *norms, lsk_pullbuf buf, int K, void const *x, int64_t xr, int64_t xc, void *y,
+                         int64_t yr, int64_t yc, double alpha, double beta, double gamma, double *d_dots, void *stream);
+/* the epilogue pass alone: Y <- alpha W + beta X + gamma Y (n rows, K columns, own strides); the dots are ADDED to d_xx[k], d_xy[k] */
+int lsk_axpby_dots(int cplx, int64_t n, int K, void const *w, int64_t wr, int64_t wc, void const *x, int64_t xr, int64_t xc,
+                   void *y, int64_t yr, int64_t yc, double alpha, double beta, double gamma, double *d_xx, double *d_xy,
+                   void *stream);
 /* out[i] = x[i] * norms[i] (f64 / c128): the owner-side prescaling of the indexed mode */
 int lsk_scale(int cplx, int64_t n, void const *x, double const *norms, void *out, void *stream);
 /* dst[perm[g] - base] = src[g] for every g with base <= perm[g] < base + count (8-byte elements): the rows one owner holds,

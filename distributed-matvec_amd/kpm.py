@@ -1,0 +1,285 @@
+"""Kernel polynomial method (Weisse, Wellein, Alvermann, Fehske, Rev. Mod. Phys. 78, 275): density of states and dynamical
+correlation functions S_A(w) = <psi|A^+ delta(w - H) A|psi> from Chebyshev moments mu_n = <v0|T_n(H~)|v0>, at any basis size the
+matvec reaches.  H~ = (H - b) / a maps the spectrum into [-1, 1] (a = (hi - lo) / 2, b = (hi + lo) / 2).
+
+The recurrence v_{n+1} = 2 H~ v_n - v_{n-1} is one call of MatvecPlan.matvec_block_axpby per step (ls_amd_matvec_block_axpby: the
+update and both dot products of the step happen where the block kernels store their result), and every step yields two moments
+(mu_2n = 2 <v_n|v_n> - mu_0, mu_2n+1 = 2 <v_n|v_n+1> - mu_1): M moments cost M / 2 steps and two blocks of memory.  One-partition
+plans.  The Jackson-damped series is summed on the host."""
+from __future__ import annotations
+
+import math
+import time
+from dataclasses import dataclass
+
+import numpy as np
+
+from ._lib import LsAmdError
+
+GUARD_EVERY = 64      # steps between two read-backs of the dots (the only host synchronisations of the recurrence)
+GUARD_SLACK = 1e-6    # ||T_n(H~) v0||^2 <= (1 + slack) ||v0||^2 while the spectrum lies inside the bounds
+
+
+@dataclass
+class KpmResult:
+    moments: np.ndarray       # [K, M] float64: mu_n of every start vector
+    bounds: tuple             # (lo, hi) the spectrum was rescaled with
+    matvec_columns: int       # columns that went through H (K per step)
+    kernel: str               # MatvecPlan.axpby_kernel(K): "k_direct_cheb", "k_pull_gather_cheb" or "epilogue"
+    seconds: float = 0.0      # wall time of the driver
+    step_seconds: float = 0.0  # ... of which inside the Chebyshev steps (device time included: measured around a synchronisation)
+    state: object = None      # spectral_function: the state |psi> the operator was applied to (device tensor)
+
+    @property
+    def trace_moments(self):
+        """the moments of the normalised trace, sum_k mu_n^(k) / sum_k mu_0^(k): [M]"""
+        return self.moments.sum(axis=0) / self.moments[:, 0].sum()
+
+
+def jackson_kernel(num_moments: int) -> np.ndarray:
+    """g_n of the Jackson kernel for M moments (RMP 78, 275, eq. 71): g_0 = 1, positive, decreasing"""
+    M = int(num_moments)
+    n = np.arange(M, dtype=np.float64)
+    q = math.pi / (M + 1)
+    return ((M - n + 1) * np.cos(q * n) + np.sin(q * n) / math.tan(q)) / (M + 1)
+
+
+def reconstruct(moments, bounds, energies) -> np.ndarray:
+    """f(E) = 1 / (pi a sqrt(1 - x^2)) [g_0 mu_0 + 2 sum_n g_n mu_n T_n(x)],  x = (E - b) / a, zero outside the bounds:
+    the Jackson-damped Chebyshev series of the moments [M] (or [..., M]: one curve per leading index) at the energies [E]."""
+    mu = np.asarray(moments, dtype=np.float64)
+    lo, hi = float(bounds[0]), float(bounds[1])
+    a, b = 0.5 * (hi - lo), 0.5 * (hi + lo)
+    M = mu.shape[-1]
+    c = mu * jackson_kernel(M)
+    c[..., 1:] *= 2.0
+    x = (np.asarray(energies, dtype=np.float64) - b) / a
+    inside = np.abs(x) < 1.0
+    theta = np.arccos(np.where(inside, x, 0.0))
+    out = np.zeros(mu.shape[:-1] + x.shape, dtype=np.float64)
+    n = np.arange(M, dtype=np.float64)
+    for e0 in range(0, x.size, 4096):  # (the cosine table in slabs: [4096, M])
+        e1 = min(x.size, e0 + 4096)
+        T = np.cos(theta.reshape(-1)[e0:e1, None] * n[None, :])
+        out.reshape(mu.shape[:-1] + (-1,))[..., e0:e1] = (c @ T.T) / (math.pi * a * np.sin(theta.reshape(-1)[e0:e1]))
+    return np.where(inside, out, 0.0)
+
+
+def chebyshev_grid(bounds, points: int) -> np.ndarray:
+    """E_k = b + a cos(pi (k + 1/2) / points), ascending: the abscissas the series is cheapest and best conditioned on"""
+    lo, hi = float(bounds[0]), float(bounds[1])
+    k = np.arange(points, dtype=np.float64)
+    return 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.cos(math.pi * (k + 0.5) / points)[::-1]
+
+
+def moments_from_dots(dots, K: int, num_moments: int) -> np.ndarray:
+    """dots [steps, 2K] (row n: <v_n|v_n> per column, then <v_n|v_n+1>) -> moments [K, M] by the doubling formulas"""
+    d = np.asarray(dots, dtype=np.float64)
+    steps = d.shape[0]
+    mu = np.empty((K, 2 * steps), dtype=np.float64)
+    mu[:, 0] = d[0, :K]
+    mu[:, 1] = d[0, K:]
+    for n in range(1, steps):
+        mu[:, 2 * n] = 2.0 * d[n, :K] - mu[:, 0]
+        mu[:, 2 * n + 1] = 2.0 * d[n, K:] - mu[:, 1]
+    return mu[:, :num_moments]
+
+
+def check_guard(dots, K: int, bounds, first_step: int = 0):
+    """||T_n(H~) v0|| <= ||v0|| holds whenever the spectrum lies inside the bounds: raise when some <v_n|v_n> of dots [steps, 2K]
+    (or a non-finite one) says it does not.  dots[0] must be the first step's row (mu_0) -- first_step only names the offset."""
+    d = np.asarray(dots, dtype=np.float64)
+    mu0 = d[0, :K]
+    norms = d[:, :K]
+    bad = ~(norms <= (1.0 + GUARD_SLACK) * mu0[None, :])
+    if bad.any():
+        step = int(np.argmax(bad.any(axis=1)))
+        raise LsAmdError(f"kpm: the Chebyshev recurrence grows at step {first_step + step} (<v_n|v_n> / <v_0|v_0> = "
+                         f"{float(np.nanmax(norms[step] / mu0)):.6g}): the spectrum is not inside the bounds ({bounds[0]!r}, {bounds[1]!r})")
+
+
+def chebyshev_moments(op, start, num_moments: int, bounds) -> np.ndarray:
+    """mu_n = <v0_k|T_n(H~)|v0_k> for the K columns of the (n, K) device block `start`, n < num_moments: [K, M] float64.
+    op: a diagonalize.LocalOperator on one partition.  The dots of all steps land in one device array; it is read back (the
+    only synchronisation) every GUARD_EVERY steps for the guard."""
+    import torch
+
+    M = int(num_moments)
+    if M < 2:
+        raise ValueError(f"num_moments = {num_moments!r}: at least 2")
+    lo, hi = float(bounds[0]), float(bounds[1])
+    if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+        raise ValueError(f"bounds = ({bounds[0]!r}, {bounds[1]!r}): need finite lo < hi")
+    if len(op.sizes) != 1:
+        raise LsAmdError("kpm: one-partition plans only")
+    if start.dim() != 2 or start.shape[0] != op.n_local:
+        raise LsAmdError(f"kpm: start {tuple(start.shape)} must be an ({op.n_local}, K) block")
+    a, b = 0.5 * (hi - lo), 0.5 * (hi + lo)
+    K = int(start.shape[1])
+    steps = (M + 1) // 2
+    X = start.to(op.dtype).contiguous().clone()
+    Y = torch.empty_like(X)
+    dots = torch.zeros((steps, 2 * K), dtype=torch.float64, device=X.device)
+    plan = op.plan
+    checked = 0
+    host = np.empty((steps, 2 * K), dtype=np.float64)
+
+    def read_back(upto):
+        nonlocal checked
+        host[checked:upto] = dots[checked:upto].cpu().numpy()
+        plan.check()
+        check_guard(np.concatenate([host[:1], host[checked:upto]]), K, (lo, hi), first_step=checked - 1)
+        checked = upto
+
+    for s in range(steps):
+        if s == 0:
+            plan.matvec_block_axpby(X, Y, 1.0 / a, -b / a, 0.0, dots=dots[0], check=False)
+        else:
+            plan.matvec_block_axpby(X, Y, 2.0 / a, -2.0 * b / a, -1.0, dots=dots[s], check=False)
+        X, Y = Y, X
+        op.matvecs += K
+        if (s + 1) % GUARD_EVERY == 0:
+            read_back(s + 1)
+    if checked < steps:
+        read_back(steps)
+    return moments_from_dots(host, K, M)
+
+
+class _Negated:
+    """-H through the operator interface of lanczos_smallest"""
+
+    def __init__(self, op):
+        self.op = op
+
+    def __getattr__(self, name):
+        return getattr(self.op, name)
+
+    def matvec(self, x, y):
+        self.op.matvec(x, y)
+        y.neg_()
+
+    @property
+    def matvecs(self):
+        return self.op.matvecs
+
+
+def spectral_bounds(op, eps: float = 1e-3, widen: float = 0.01):
+    """(lo, hi) enclosing the spectrum of the Hermitian operator: the extremal Ritz values of two loose Lanczos runs (on H and on
+    -H), widened by `widen` of the width on each side -- Ritz values lie INSIDE the spectrum."""
+    from .diagonalize import lanczos_smallest
+
+    e_min = lanczos_smallest(op, num_evals=1, eps=eps).eigenvalues[0]
+    e_max = -lanczos_smallest(_Negated(op), num_evals=1, eps=eps).eigenvalues[0]
+    width = max(e_max - e_min, 1e-9 * max(1.0, abs(e_min), abs(e_max)))
+    return e_min - widen * width, e_max + widen * width
+
+
+def random_phase_block(n: int, K: int, dtype, seed: int, device="cuda"):
+    """(n, K) start vectors for a stochastic trace, generated on the device: random signs (f64) or random phases (c128)"""
+    import torch
+
+    g = torch.Generator(device=device).manual_seed(int(seed))
+    if dtype == torch.complex128:
+        phi = torch.rand((n, K), dtype=torch.float64, device=device, generator=g) * (2.0 * math.pi)
+        return torch.polar(torch.ones_like(phi), phi)
+    return (torch.randint(0, 2, (n, K), device=device, generator=g, dtype=torch.int64) * 2 - 1).to(torch.float64)
+
+
+def _load(config, observables=False):
+    from . import api
+
+    load = api.loadConfigFromYaml if isinstance(config, str) else api.loadConfigFromDict
+    out = load(config, hamiltonian=True, observables=observables)
+    h = out[1]
+    if not h.isHermitian:
+        raise ValueError("kpm: the Hamiltonian is not Hermitian (Chebyshev moments need a real spectrum)")
+    return out
+
+
+def density_of_states(config, num_moments: int = 256, num_vectors: int = 8, seed: int = 0, bounds=None, dtype=None, energies=None,
+                      start=None):
+    """rho(E) = (1 / n) sum_j delta(E - E_j) of the configured Hamiltonian (dict or YAML path) by a stochastic trace over
+    `num_vectors` random-sign (c128: random-phase) vectors, or over the columns of the (n, K) device block `start`.
+    -> (energies, rho, KpmResult); energies default to a Chebyshev grid of 2 M points inside the bounds (spectral_bounds(op) unless
+    given)."""
+    import torch
+
+    from . import api
+    from .diagonalize import LocalOperator
+
+    t0 = time.perf_counter()
+    basis, h = _load(config)
+    dtype = dtype or torch.float64
+    reps, _ = api.enumerateStates(basis, 1)
+    op = LocalOperator(h, reps, dtype)
+    if bounds is None:
+        bounds = spectral_bounds(op)
+    bounds = (float(bounds[0]), float(bounds[1]))
+    if start is None:
+        if not 1 <= int(num_vectors) <= 64:
+            raise ValueError(f"num_vectors = {num_vectors!r}: 1 <= num_vectors <= 64")
+        start = random_phase_block(op.n_local, int(num_vectors), dtype, seed, device=op.device)
+    K = int(start.shape[1])
+    before = op.matvecs
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    mu = chebyshev_moments(op, start, num_moments, bounds)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    res = KpmResult(mu, bounds, op.matvecs - before, op.plan.axpby_kernel(K))
+    if energies is None:
+        energies = chebyshev_grid(bounds, 2 * int(num_moments))
+    energies = np.asarray(energies, dtype=np.float64)
+    rho = reconstruct(res.trace_moments, bounds, energies)
+    res.step_seconds = t2 - t1
+    res.seconds = time.perf_counter() - t0
+    return energies, rho, res
+
+
+def spectral_function(config, operator, state=None, num_moments: int = 256, energies=None, bounds=None, dtype=None,
+                      eps: float = 1e-10):
+    """S_A(w) = <psi|A^+ delta(w - H) A|psi> on the absolute energy scale of H.  operator: an api.Operator on the basis of the
+    config, or the index of one of the config's `observables`; it must map the basis into itself.  state: a device vector in the
+    order of the representatives; None: the ground state (thick-restart Lanczos to `eps`).  -> (energies, S, KpmResult)."""
+    import torch
+
+    from . import api
+    from .diagonalize import LocalOperator, lanczos_smallest
+
+    t0 = time.perf_counter()
+    basis, h, obs = _load(config, observables=True)
+    if isinstance(operator, (int, np.integer)) and not isinstance(operator, bool):
+        if not 0 <= int(operator) < len(obs):
+            raise ValueError(f"operator = {operator}: the config has {len(obs)} observables")
+        A = obs[int(operator)]
+    elif isinstance(operator, api.Operator):
+        A = operator
+    else:
+        raise ValueError("operator: an api.Operator or the index of one of the config's observables")
+    dtype = dtype or torch.float64
+    reps, _ = api.enumerateStates(basis, 1)
+    op = LocalOperator(h, reps, dtype)
+    if state is None:
+        state = lanczos_smallest(op, num_evals=1, eps=eps).eigenvectors[0]
+    state = state.to(dtype).contiguous()
+    if state.dim() != 1 or state.numel() != op.n_local:
+        raise LsAmdError(f"kpm: state {tuple(state.shape)} must be a vector of {op.n_local} elements")
+    if bounds is None:
+        bounds = spectral_bounds(op)
+    bounds = (float(bounds[0]), float(bounds[1]))
+    v0 = torch.zeros_like(state)
+    api.MatvecPlan(A, reps, dtype).matvec([state], [v0])
+    before = op.matvecs
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    mu = chebyshev_moments(op, v0.reshape(-1, 1), num_moments, bounds)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    res = KpmResult(mu, bounds, op.matvecs - before, op.plan.axpby_kernel(1), state=state)
+    if energies is None:
+        energies = chebyshev_grid(bounds, 2 * int(num_moments))
+    energies = np.asarray(energies, dtype=np.float64)
+    S = reconstruct(mu[0], bounds, energies)
+    res.step_seconds = t2 - t1
+    res.seconds = time.perf_counter() - t0
+    return energies, S, res

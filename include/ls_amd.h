@@ -321,6 +321,26 @@ int ls_amd_matvec_block(ls_amd_plan *plan, int K, void const *d_x, int64_t x_row
 /* which path a block of K columns takes on this plan now: "k_direct_blk", "k_pull_gather_blk" or "columns" (NULL plan or K out of
  * range: NULL, with ls_amd_last_error set) */
 char const *ls_amd_plan_block_kernel_name(ls_amd_plan const *plan, int K);
+
+/* Chebyshev / Lanczos step on a block (the kernel polynomial method, distributed_matvec_amd.kpm):
+ * Y[:,k] <- alpha * (H X)[:,k] + beta * X[:,k] + gamma * Y[:,k]   for k < K (1 <= K <= 64), strides as ls_amd_matvec_block.
+ * d_dots: NULL, or 2K doubles on the device, ASSIGNED: [k] = <X_k|X_k>, [K + k] = Re <X_k|Y_k> with the new Y.
+ * gamma == 0: Y is not read.  X and Y must not overlap.  One-partition plans only.  Asynchronous on `stream`;
+ * ls_amd_plan_check as after ls_amd_matvec_block.
+ * Where ls_amd_matvec_block would run k_direct_blk / k_pull_gather_blk, the same row loop runs with the update and the two sums in
+ * place of its store (k_direct_cheb / k_pull_gather_cheb: Y is read and written once, nothing else is added to the matvec's
+ * traffic); everywhere else each column goes through ls_amd_matvec into one column of scratch and one streaming pass finishes it
+ * ("epilogue").  LS_AMD_BLOCK and LS_AMD_BLOCK_RESOLVE_BYTES apply as they do to ls_amd_matvec_block. */
+int ls_amd_matvec_block_axpby(ls_amd_plan *plan, int K, void const *d_x, int64_t x_row, int64_t x_col,
+                              void *d_y, int64_t y_row, int64_t y_col, double alpha, double beta, double gamma,
+                              double *d_dots, void *stream);
+/* "k_direct_cheb", "k_pull_gather_cheb" or "epilogue" (block matvec into scratch, then k_axpby_dots) */
+char const *ls_amd_plan_axpby_kernel_name(ls_amd_plan const *plan, int K);
+/* the epilogue alone, no plan: Y <- alpha W + beta X + gamma Y and the same two dots (W, X, Y: K columns of n rows, own strides;
+ * cplx != 0: c128 elements, else f64).  W and Y, X and Y must not overlap. */
+int ls_amd_block_axpby_dots(int cplx, int64_t n, int K, void const *d_w, int64_t w_row, int64_t w_col, void const *d_x, int64_t x_row,
+                            int64_t x_col, void *d_y, int64_t y_row, int64_t y_col, double alpha, double beta, double gamma,
+                            double *d_dots, void *stream);
 int ls_amd_plan_check(ls_amd_plan *plan, void *stream);
 
 /* ------------------------------------------------------------------------------------------
