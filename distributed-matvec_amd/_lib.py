@@ -152,6 +152,14 @@ def load():
         "ls_amd_plan_enable_stage_timing": (C.c_int, [vp, C.c_int]),
         "ls_amd_plan_stage_times": (C.c_int, [vp, c_f64p, c_i64p, c_i64p]),
         "ls_amd_plan_timing_report": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
+        "ls_amd_operator_adjoint": (op, [op]),
+        "ls_amd_operator_maps_sector": (C.c_int, [op, bp]),
+        "ls_amd_cross_create": (C.c_int, [C.POINTER(vp), op, bp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
+        "ls_amd_cross_apply": (C.c_int, [vp, vp, vp, vp]),
+        "ls_amd_cross_check": (C.c_int, [vp, vp]),
+        "ls_amd_cross_kernel_name": (C.c_char_p, [vp]),
+        "ls_amd_cross_nnz": (C.c_int64, [vp]),
+        "ls_amd_cross_destroy": (None, [vp]),
         "ls_amd_fill_random": (C.c_int, [C.c_int64, vp, C.c_uint64, C.c_int, vp, vp]),
         "ls_amd_diag": (C.c_int, [vp, vp, vp, vp]),
         "ls_amd_generate": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),

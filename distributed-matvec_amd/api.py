@@ -25,7 +25,7 @@ __all__ = [
     "Basis", "Operator", "LsAmdError", "loadConfigFromYaml", "loadConfigFromDict", "enumerateStates",
     "arrFromBlockToHashed", "arrFromHashedToBlock", "matrixVectorProduct", "localMatrixVector",
     "localeIdxOf", "hash64_01", "MatvecPlan", "ReplicatedPlan", "build_library", "fillRandom",
-    "Communicator", "DistMatvec", "ReplMatvec", "block_axpby_dots",
+    "Communicator", "DistMatvec", "ReplMatvec", "block_axpby_dots", "CrossSectorPlan",
 ]
 
 
@@ -194,6 +194,27 @@ class Operator:
 
     @property
     def isReal(self): return bool(_lib.load().ls_hs_operator_is_real(self.payload))
+
+    def adjoint(self) -> "Operator":
+        """A^+ on the same basis (ls_amd_operator_adjoint): the conjugate transpose of every term; host only"""
+        L = _lib.load()
+        p = L.ls_amd_operator_adjoint(self.payload)
+        if not p:
+            raise LsAmdError(L.ls_amd_last_error().decode())
+        out = Operator(p, True)
+        out.basis.spec = self.basis.spec
+        return out
+
+    def mapsSector(self, target_basis: Basis, explain: bool = False) -> bool:
+        """whether this operator maps its own (source) sector into the sector of target_basis (ls_amd_operator_maps_sector: the
+        exact covariance check U_g A U_g^-1 = chi2(g) conj(chi1(g)) A on the term tables; host only).  explain=True raises LsAmdError
+        with the reason -- the offending generator, or why the two bases cannot be paired -- instead of returning False."""
+        L = _lib.load()
+        rc = L.ls_amd_operator_maps_sector(self.payload, target_basis.payload)
+        if rc != 0 and explain:
+            raise LsAmdError(L.ls_amd_last_error().decode("utf-8", "replace"))
+        _lib.raise_pending_halt()
+        return rc == 0
 
     # host-pointer entry points of the kernel table ----------------------------------------------
     def __matmul__(self, x: np.ndarray) -> np.ndarray:
@@ -591,6 +612,85 @@ class MatvecPlan:
         n = len(counts)
         _lib.check(_lib.load().ls_amd_scatter_round(self.h, n, (C.c_int64 * n)(*counts), (C.c_int64 * n)(*offsets), C.c_void_p(recv_ptr),
                                                     C.c_void_p(y.data_ptr()), _stream_ptr()))
+
+
+class CrossSectorPlan:
+    """ls_amd_cross: y = A x between two symmetry sectors (include/ls_amd.h).  operator: A on the SOURCE basis; source_reps /
+    target_reps: the ascending representatives of the source basis / of target_basis (device tensors, one partition); x lives on
+    the source rows, y on the target rows.  Creation checks that A maps the source sector into the target's (LsAmdError names the
+    offending generator otherwise); float64 needs a real operator and +-1 characters on both bases."""
+
+    def __init__(self, operator: Operator, source_reps, target_basis: Basis, target_reps, dtype):
+        torch = _torch()
+        _lib.require_device()
+        for name, t in (("source_reps", source_reps), ("target_reps", target_reps)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int64 or t.device.type != "cuda" or not t.is_contiguous():
+                raise LsAmdError(f"CrossSectorPlan: {name} must be a contiguous 1-D int64 device tensor (one partition)")
+        self.operator, self.target_basis = operator, target_basis
+        self.source_reps, self.target_reps = source_reps, target_reps  # borrowed by the plan: keep alive
+        self.cplx = dtype in (torch.complex128, "c128")
+        if not self.cplx and dtype not in (torch.float64, "f64"):
+            raise LsAmdError(f"CrossSectorPlan: dtype {dtype} is neither float64 nor complex128")
+        self.dtype = torch.complex128 if self.cplx else torch.float64
+        h = C.c_void_p()
+        _lib.check(_lib.load().ls_amd_cross_create(C.byref(h), operator.payload, target_basis.payload, 1 if self.cplx else 0,
+                                                   C.c_void_p(source_reps.data_ptr()), source_reps.numel(),
+                                                   C.c_void_p(target_reps.data_ptr()), target_reps.numel(), _stream_ptr()))
+        self.h = h
+
+    def destroy(self):
+        if getattr(self, "h", None):
+            _lib.load().ls_amd_cross_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    @property
+    def kernel(self): return _lib.load().ls_amd_cross_kernel_name(self.h).decode()
+    @property
+    def nnz(self): return int(_lib.load().ls_amd_cross_nnz(self.h))
+    @property
+    def n_src(self): return int(self.source_reps.numel())
+    @property
+    def n_dst(self): return int(self.target_reps.numel())
+
+    def _vector(self, name, t, n):
+        torch = _torch()
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise LsAmdError(f"CrossSectorPlan.apply: {name} must be a device tensor")
+        if t.dtype != self.dtype:
+            raise LsAmdError(f"CrossSectorPlan.apply: {name} is {t.dtype}, the plan computes in {self.dtype}")
+        if t.dim() not in (1, 2) or t.shape[0] != n:
+            raise LsAmdError(f"CrossSectorPlan.apply: {name} {tuple(t.shape)} must have {n} rows")
+
+    def apply(self, x, y, check: bool = True):
+        """y <- A x: x of n_src, y of n_dst elements (y is assigned); (n_src, K) and (n_dst, K) blocks are a loop over the columns"""
+        self._vector("x", x, self.n_src)
+        self._vector("y", y, self.n_dst)
+        if x.dim() != y.dim() or (x.dim() == 2 and x.shape[1] != y.shape[1]):
+            raise LsAmdError(f"CrossSectorPlan.apply: x {tuple(x.shape)} and y {tuple(y.shape)} must both be vectors or both have K columns")
+        L = _lib.load()
+        if x.dim() == 1:
+            xc = x if x.is_contiguous() else x.contiguous()
+            yc = y if y.is_contiguous() else _torch().empty_like(y, memory_format=_torch().contiguous_format)
+            _lib.check(L.ls_amd_cross_apply(self.h, C.c_void_p(xc.data_ptr()), C.c_void_p(yc.data_ptr()), _stream_ptr()))
+            if yc is not y:
+                y.copy_(yc)
+        else:
+            for k in range(int(x.shape[1])):
+                xc = x[:, k].contiguous()
+                yc = _torch().empty(self.n_dst, dtype=self.dtype, device=y.device)
+                _lib.check(L.ls_amd_cross_apply(self.h, C.c_void_p(xc.data_ptr()), C.c_void_p(yc.data_ptr()), _stream_ptr()))
+                y[:, k].copy_(yc)
+        if check:
+            self.check()
+
+    def check(self):
+        _lib.check(_lib.load().ls_amd_cross_check(self.h, _stream_ptr()))
 
 
 class _BorrowedPlan(MatvecPlan):

@@ -4958,3 +4958,378 @@ void ls_internal_operator_apply_off_diag_x1(ls_hs_operator const *op, ptrdiff_t 
     free(h_off);
     if (rc) halt_with("%s", lsk_last_error());
 }
+
+/* ============================================================================================ */
+/* cross-sector operators (include/ls_amd.h: ls_amd_operator_adjoint, ls_amd_operator_maps_sector, ls_amd_cross) */
+/* ============================================================================================ */
+/* every term of an operator as (v, m, r, x, s): the diagonal ones (x = 0), then the groups */
+static int operator_raw_terms(ls_hs_operator const *op, raw_term **out) {
+    struct ls_amd_operator_ext const *e = OEXT(op);
+    int const n = e->n_diag + e->n_off;
+    raw_term *t = (raw_term *)malloc(sizeof(raw_term) * (size_t)(n > 0 ? n : 1));
+    int k = 0;
+    for (int i = 0; i < e->n_diag; ++i, ++k) { raw_term r = {e->diag[i].v_re, e->diag[i].v_im, e->diag[i].m, e->diag[i].r, 0, e->diag[i].s}; t[k] = r; }
+    for (int g = 0; g < e->n_groups; ++g)
+        for (int i = e->groups[g].begin; i < e->groups[g].end; ++i, ++k) {
+            raw_term r = {e->off[i].v_re, e->off[i].v_im, e->off[i].m, e->off[i].r, e->groups[g].x, e->off[i].s};
+            t[k] = r;
+        }
+    *out = t;
+    return n;
+}
+
+/* A|a> = v [a & m == r] (-1)^popcount(a & s) |a ^ x>, so <b|A|a> lives at b = a ^ x and
+ *   A+|b> = conj(v) [(b ^ x) & m == r] (-1)^popcount((b ^ x) & s) |b ^ x>
+ *         = conj(v) (-1)^popcount(x & s) [b & m == r ^ (x & m)] (-1)^popcount(b & s) |b ^ x>
+ * (the parity of (b ^ x) & s is the sum of the parities of b & s and x & s) */
+ls_hs_operator *ls_amd_operator_adjoint(ls_hs_operator const *op) {
+    if (!op) { set_error("ls_amd_operator_adjoint: NULL operator"); return NULL; }
+    if (!reg_get(op)) { set_error("ls_amd_operator_adjoint: unknown operator (ls_amd_adopt_operator first)"); return NULL; }
+    raw_term *t = NULL;
+    int const n = operator_raw_terms(op, &t);
+    size_t const cap = (size_t)(n > 0 ? n : 1);
+    double *v = (double *)malloc(16 * cap);
+    uint64_t *m = (uint64_t *)malloc(8 * cap), *r = (uint64_t *)malloc(8 * cap), *x = (uint64_t *)malloc(8 * cap), *s = (uint64_t *)malloc(8 * cap);
+    for (int k = 0; k < n; ++k) {
+        double const sg = (__builtin_popcountll(t[k].x & t[k].s) & 1) ? -1.0 : 1.0;
+        v[2 * k] = sg * t[k].re; v[2 * k + 1] = -sg * t[k].im;
+        m[k] = t[k].m; r[k] = t[k].r ^ (t[k].x & t[k].m); x[k] = t[k].x; s[k] = t[k].s;
+    }
+    ls_hs_operator *adj = ls_hs_create_operator_from_terms(op->basis, n, v, m, r, x, s);
+    free(t); free(v); free(m); free(r); free(x); free(s);
+    return adj;
+}
+
+/* ---- the covariance check: U_g A U_g^-1 == chi2(g) conj(chi1(g)) A for every generator and the spin inversion ----
+ * A term is first written out on its full support u = m | x | s as 2^|u \ m| pure projector terms (u, pattern, x) with the sign
+ * folded into the coefficient: sigma^z given as a sign mask and as two projector terms then are the same two entries.  A
+ * permutation relabels the sites of such an entry, (g.w)[i] = w[g[i]] for w = u, pattern, x; the inversion complements the
+ * pattern inside u.  Two operators are compared entry by entry after sorting and merging. */
+typedef struct { uint64_t u, r, x; double re, im; } canon_term;
+static int canon_cmp(void const *pa, void const *pb) {
+    canon_term const *a = (canon_term const *)pa, *b = (canon_term const *)pb;
+    if (a->x != b->x) return a->x < b->x ? -1 : 1;
+    if (a->u != b->u) return a->u < b->u ? -1 : 1;
+    if (a->r != b->r) return a->r < b->r ? -1 : 1;
+    return 0;
+}
+#define CANON_MAX_FREE 12 /* sites of a term's support outside its projector mask (spin operators: 0-2) */
+static int64_t canon_expand(ls_hs_operator const *op, canon_term **out) {
+    raw_term *t = NULL;
+    int const n = operator_raw_terms(op, &t);
+    int64_t total = 0;
+    for (int k = 0; k < n; ++k) {
+        int const nf = __builtin_popcountll((t[k].x | t[k].s) & ~t[k].m);
+        if (nf > CANON_MAX_FREE) { free(t); *out = NULL; return -1; }
+        total += (int64_t)1 << nf;
+    }
+    canon_term *c = (canon_term *)malloc(sizeof(canon_term) * (size_t)(total > 0 ? total : 1));
+    int64_t w = 0;
+    for (int k = 0; k < n; ++k) {
+        uint64_t const fr = (t[k].x | t[k].s) & ~t[k].m;
+        int const nf = __builtin_popcountll(fr);
+        for (uint64_t pat = 0; pat < (1ULL << nf); ++pat) {
+            uint64_t const a = t[k].r | deposit_bits(pat, fr);
+            double const sg = (__builtin_popcountll(a & t[k].s) & 1) ? -1.0 : 1.0;
+            canon_term e = {t[k].m | fr, a, t[k].x, sg * t[k].re, sg * t[k].im};
+            c[w++] = e;
+        }
+    }
+    free(t);
+    *out = c;
+    return total;
+}
+static int64_t canon_merge(canon_term *c, int64_t n) {
+    qsort(c, (size_t)n, sizeof(canon_term), canon_cmp);
+    int64_t w = 0;
+    for (int64_t i = 0; i < n;) {
+        canon_term acc = c[i];
+        int64_t j = i + 1;
+        while (j < n && canon_cmp(&c[i], &c[j]) == 0) { acc.re += c[j].re; acc.im += c[j].im; ++j; }
+        c[w++] = acc;
+        i = j;
+    }
+    return w;
+}
+static uint64_t permute_mask(int const *p, int L, uint64_t w) { /* (g.w)[i] = w[p[i]] */
+    uint64_t out = 0;
+    for (int i = 0; i < L; ++i) out |= ((w >> p[i]) & 1ULL) << i;
+    return out;
+}
+/* largest |g.A - f A| over the entries (c: the merged entries of A, n of them; p == NULL: the inversion) */
+static double canon_defect(canon_term const *c, int64_t n, int const *p, int L, double f_re, double f_im) {
+    canon_term *both = (canon_term *)malloc(sizeof(canon_term) * (size_t)(2 * n > 0 ? 2 * n : 1));
+    for (int64_t i = 0; i < n; ++i) {
+        canon_term e = c[i];
+        if (p) { e.u = permute_mask(p, L, e.u); e.r = permute_mask(p, L, e.r); e.x = permute_mask(p, L, e.x); }
+        else e.r ^= e.u; /* (no sign mask is left after the expansion: the factor (-1)^popcount(s) of the inversion is 1) */
+        both[i] = e;
+        canon_term m = c[i];
+        m.re = -(f_re * c[i].re - f_im * c[i].im);
+        m.im = -(f_re * c[i].im + f_im * c[i].re);
+        both[n + i] = m;
+    }
+    int64_t const k = canon_merge(both, 2 * n);
+    double worst = 0.0;
+    for (int64_t i = 0; i < k; ++i) {
+        double const d = fabs(both[i].re) > fabs(both[i].im) ? fabs(both[i].re) : fabs(both[i].im);
+        if (d > worst) worst = d;
+    }
+    free(both);
+    return worst;
+}
+
+static int cross_preconditions(ls_hs_basis const *a, ls_hs_basis const *b) {
+    struct ls_amd_basis_ext const *ea = (struct ls_amd_basis_ext const *)reg_get(a), *eb = (struct ls_amd_basis_ext const *)reg_get(b);
+    if (!ea || !eb) return set_error("cross-sector: unknown basis (ls_amd_adopt_basis first)");
+    if (a->particle_type != b->particle_type) return set_error("cross-sector: the bases have different particle types (%d and %d)", a->particle_type, b->particle_type);
+    if (ea->fermi || eb->fermi)
+        return set_error("cross-sector: projected fermionic bases are not supported (permutation signs in the projection; follow-up: a "
+                         "sign-aware cross kernel next to k_fermi) -- use the unprojected (N, N_up) bases");
+    if (a->number_sites != b->number_sites || ea->nbits != eb->nbits)
+        return set_error("cross-sector: the bases have different number_sites (%d and %d)", a->number_sites, b->number_sites);
+    if (ea->nbits > 64) return set_error("cross-sector: more than 64 sites are not supported (number_words == 1)");
+    if ((a->spin_inversion != 0) != (b->spin_inversion != 0))
+        return set_error("cross-sector: spin inversion is present on one basis only (source %d, target %d)", a->spin_inversion, b->spin_inversion);
+    if (ea->n_generators != eb->n_generators ||
+        (ea->n_generators > 0 && memcmp(ea->gen_perms, eb->gen_perms, sizeof(int) * (size_t)ea->n_generators * (size_t)ea->nbits) != 0))
+        return set_error("cross-sector: the bases have different generators (same permutations in the same order are required; only the "
+                         "sectors may differ)");
+    return 0;
+}
+
+int ls_amd_operator_maps_sector(ls_hs_operator const *op, ls_hs_basis const *target) {
+    if (!op || !target) return set_error("ls_amd_operator_maps_sector: NULL %s", !op ? "operator" : "target basis");
+    if (!reg_get(op)) return set_error("ls_amd_operator_maps_sector: unknown operator (ls_amd_adopt_operator first)");
+    ls_hs_basis const *src = op->basis;
+    if (cross_preconditions(src, target) != 0) return -1;
+    struct ls_amd_basis_ext const *es = BEXT(src), *et = BEXT(target);
+    int const L = es->nbits;
+    if (es->n_generators == 0 && src->spin_inversion == 0) return 0; /* no group: nothing to be covariant under */
+    canon_term *c = NULL;
+    int64_t n = canon_expand(op, &c);
+    if (n < 0) return set_error("ls_amd_operator_maps_sector: a term's support exceeds its projector mask by more than %d sites", CANON_MAX_FREE);
+    n = canon_merge(c, n);
+    double vmax = 0.0;
+    for (int64_t i = 0; i < n; ++i) { double const a = fabs(c[i].re) > fabs(c[i].im) ? fabs(c[i].re) : fabs(c[i].im); if (a > vmax) vmax = a; }
+    double const tol = 1e-12 * vmax;
+    int rc = 0;
+    for (int g = 0; g < es->n_generators && rc == 0; ++g) {
+        int const *p = es->gen_perms + (size_t)g * L;
+        int const ord = perm_order(p, L);
+        /* chi(g) = exp(-2 pi i sector / order): chi2 conj(chi1) = exp(-2 pi i (sector2 - sector1) / order) */
+        double const phi = -2.0 * M_PI * (double)(et->gen_sectors[g] - es->gen_sectors[g]) / (double)ord;
+        double const defect = canon_defect(c, n, p, L, cos(phi), sin(phi));
+        if (defect > tol)
+            rc = set_error("the operator does not map the source sector into the target sector: under generator %d (sector %d -> %d of "
+                           "order %d) it must pick up the factor exp(-2 pi i %d / %d), and misses that by %.3g",
+                           g, es->gen_sectors[g], et->gen_sectors[g], ord, et->gen_sectors[g] - es->gen_sectors[g], ord, defect);
+    }
+    if (rc == 0 && src->spin_inversion != 0) {
+        double const f = (double)(src->spin_inversion * target->spin_inversion);
+        double const defect = canon_defect(c, n, NULL, L, f, 0.0);
+        if (defect > tol)
+            rc = set_error("the operator does not map the source sector into the target sector: under the spin inversion (character %d -> "
+                           "%d) it must pick up the factor %d, and misses that by %.3g", src->spin_inversion, target->spin_inversion, (int)f, defect);
+    }
+    free(c);
+    return rc;
+}
+
+struct ls_amd_cross {
+    ls_hs_operator *adj;      /* owned: the adjoint, on the source basis' struct (only its term tables are used) */
+    lsk_group *d_groups;      /* owned: the adjoint's groups, x = 0 first when it has diagonal terms */
+    lsk_term *d_terms;        /* owned */
+    int n_groups, is_real, cplx;
+    double tiny;              /* 1e-13 sum |v| over the adjoint's terms: a smaller summed coefficient is rounding residue, not a packet */
+    lsk_basis src;            /* device tables owned by the source basis */
+    lsk_index six;
+    uint32_t *d_table;        /* owned: prefix table of a searched (unprojected, incomplete) source */
+    ls_amd_gtab *gtab;        /* shared: static index table of a projected source */
+    double *d_norms;          /* owned: n2(r') of every target row */
+    uint64_t const *d_src_reps, *d_dst_reps; /* borrowed */
+    int64_t n_src, n_dst, nnz;
+    int *d_err;               /* owned; d_err + 2: the packet counter of the counting pass (8 bytes) */
+};
+
+void ls_amd_cross_destroy(ls_amd_cross *cx) {
+    if (!cx) return;
+    if (cx->d_groups) lsk_free(cx->d_groups);
+    if (cx->d_terms) lsk_free(cx->d_terms);
+    if (cx->d_table) lsk_free(cx->d_table);
+    if (cx->d_norms) lsk_free(cx->d_norms);
+    if (cx->d_err) lsk_free(cx->d_err);
+    if (cx->gtab) ls_amd_internal_gtab_release(cx->gtab);
+    if (cx->adj) ls_hs_destroy_operator(cx->adj);
+    free(cx);
+}
+
+static int cross_every_char_pm1(ls_hs_basis const *b) {
+    struct ls_amd_basis_ext const *e = BEXT(b);
+    for (int g = 0; g < e->order; ++g)
+        if (e->elems[g].ch_im != 0.0 || fabs(e->elems[g].ch_re) != 1.0) return 0;
+    return 1;
+}
+
+static int cross_setup(ls_amd_cross *cx, ls_hs_operator const *op, ls_hs_basis const *target, void *stream) {
+    ls_hs_basis const *src = op->basis;
+    struct ls_amd_basis_ext const *es = BEXT(src);
+    int const L = es->nbits;
+    lsk_basis dst;
+    if (basis_device(src, &cx->src) != 0 || basis_device(target, &dst) != 0) return -1;
+    /* the adjoint's device groups: the diagonal terms are the group with flip mask 0 (row i of the target is not column i of the
+     * source, so they take the projected path like every other group) */
+    struct ls_amd_operator_ext const *ae = OEXT(cx->adj);
+    int const nt = ae->n_diag + ae->n_off;
+    cx->n_groups = ae->n_groups + (ae->n_diag > 0 ? 1 : 0);
+    cx->is_real = ae->is_real;
+    for (int k = 0; k < ae->n_diag; ++k) cx->tiny += hypot(ae->diag[k].v_re, ae->diag[k].v_im);
+    for (int k = 0; k < ae->n_off; ++k) cx->tiny += hypot(ae->off[k].v_re, ae->off[k].v_im);
+    cx->tiny *= 1e-13;
+    if (cx->n_groups > 0) {
+        lsk_term *terms = (lsk_term *)malloc(sizeof(lsk_term) * (size_t)nt);
+        lsk_group *groups = (lsk_group *)calloc((size_t)cx->n_groups, sizeof(lsk_group));
+        int w = 0;
+        if (ae->n_diag > 0) {
+            memcpy(terms, ae->diag, sizeof(lsk_term) * (size_t)ae->n_diag);
+            groups[w].x = 0; groups[w].begin = 0; groups[w].end = ae->n_diag; groups[w].adj = -1; groups[w].fast = LSK_GROUP_GENERIC;
+            ++w;
+        }
+        if (ae->n_off > 0) memcpy(terms + ae->n_diag, ae->off, sizeof(lsk_term) * (size_t)ae->n_off);
+        for (int g = 0; g < ae->n_groups; ++g, ++w) {
+            groups[w] = ae->groups[g];
+            groups[w].begin += ae->n_diag; groups[w].end += ae->n_diag;
+            groups[w].fast = LSK_GROUP_GENERIC; /* the kernel sums the terms of every group */
+        }
+        void *p = NULL, *q = NULL;
+        int const bad = upload(&p, terms, sizeof(lsk_term) * (size_t)nt) != 0 || upload(&q, groups, sizeof(lsk_group) * (size_t)cx->n_groups) != 0;
+        cx->d_terms = (lsk_term *)p; cx->d_groups = (lsk_group *)q;
+        free(terms); free(groups);
+        if (bad) return -1;
+    }
+    void *p = NULL;
+    DEV(lsk_malloc(&p, 4 * sizeof(int)));
+    cx->d_err = (int *)p;
+    DEV(lsk_memset_async(cx->d_err, 0, 4 * sizeof(int), stream));
+    DEV(lsk_malloc(&p, 8 * (size_t)(cx->n_dst > 0 ? cx->n_dst : 1)));
+    cx->d_norms = (double *)p;
+    DEV(lsk_norms(dst, cx->n_dst, cx->d_dst_reps, cx->d_norms, stream));
+    /* the source look-up */
+    uint64_t const *d_binom;
+    if (device_binom(&d_binom) != 0) return -1;
+    memset(&cx->six, 0, sizeof(cx->six));
+    cx->six.kind = LSK_INDEX_SEARCH;
+    cx->six.count = cx->n_src;
+    cx->six.reps = cx->d_src_reps;
+    cx->six.binom = d_binom;
+    cx->six.dir_sites = L;
+    cx->six.dir_weight = es->hamming_weight;
+    if (cx->n_src >= 0xffffffffLL) return set_error("cross-sector: source bases with >= 2^32 - 1 states are not supported");
+    if (cx->src.proj != LSK_PROJ_NONE) {
+        if (cx->n_src > 0 && ls_amd_internal_gtab_acquire(&cx->gtab, L, cx->d_src_reps, cx->n_src, NULL, 1, stream) != 0) return -1;
+    } else if (cx->n_src > 0) {
+        int const h = es->hamming_weight;
+        int closed = 0, zero = 0, flag = 0;
+        if (h < 0 && L < 63 && cx->n_src == ((int64_t)1 << L)) { cx->six.kind = LSK_INDEX_IDENTITY; closed = 1; }
+        else if (h >= 0 && (uint64_t)cx->n_src == binom(L, h)) {
+            DEV(lsk_check_combinadic(cx->six, h, cx->n_src, cx->d_src_reps, cx->d_err, stream));
+            DEV(lsk_sync(stream));
+            DEV(lsk_d2h(&flag, cx->d_err, sizeof(int)));
+            DEV(lsk_h2d(cx->d_err, &zero, sizeof(int)));
+            if (!flag) { cx->six.kind = LSK_INDEX_COMBINADIC; closed = 1; }
+        } else if (es->product) {
+            lsk_index pix = cx->six;
+            pix.kind = LSK_INDEX_PRODUCT;
+            pix.prod_sites = src->number_sites; pix.prod_up = es->prod_up; pix.prod_dn = es->prod_dn;
+            pix.prod_na = (int64_t)binom(src->number_sites, es->prod_up);
+            if (cx->n_src == pix.prod_na * (int64_t)binom(src->number_sites, es->prod_dn)) {
+                DEV(lsk_check_product(pix, cx->n_src, cx->d_src_reps, cx->d_err, stream));
+                DEV(lsk_sync(stream));
+                DEV(lsk_d2h(&flag, cx->d_err, sizeof(int)));
+                DEV(lsk_h2d(cx->d_err, &zero, sizeof(int)));
+                if (!flag) { cx->six = pix; closed = 1; }
+            }
+        }
+        if (!closed) {
+            part_state ps;
+            memset(&ps, 0, sizeof(ps));
+            ps.count = cx->n_src;
+            ps.d_reps = (uint64_t *)cx->d_src_reps;
+            if (build_search_index(&ps, L, stream) != 0) return -1;
+            cx->d_table = ps.d_table;
+            cx->six.shift = ps.index.shift;
+            cx->six.table = ps.index.table;
+        }
+    }
+    /* counting pass: the packets that reach a source row (ls_amd_cross_nnz); whether some do not is left to the first apply */
+    unsigned long long count = 0;
+    if (cx->n_groups > 0 && cx->n_dst > 0 && cx->n_src > 0) {
+        int zero = 0;
+        DEV(lsk_cross_pull(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, cx->gtab ? cx->gtab->tab : no_gtab(), cx->cplx,
+                           cx->n_dst, cx->d_dst_reps, cx->d_norms, NULL, NULL, cx->tiny, (unsigned long long *)(cx->d_err + 2), cx->d_err, stream));
+        DEV(lsk_sync(stream));
+        DEV(lsk_d2h(&count, cx->d_err + 2, sizeof(count)));
+        DEV(lsk_h2d(cx->d_err, &zero, sizeof(int)));
+    }
+    cx->nnz = (int64_t)count;
+    return 0;
+}
+
+int ls_amd_cross_create(ls_amd_cross **out, ls_hs_operator const *op, ls_hs_basis const *target, ls_amd_dtype dtype,
+                        uint64_t const *d_src_reps, int64_t n_src, uint64_t const *d_dst_reps, int64_t n_dst, void *stream) {
+    if (out) *out = NULL;
+    if (!out || !op || !target) return set_error("ls_amd_cross_create: NULL %s", !out ? "handle" : (!op ? "operator" : "target basis"));
+    if (n_src < 0 || n_dst < 0 || (n_src > 0 && !d_src_reps) || (n_dst > 0 && !d_dst_reps))
+        return set_error("ls_amd_cross_create: NULL representatives or a negative count");
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("ls_amd_cross_create: unknown dtype %d", (int)dtype);
+    if (ls_amd_operator_maps_sector(op, target) != 0) return -1;
+    ls_hs_operator *adj = ls_amd_operator_adjoint(op);
+    if (!adj) return -1;
+    if (dtype == LS_AMD_F64 && !(OEXT(adj)->is_real && cross_every_char_pm1(op->basis) && cross_every_char_pm1(target))) {
+        ls_hs_destroy_operator(adj);
+        return set_error("ls_amd_cross_create: f64 needs a real operator and +-1 characters on both bases (complex characters or "
+                         "coefficients: use c128)");
+    }
+    ls_amd_cross *cx = (ls_amd_cross *)calloc(1, sizeof(*cx));
+    cx->adj = adj;
+    cx->cplx = dtype == LS_AMD_C128;
+    cx->d_src_reps = d_src_reps; cx->n_src = n_src;
+    cx->d_dst_reps = d_dst_reps; cx->n_dst = n_dst;
+    if (cross_setup(cx, op, target, stream) != 0) { ls_amd_cross_destroy(cx); return -1; }
+    *out = cx;
+    return 0;
+}
+
+int ls_amd_cross_apply(ls_amd_cross *cx, void const *d_x, void *d_y, void *stream) {
+    if (!cx || !d_y || (!d_x && cx && cx->n_src > 0)) return set_error("ls_amd_cross_apply: NULL %s", !cx ? "plan" : (!d_y ? "y" : "x"));
+    if (cx->n_dst == 0) return 0;
+    if (cx->n_groups == 0 || cx->n_src == 0) { /* A = 0, or nothing to read: y = 0 */
+        DEV(lsk_memset_async(d_y, 0, (size_t)cx->n_dst * (cx->cplx ? 16 : 8), stream));
+        return 0;
+    }
+    DEV(lsk_cross_pull(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, cx->gtab ? cx->gtab->tab : no_gtab(), cx->cplx,
+                       cx->n_dst, cx->d_dst_reps, cx->d_norms, d_x, d_y, cx->tiny, NULL, cx->d_err, stream));
+    return 0;
+}
+
+int ls_amd_cross_check(ls_amd_cross *cx, void *stream) {
+    if (!cx) return set_error("ls_amd_cross_check: NULL plan");
+    int flag = 0, zero = 0;
+    DEV(lsk_sync(stream));
+    DEV(lsk_d2h(&flag, cx->d_err, sizeof(int)));
+    if (flag) {
+        DEV(lsk_h2d(cx->d_err, &zero, sizeof(int)));
+        return set_error("cross-sector: the adjoint of the operator generated a state with non-zero norm that is not in the source basis "
+                         "(the operator does not map the source basis into the target basis, e.g. it changes the Hamming weight otherwise)");
+    }
+    return 0;
+}
+
+char const *ls_amd_cross_kernel_name(ls_amd_cross const *cx) {
+    if (!cx) { set_error("ls_amd_cross_kernel_name: NULL plan"); return NULL; }
+    return lsk_cross_kernel_name();
+}
+int64_t ls_amd_cross_nnz(ls_amd_cross const *cx) {
+    if (!cx) { set_error("ls_amd_cross_nnz: NULL plan"); return -1; }
+    return cx->nnz;
+}

@@ -544,6 +544,18 @@ int lsk_fermi_pull(lsk_operator op, lsk_basis bs, int wide, int cplx, int sink, 
                    double const *norms_local, lsk_pullidx ix, uint64_t const *reps_global, int64_t n_global, void const *xsrc, int halo,
                    void *y, lsk_pullbuf buf, int *d_err, void *stream);
 
+/* cross-sector operators (k_cross.hip): y[r'] = sum over the packets of the target rows r' = dst_reps[0, n_dst) -- the adjoint's
+ * flip-mask groups (groups / terms: device arrays, the x = 0 group included) applied to r', projected into the SOURCE basis `src`
+ * (always the general K4: orbit minimum, character, stabiliser norm), looked up there (gt.entries != NULL: the static index table
+ * of the source's representatives; else `six`, whose dir_sites / dir_weight hold the source's bits and Hamming weight) -- of
+ * conj(c) chi1(g0) n1(rep) / dst_norms[r'] x[index].  y is assigned.  *d_err is raised by a packet with non-zero source norm that
+ * is not in the source basis.  A group whose summed coefficient on a row is at most `tiny` in both parts is no packet (rounding
+ * residue of cancelling terms).  d_count != NULL: count the packets that reach a source row instead (x, y untouched). */
+char const *lsk_cross_kernel_name(void);
+int lsk_cross_pull(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
+                   lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, void const *x, void *y,
+                   double tiny, unsigned long long *d_count, int *d_err, void *stream);
+
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */
 int lsk_norms(lsk_basis bs, int64_t n, uint64_t const *reps, double *norms, void *stream);

@@ -29,6 +29,7 @@ class KpmResult:
     seconds: float = 0.0      # wall time of the driver
     step_seconds: float = 0.0  # ... of which inside the Chebyshev steps (device time included: measured around a synchronisation)
     state: object = None      # spectral_function: the state |psi> the operator was applied to (device tensor)
+    target_state: object = None  # spectral_function(target=...): v0 = A|psi> on the target basis (device tensor)
 
     @property
     def trace_moments(self):
@@ -236,12 +237,106 @@ def density_of_states(config, num_moments: int = 256, num_vectors: int = 8, seed
     return energies, rho, res
 
 
+def _terms_of(op):
+    """the (v, m, r, x, s) terms of an api.Operator, read through the ls_hs_nonbranching_terms ABI"""
+    import ctypes as C
+
+    out = []
+    for nbt in (op.payload.contents.diag_terms, op.payload.contents.off_diag_terms):
+        if not nbt:
+            continue
+        t = nbt.contents
+        n = int(t.number_terms)
+        v = np.frombuffer((C.c_double * (2 * n)).from_address(t.v), dtype=np.float64).reshape(n, 2)
+        m, r, x, s = (np.frombuffer((C.c_uint64 * n).from_address(q), dtype=np.uint64) for q in (t.m, t.r, t.x, t.s))
+        out += [(complex(v[i, 0], v[i, 1]), int(m[i]), int(r[i]), int(x[i]), int(s[i])) for i in range(n)]
+    return out
+
+
+def _target_basis(target):
+    """target of spectral_function: a `basis:` section, a whole config (dict), or the path of a YAML config -> api.Basis"""
+    from . import api
+
+    if isinstance(target, api.Basis):
+        return target
+    if isinstance(target, str):
+        return api.loadConfigFromYaml(target)
+    if isinstance(target, dict):
+        return api.loadConfigFromDict(target if "basis" in target else {"basis": target})
+    raise ValueError("target: a `basis:` section (dict), a whole config (dict or YAML path) or an api.Basis")
+
+
+def _spectral_function_cross(config, operator, target, state, num_moments, energies, bounds, dtype, eps):
+    """spectral_function for an operator that maps the config's sector into another one: psi lives in the config's own (source)
+    sector, v0 = A psi goes through an api.CrossSectorPlan, and the config's Hamiltonian -- re-compiled on the target basis from
+    its term tables -- supplies bounds and moments there."""
+    import torch
+
+    from . import api, config as _config
+    from .diagonalize import LocalOperator, lanczos_smallest
+
+    t0 = time.perf_counter()
+    basis, h, obs = _load(config, observables=True)
+    if isinstance(operator, (int, np.integer)) and not isinstance(operator, bool):
+        if not 0 <= int(operator) < len(obs):
+            raise ValueError(f"operator = {operator}: the config has {len(obs)} observables")
+        A = obs[int(operator)]
+    elif isinstance(operator, api.Operator):
+        A = operator
+    else:
+        raise ValueError("operator: an api.Operator (on the source basis) or the index of one of the config's observables")
+    dtype = dtype or torch.float64
+    tbasis = _target_basis(target)
+    A.mapsSector(tbasis, explain=True)
+    h_t = api.Operator.fromSpec(tbasis, _config.OperatorSpec(_terms_of(h)))
+    if not h_t.isHermitian:
+        raise ValueError("kpm: the Hamiltonian is not Hermitian (Chebyshev moments need a real spectrum)")
+    reps, _ = api.enumerateStates(basis, 1)
+    treps, _ = api.enumerateStates(tbasis, 1)
+    if state is None:
+        state = lanczos_smallest(LocalOperator(h, reps, dtype), num_evals=1, eps=eps).eigenvectors[0]
+    state = state.to(dtype).contiguous()
+    if state.dim() != 1 or state.numel() != reps[0].numel():
+        raise LsAmdError(f"kpm: state {tuple(state.shape)} must be a vector of {reps[0].numel()} elements (the source basis)")
+    op = LocalOperator(h_t, treps, dtype)
+    if bounds is None:
+        bounds = spectral_bounds(op)
+    bounds = (float(bounds[0]), float(bounds[1]))
+    v0 = torch.zeros(op.n_local, dtype=dtype, device=state.device)
+    cross = api.CrossSectorPlan(A, reps[0], tbasis, treps[0], dtype)
+    cross.apply(state, v0)
+    cross.destroy()
+    before = op.matvecs
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    mu = chebyshev_moments(op, v0.reshape(-1, 1), num_moments, bounds)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    res = KpmResult(mu, bounds, op.matvecs - before, op.plan.axpby_kernel(1), state=state, target_state=v0)
+    if energies is None:
+        energies = chebyshev_grid(bounds, 2 * int(num_moments))
+    energies = np.asarray(energies, dtype=np.float64)
+    S = reconstruct(mu[0], bounds, energies)
+    res.step_seconds = t2 - t1
+    res.seconds = time.perf_counter() - t0
+    return energies, S, res
+
+
 def spectral_function(config, operator, state=None, num_moments: int = 256, energies=None, bounds=None, dtype=None,
-                      eps: float = 1e-10):
+                      eps: float = 1e-10, target=None):
     """S_A(w) = <psi|A^+ delta(w - H) A|psi> on the absolute energy scale of H.  operator: an api.Operator on the basis of the
     config, or the index of one of the config's `observables`; it must map the basis into itself.  state: a device vector in the
-    order of the representatives; None: the ground state (thick-restart Lanczos to `eps`).  -> (energies, S, KpmResult)."""
+    order of the representatives; None: the ground state (thick-restart Lanczos to `eps`).  -> (energies, S, KpmResult).
+
+    target: the sector A maps INTO when that is not the config's own -- a `basis:` section (dict), a whole config whose basis it is
+    (dict or YAML path), or an api.Basis -- e.g. momentum k + q for S^z_q on a ground state of momentum k.  The operator is then
+    compiled on (and psi lives in) the config's own basis, the source; v0 = A psi is an api.CrossSectorPlan, and the config's
+    `hamiltonian:` is re-compiled on the target basis, where the bounds and the moments are computed; KpmResult.target_state is
+    v0.  Sectors with complex characters need dtype=torch.complex128."""
     import torch
+
+    if target is not None:
+        return _spectral_function_cross(config, operator, target, state, num_moments, energies, bounds, dtype, eps)
 
     from . import api
     from .diagonalize import LocalOperator, lanczos_smallest

@@ -447,6 +447,55 @@ int ls_amd_block_to_hashed(int64_t n, uint8_t const *d_masks, int num_locales, i
 int ls_amd_hashed_to_block(int64_t n, uint8_t const *d_masks, int num_locales, int elt_size,
                            void const *const *d_src, void *d_dest, void *stream);
 
+/* cross-sector operators ------------------------------------------------------------------------------------------------------
+ * An operator A that does not map a symmetry sector into itself -- S^z_q = sum_j e^{-iqj} sigma^z_j takes momentum k to k + q,
+ * S^+_q changes the Hamming weight, c+ the particle numbers -- is applied BETWEEN two bases: x is indexed by the representatives
+ * of the operator's own (source) basis, y by those of a target basis.  With the projector P = |G|^-1 sum_g conj(chi(g)) U_g, the
+ * basis vectors |r> = P|r> / n(r), n(r)^2 = |G|^-1 sum_{g in Stab(r)} chi(g), and A|r> = sum_j c_j |b_j>,
+ *     <r'|_2 A |r>_1 = sum_{j : rep(b_j) = r'} c_j conj(chi2(g0j)) n2(r') / n1(r),     g0j b_j = r'
+ * provided A is COVARIANT: U_g A U_g^-1 = chi2(g) conj(chi1(g)) A for every generator g and for the spin inversion (then
+ * P2 A = A P1).  The kernel (k_cross_pull, csrc/k_cross.hip) evaluates the pull form -- one target row per thread, the adjoint A+
+ * applied to the target representative, every image projected into the source basis with the general orbit loop and looked up
+ * there -- so y is assigned without atomics.  DESIGN.md section 6b.
+ *
+ * Scope: spin-1/2 bases, projected or not, on both sides, with the SAME generator permutations in the same order (any sectors,
+ * any inversion characters, any Hamming weights), and the unprojected fermionic bases of ls_hs_create_basis (spinless N -> N',
+ * spinful (N, N_up) -> (N', N_up'); the Jordan-Wigner signs are in the terms' sign masks).  One partition.  Refused with their own
+ * messages: projected fermionic bases on either side (permutation signs in the projection; a follow-up next to k_fermi), bases of
+ * different number_sites, particle types or generators, spin inversion on one side only. */
+typedef struct ls_amd_cross ls_amd_cross;
+/* A new operator on the same basis whose terms are the conjugate transpose: (v, m, r, x, s) becomes
+ * (conj(v) (-1)^popcount(x & s), m, r ^ (x & m), x, s).  Host only (no device).  Release with ls_hs_destroy_operator.  NULL on
+ * error. */
+ls_hs_operator *ls_amd_operator_adjoint(ls_hs_operator const *op);
+/* 0 when `op` (on its own basis, the source) maps the source sector into the sector of `target_basis`, i.e. when it is covariant
+ * as above; -1 otherwise, with a message that names the offending generator ("generator g" in the order the bases were created
+ * with, or "spin inversion").  Exact and host only: the term tables are written out on their full supports m | x | s (sigma^z as a
+ * sign mask and as two projector terms are the same operator), transformed by every generator -- a permutation relabels the
+ * sites of m, r, x, s as (g.w)[i] = w[g[i]]; the inversion sends r to r ^ m and multiplies v by (-1)^popcount(s) -- and compared
+ * to 1e-12 max|v|.  No state is sampled.  Hamming weights and particle numbers are NOT examined (ls_amd_cross_check reports an
+ * image outside the source basis at run time).  The refusals listed under Scope above come back as -1 with their own messages. */
+int ls_amd_operator_maps_sector(ls_hs_operator const *op, ls_hs_basis const *target_basis);
+/* The plan of y = A x: `op_on_source` is A on the source basis, d_src_reps / d_dst_reps the ascending representatives of the
+ * source / target basis in HBM (borrowed until ls_amd_cross_destroy).  Creation runs ls_amd_operator_maps_sector, builds the
+ * adjoint's device term groups (terms without a flip are a group like any other: row i of the target is not column i of the
+ * source), the norms of the target rows, and the source look-up: the static index table of a projected source (shared with
+ * matvec plans over the same array), the closed-form index of a complete unprojected one (identity, combinadic, product) or a
+ * searched index.  LS_AMD_F64 needs a real operator and +-1 characters on both bases; anything else must be LS_AMD_C128. */
+int ls_amd_cross_create(ls_amd_cross **out, ls_hs_operator const *op_on_source, ls_hs_basis const *target_basis, ls_amd_dtype dtype,
+                        uint64_t const *d_src_reps, int64_t n_src, uint64_t const *d_dst_reps, int64_t n_dst, void *stream);
+/* y <- A x (d_x: n_src, d_y: n_dst elements of the plan's dtype); y is ASSIGNED.  Asynchronous on `stream`. */
+int ls_amd_cross_apply(ls_amd_cross *plan, void const *d_x, void *d_y, void *stream);
+/* synchronises `stream` and reports the device error flag: -1 ("... not in the source basis") when an image of A+ with non-zero
+ * source norm was not found among the source's representatives -- A leaves the target's weight sector, say; y is then not A x.
+ * The run-time counterpart of ls_amd_plan_check's "invalid index". */
+int ls_amd_cross_check(ls_amd_cross *plan, void *stream);
+char const *ls_amd_cross_kernel_name(ls_amd_cross const *plan); /* "k_cross_pull" */
+/* the (target row, flip mask) pairs that contribute: a coefficient of A+ above the rounding residue of cancelling terms
+ * (1e-13 sum |v|) whose image has non-zero norm in the source sector */
+int64_t ls_amd_cross_nnz(ls_amd_cross const *plan);
+void ls_amd_cross_destroy(ls_amd_cross *plan);
+
 /* test hooks: evaluate compiled host-side tables on the CPU (no device work) ------------------ */
 int ls_amd_basis_group_order(ls_hs_basis const *basis);
 /* 1 when the basis is a projected fermionic basis (spinless, or spinful with fixed number_up), i.e.
