@@ -154,6 +154,7 @@ def load():
         "ls_amd_plan_timing_report": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
         "ls_amd_operator_adjoint": (op, [op]),
         "ls_amd_operator_maps_sector": (C.c_int, [op, bp]),
+        "ls_amd_operator_maps_sector_signed": (C.c_int, [op, bp]),
         "ls_amd_cross_create": (C.c_int, [C.POINTER(vp), op, bp, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
         "ls_amd_cross_apply": (C.c_int, [vp, vp, vp, vp]),
         "ls_amd_cross_check": (C.c_int, [vp, vp]),

@@ -205,12 +205,16 @@ class Operator:
         out.basis.spec = self.basis.spec
         return out
 
-    def mapsSector(self, target_basis: Basis, explain: bool = False) -> bool:
+    def mapsSector(self, target_basis: Basis, explain: bool = False, signs: bool = False) -> bool:
         """whether this operator maps its own (source) sector into the sector of target_basis (ls_amd_operator_maps_sector: the
         exact covariance check U_g A U_g^-1 = chi2(g) conj(chi1(g)) A on the term tables; host only).  explain=True raises LsAmdError
-        with the reason -- the offending generator, or why the two bases cannot be paired -- instead of returning False."""
+        with the reason -- the offending generator, or why the two bases cannot be paired -- instead of returning False.
+        signs=True runs the rule that CrossSectorPlan runs (ls_amd_operator_maps_sector_signed): the same answer for bases without
+        permutation signs, and for projected fermionic bases -- which the plain rule refuses -- the covariance under
+        U_g|a> = sign(g, a)|g.a>, with the Jordan-Wigner strings of the terms absorbed (c+_k, c_k, n_q, S^z_q, pair operators
+        between momentum, point-group and spin-flip sectors; particle numbers are not examined)."""
         L = _lib.load()
-        rc = L.ls_amd_operator_maps_sector(self.payload, target_basis.payload)
+        rc = (L.ls_amd_operator_maps_sector_signed if signs else L.ls_amd_operator_maps_sector)(self.payload, target_basis.payload)
         if rc != 0 and explain:
             raise LsAmdError(L.ls_amd_last_error().decode("utf-8", "replace"))
         _lib.raise_pending_halt()
@@ -618,7 +622,10 @@ class CrossSectorPlan:
     """ls_amd_cross: y = A x between two symmetry sectors (include/ls_amd.h).  operator: A on the SOURCE basis; source_reps /
     target_reps: the ascending representatives of the source basis / of target_basis (device tensors, one partition); x lives on
     the source rows, y on the target rows.  Creation checks that A maps the source sector into the target's (LsAmdError names the
-    offending generator otherwise); float64 needs a real operator and +-1 characters on both bases."""
+    offending generator otherwise; the check is Operator.mapsSector(target_basis, signs=True)); float64 needs a real operator and
+    +-1 characters on both bases.  Spin bases, unprojected fermionic bases, and projected fermionic bases (spinless, spinful with
+    spin_flip; up to 60 modes) whose generators are the same on both sides: there the kernel is "k_cross_pull_fermi", which
+    projects every image with the permutation signs (always +-1, so they never stand in the way of float64)."""
 
     def __init__(self, operator: Operator, source_reps, target_basis: Basis, target_reps, dtype):
         torch = _torch()

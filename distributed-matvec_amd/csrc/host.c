@@ -5079,11 +5079,12 @@ static double canon_defect(canon_term const *c, int64_t n, int const *p, int L, 
     return worst;
 }
 
-static int cross_preconditions(ls_hs_basis const *a, ls_hs_basis const *b) {
+/* signs != 0: projected fermionic bases are admitted (the caller runs the signed covariance rule) */
+static int cross_preconditions(ls_hs_basis const *a, ls_hs_basis const *b, int signs) {
     struct ls_amd_basis_ext const *ea = (struct ls_amd_basis_ext const *)reg_get(a), *eb = (struct ls_amd_basis_ext const *)reg_get(b);
     if (!ea || !eb) return set_error("cross-sector: unknown basis (ls_amd_adopt_basis first)");
     if (a->particle_type != b->particle_type) return set_error("cross-sector: the bases have different particle types (%d and %d)", a->particle_type, b->particle_type);
-    if (ea->fermi || eb->fermi)
+    if (!signs && (ea->fermi || eb->fermi))
         return set_error("cross-sector: projected fermionic bases are not supported (permutation signs in the projection; follow-up: a "
                          "sign-aware cross kernel next to k_fermi) -- use the unprojected (N, N_up) bases");
     if (a->number_sites != b->number_sites || ea->nbits != eb->nbits)
@@ -5102,7 +5103,7 @@ int ls_amd_operator_maps_sector(ls_hs_operator const *op, ls_hs_basis const *tar
     if (!op || !target) return set_error("ls_amd_operator_maps_sector: NULL %s", !op ? "operator" : "target basis");
     if (!reg_get(op)) return set_error("ls_amd_operator_maps_sector: unknown operator (ls_amd_adopt_operator first)");
     ls_hs_basis const *src = op->basis;
-    if (cross_preconditions(src, target) != 0) return -1;
+    if (cross_preconditions(src, target, 0) != 0) return -1;
     struct ls_amd_basis_ext const *es = BEXT(src), *et = BEXT(target);
     int const L = es->nbits;
     if (es->n_generators == 0 && src->spin_inversion == 0) return 0; /* no group: nothing to be covariant under */
@@ -5133,6 +5134,144 @@ int ls_amd_operator_maps_sector(ls_hs_operator const *op, ls_hs_basis const *tar
                            "%d) it must pick up the factor %d, and misses that by %.3g", src->spin_inversion, target->spin_inversion, (int)f, defect);
     }
     free(c);
+    return rc;
+}
+
+/* ---- the signed covariance rule: projected fermionic bases, U_g|a> = sign(g, a)|g.a> ----
+ * sign(g, a) = (-1)^Q(a), Q(a) = the occupied pairs j < i with j in tab[i] (tab: the sign table of g, as fermi_sign_table builds
+ * it): a GF(2) quadratic form.  For a raw term (v, m, r, x, s) with x inside m, sign(g, a) sign(g, a ^ x) is affine in the bits of a
+ * outside x -- a pair with exactly one mode i in x contributes the other mode's bit: the sign mask lin = XOR_{i in x} nb(i) & ~x,
+ * nb(i) = tab[i] | {k > i : i in tab[k]} -- and constant on the bits inside, which r fixes: a pair inside x contributes
+ * r'_i r'_j + r_i r_j with r' = r ^ x.  So conjugation stays inside the term format,
+ *     U_g A_t U_g^-1 = ((-1)^c v, g.m, g.r, g.x, g.(s ^ lin)).
+ * A fermionic term drags a Jordan-Wigner string over up to 63 modes outside m, which canon_expand cannot write out; but the string
+ * of a flip mask x is J(x) = XOR_{j in x} ((1 << j) - 1) whatever the monomial, so only free = (s ^ J(x)) & ~m is expanded --
+ * entries (u = m | free, pattern, x), the sign of the pattern folded into the coefficient -- and the residual sign
+ * (-1)^popcount(a & J(x) & ~u) is a function of the key (u, x): two entries with one key are the same operator. */
+static void perm_sign_table(int const *p, int L, uint64_t *tab, uint64_t *nb) {
+    int q[64];
+    for (int i = 0; i < L; ++i) q[p[i]] = i;
+    for (int i = 0; i < L; ++i) {
+        tab[i] = 0;
+        for (int j = 0; j < i; ++j)
+            if (q[j] > q[i]) tab[i] |= 1ULL << j;
+    }
+    for (int i = 0; i < L; ++i) {
+        nb[i] = tab[i];
+        for (int k = i + 1; k < L; ++k)
+            if ((tab[k] >> i) & 1ULL) nb[i] |= 1ULL << k;
+    }
+}
+static uint64_t jw_string(uint64_t x) { /* bit k: the parity of the modes of x above k */
+    uint64_t out = 0;
+    for (uint64_t w = x; w != 0; w &= w - 1) out ^= (1ULL << __builtin_ctzll(w)) - 1;
+    return out;
+}
+/* U_g t U_g^-1 of one raw term with t.x inside t.m */
+static raw_term signed_conjugate(raw_term t, int const *p, int L, uint64_t const *tab, uint64_t const *nb) {
+    uint64_t lin = 0;
+    uint64_t const r0 = t.r & t.x, r1 = r0 ^ t.x;
+    int c = 0;
+    for (uint64_t w = t.x; w != 0; w &= w - 1) {
+        int const i = __builtin_ctzll(w);
+        lin ^= nb[i] & ~t.x;
+        if ((r0 >> i) & 1ULL) c ^= __builtin_popcountll(tab[i] & r0) & 1;
+        if ((r1 >> i) & 1ULL) c ^= __builtin_popcountll(tab[i] & r1) & 1;
+    }
+    raw_term out = t;
+    if (c) { out.re = -out.re; out.im = -out.im; }
+    out.m = permute_mask(p, L, t.m); out.r = permute_mask(p, L, t.r); out.x = permute_mask(p, L, t.x);
+    out.s = permute_mask(p, L, t.s ^ lin);
+    return out;
+}
+/* the canonical entries of n raw terms; -1 - k when term k keeps more than CANON_MAX_FREE sign bits beside its Jordan-Wigner string */
+static int64_t signed_expand(raw_term const *t, int n, canon_term **out) {
+    int64_t total = 0;
+    *out = NULL;
+    for (int k = 0; k < n; ++k) {
+        int const nf = __builtin_popcountll((t[k].s ^ jw_string(t[k].x)) & ~t[k].m);
+        if (nf > CANON_MAX_FREE) return -1 - (int64_t)k;
+        total += (int64_t)1 << nf;
+    }
+    canon_term *c = (canon_term *)malloc(sizeof(canon_term) * (size_t)(total > 0 ? total : 1));
+    int64_t w = 0;
+    for (int k = 0; k < n; ++k) {
+        uint64_t const fr = (t[k].s ^ jw_string(t[k].x)) & ~t[k].m;
+        int const nf = __builtin_popcountll(fr);
+        for (uint64_t pat = 0; pat < (1ULL << nf); ++pat) {
+            uint64_t const a = t[k].r | deposit_bits(pat, fr);
+            double const sg = (__builtin_popcountll(a & t[k].s) & 1) ? -1.0 : 1.0;
+            canon_term e = {t[k].m | fr, a, t[k].x, sg * t[k].re, sg * t[k].im};
+            c[w++] = e;
+        }
+    }
+    *out = c;
+    return total;
+}
+static int not_fermionic(raw_term const *t) {
+    return set_error("ls_amd_operator_maps_sector_signed: a term is not a fermionic operator: beside the Jordan-Wigner string of its "
+                     "flip mask (x = 0x%llx) its sign mask (s = 0x%llx) holds more than %d modes outside its projector mask (m = 0x%llx)",
+                     (unsigned long long)t->x, (unsigned long long)t->s, CANON_MAX_FREE, (unsigned long long)t->m);
+}
+
+int ls_amd_operator_maps_sector_signed(ls_hs_operator const *op, ls_hs_basis const *target) {
+    if (!op || !target) return set_error("ls_amd_operator_maps_sector_signed: NULL %s", !op ? "operator" : "target basis");
+    if (!reg_get(op)) return set_error("ls_amd_operator_maps_sector_signed: unknown operator (ls_amd_adopt_operator first)");
+    ls_hs_basis const *src = op->basis;
+    struct ls_amd_basis_ext const *es = (struct ls_amd_basis_ext const *)reg_get(src), *et = (struct ls_amd_basis_ext const *)reg_get(target);
+    if (!es || !et || !(es->fermi || et->fermi)) return ls_amd_operator_maps_sector(op, target); /* no permutation signs: the plain rule */
+    if (cross_preconditions(src, target, 1) != 0) return -1;
+    int const L = es->nbits;
+    raw_term *t = NULL, *tg = NULL;
+    canon_term *c = NULL, *both = NULL;
+    int const n = operator_raw_terms(op, &t);
+    int rc = 0;
+    for (int k = 0; k < n && rc == 0; ++k)
+        if (t[k].x & ~t[k].m)
+            rc = set_error("ls_amd_operator_maps_sector_signed: a term flips modes outside its projector mask (x = 0x%llx is not inside "
+                           "m = 0x%llx): not a product of creation and annihilation operators", (unsigned long long)t[k].x, (unsigned long long)t[k].m);
+    int64_t nc = 0;
+    if (rc == 0 && (nc = signed_expand(t, n, &c)) < 0) rc = not_fermionic(&t[-1 - nc]);
+    if (rc == 0) {
+        nc = canon_merge(c, nc);
+        double vmax = 0.0;
+        for (int64_t i = 0; i < nc; ++i) { double const a = fabs(c[i].re) > fabs(c[i].im) ? fabs(c[i].re) : fabs(c[i].im); if (a > vmax) vmax = a; }
+        double const tol = 1e-12 * vmax;
+        tg = (raw_term *)malloc(sizeof(raw_term) * (size_t)(n > 0 ? n : 1));
+        uint64_t tab[64], nb[64];
+        for (int g = 0; g < es->n_generators && rc == 0; ++g) {
+            int const *p = es->gen_perms + (size_t)g * L;
+            int const ord = perm_order(p, L);
+            perm_sign_table(p, L, tab, nb);
+            for (int k = 0; k < n; ++k) tg[k] = signed_conjugate(t[k], p, L, tab, nb);
+            canon_term *cg = NULL;
+            int64_t const ng = signed_expand(tg, n, &cg);
+            if (ng < 0) { rc = not_fermionic(&t[-1 - ng]); break; } /* (shown by the image only: the term as it was given) */
+            /* g.A - f A, f = chi2(g) conj(chi1(g)) = exp(-2 pi i (sector2 - sector1) / order) */
+            double const phi = -2.0 * M_PI * (double)(et->gen_sectors[g] - es->gen_sectors[g]) / (double)ord;
+            double const f_re = cos(phi), f_im = sin(phi);
+            both = (canon_term *)realloc(both, sizeof(canon_term) * (size_t)(ng + nc > 0 ? ng + nc : 1));
+            memcpy(both, cg, sizeof(canon_term) * (size_t)ng);
+            free(cg);
+            for (int64_t i = 0; i < nc; ++i) {
+                canon_term m = c[i];
+                m.re = -(f_re * c[i].re - f_im * c[i].im);
+                m.im = -(f_re * c[i].im + f_im * c[i].re);
+                both[ng + i] = m;
+            }
+            int64_t const k = canon_merge(both, ng + nc);
+            double defect = 0.0;
+            for (int64_t i = 0; i < k; ++i) {
+                double const d = fabs(both[i].re) > fabs(both[i].im) ? fabs(both[i].re) : fabs(both[i].im);
+                if (d > defect) defect = d;
+            }
+            if (defect > tol)
+                rc = set_error("the operator does not map the source sector into the target sector: under generator %d (sector %d -> %d of "
+                               "order %d) it must pick up the factor exp(-2 pi i %d / %d), and misses that by %.3g",
+                               g, es->gen_sectors[g], et->gen_sectors[g], ord, et->gen_sectors[g] - es->gen_sectors[g], ord, defect);
+        }
+    }
+    free(t); free(tg); free(c); free(both);
     return rc;
 }
 
@@ -5225,6 +5364,9 @@ static int cross_setup(ls_amd_cross *cx, ls_hs_operator const *op, ls_hs_basis c
     cx->six.dir_sites = L;
     cx->six.dir_weight = es->hamming_weight;
     if (cx->n_src >= 0xffffffffLL) return set_error("cross-sector: source bases with >= 2^32 - 1 states are not supported");
+    if (cx->src.fermi && L > 60)
+        return set_error("cross-sector: projected fermionic bases of more than 60 modes are not supported (%d modes: the static index table "
+                         "of the source does not fit, as for their matvec plans)", L);
     if (cx->src.proj != LSK_PROJ_NONE) {
         if (cx->n_src > 0 && ls_amd_internal_gtab_acquire(&cx->gtab, L, cx->d_src_reps, cx->n_src, NULL, 1, stream) != 0) return -1;
     } else if (cx->n_src > 0) {
@@ -5282,7 +5424,7 @@ int ls_amd_cross_create(ls_amd_cross **out, ls_hs_operator const *op, ls_hs_basi
     if (n_src < 0 || n_dst < 0 || (n_src > 0 && !d_src_reps) || (n_dst > 0 && !d_dst_reps))
         return set_error("ls_amd_cross_create: NULL representatives or a negative count");
     if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("ls_amd_cross_create: unknown dtype %d", (int)dtype);
-    if (ls_amd_operator_maps_sector(op, target) != 0) return -1;
+    if (ls_amd_operator_maps_sector_signed(op, target) != 0) return -1; /* (the plain rule where no basis has permutation signs) */
     ls_hs_operator *adj = ls_amd_operator_adjoint(op);
     if (!adj) return -1;
     if (dtype == LS_AMD_F64 && !(OEXT(adj)->is_real && cross_every_char_pm1(op->basis) && cross_every_char_pm1(target))) {
@@ -5327,7 +5469,7 @@ int ls_amd_cross_check(ls_amd_cross *cx, void *stream) {
 
 char const *ls_amd_cross_kernel_name(ls_amd_cross const *cx) {
     if (!cx) { set_error("ls_amd_cross_kernel_name: NULL plan"); return NULL; }
-    return lsk_cross_kernel_name();
+    return cx->src.fermi ? lsk_cross_fermi_kernel_name() : lsk_cross_kernel_name();
 }
 int64_t ls_amd_cross_nnz(ls_amd_cross const *cx) {
     if (!cx) { set_error("ls_amd_cross_nnz: NULL plan"); return -1; }

@@ -1,0 +1,165 @@
+// k_cross_t.hpp -- the cross-sector pull kernel k_cross_pull as a template header: k_cross.hip instantiates
+// it for the bases without permutation signs (FERMI = false), k_cross_fermi.hip for the projected fermionic ones (FERMI = true; the
+// plans call that family "k_cross_pull_fermi").  Moved out of k_cross.hip unchanged (the machine code of the 10 spin kinds is the
+// same, instruction for instruction); it gained ONE compile-time switch, FERMI, which makes stage B1 project a packet with the signed characters
+// chi(g) sign(g, a) of lsk_fermi.hpp (fermi_state_info_w) instead of state_info_w.  Nothing else in the formula changes: chr, chi
+// and stab then carry sign(g0, beta) and the signed stabiliser sum, and the zero-norm test drops the orbits whose signed sum
+// vanishes (which happens in ANY fermionic sector).  The branch is discarded at compile time by the spin instantiations.
+#pragma once
+#include "lsk_dev.hpp"
+#include "lsk_fermi.hpp"
+
+constexpr int kGCCross = 4;                    // flip-mask groups per pass
+constexpr int kCapCross = kBlock * kGCCross;   // packets a pass of one tile can generate
+
+// index of state s in an UNPROJECTED source basis, or -1 (the closed forms check membership themselves: the adjoint may leave the
+// source's weight sector, which is an error the caller reads back, never an out-of-range load)
+__device__ __forceinline__ int64_t cross_index(lsk_index const &ix, uint64_t s) {
+    if (ix.kind == LSK_INDEX_IDENTITY) return s < (uint64_t)ix.count ? (int64_t)s : -1;
+    if (ix.kind == LSK_INDEX_COMBINADIC) {
+        if (__popcll(s) != ix.dir_weight || (ix.dir_sites < 64 && (s >> ix.dir_sites) != 0)) return -1;
+        const int64_t r = rank_combinadic(s, ix.binom);
+        return r < ix.count ? r : -1;
+    }
+    if (ix.kind == LSK_INDEX_PRODUCT) {
+        const int64_t r = product_index(ix, s, ix.binom);
+        return r < ix.count ? r : -1;
+    }
+    if (ix.count <= 0 || (ix.dir_sites < 64 && (s >> ix.dir_sites) != 0)) return -1; // (SEARCH: the prefix table covers dir_sites bits)
+    return search_index(ix, s);
+}
+
+template <typename W, bool PM1, bool CPLX, bool REAL, bool FERMI>
+__global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group const *__restrict__ groups,
+                                                       lsk_term const *__restrict__ terms, lsk_basis sbs,
+                                                       lsk_group_elem const *__restrict__ elems, lsk_index six, lsk_gtab gt,
+                                                       int64_t n_dst, uint64_t const *__restrict__ dst_reps,
+                                                       double const *__restrict__ dst_norms, double const *__restrict__ x,
+                                                       double *__restrict__ y, double tiny, unsigned long long *count, int *err) {
+    constexpr bool RC = REAL && PM1; // the coefficient stays real: real terms and +-1 source characters
+    __shared__ uint64_t s_beta[kCapCross];
+    __shared__ double s_coef[kCapCross * (RC ? 1 : 2)];
+    __shared__ uint16_t s_row[kCapCross];
+    __shared__ double s_acc[kBlock * (CPLX ? 2 : 1)];
+    __shared__ int s_n;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const bool project = sbs.proj != LSK_PROJ_NONE;
+    const bool table = gt.entries != nullptr;
+    for (int64_t t0 = (int64_t)blockIdx.x * kBlock; t0 < n_dst; t0 += (int64_t)gridDim.x * kBlock) {
+        const int64_t i = t0 + tid;
+        const bool valid = i < n_dst;
+        uint64_t a = 0;
+        double inv_na = 0.0;
+        if (valid) {
+            a = dst_reps[i];
+            const double na = dst_norms[i];
+            inv_na = na > 0.0 ? 1.0 / na : 0.0;
+        }
+        if (CPLX) { s_acc[2 * tid] = 0.0; s_acc[2 * tid + 1] = 0.0; } else s_acc[tid] = 0.0;
+        unsigned long long found = 0;
+        for (int g0 = 0; g0 < n_groups; g0 += kGCCross) {
+            if (tid == 0) s_n = 0;
+            __syncthreads();
+            // ---- stage A: the adjoint's groups of every row -> packets (state, conj(c) / n2(r'), row) ------------------
+            const int g1 = min(g0 + kGCCross, n_groups);
+            for (int g = g0; g < g1; ++g) {
+                lsk_group const G = groups[g];
+                double cr = 0.0, ci = 0.0;
+                if (valid) term_sum<REAL>(terms, G.begin, G.end, a, cr, ci);
+                // (tiny: the rounding residue of terms that cancel -- sum_j e^{-iqj} sigma^z_j on a state of shorter period -- is no packet)
+                const bool act = valid && (fabs(cr) > tiny || (!REAL && fabs(ci) > tiny));
+                const unsigned long long ball = __ballot(act);
+                int base = 0;
+                if (lane == 0 && ball) base = atomicAdd(&s_n, __popcll(ball));
+                base = __shfl(base, 0);
+                if (act) {
+                    const int slot = base + __popcll(ball & ((1ULL << lane) - 1));
+                    s_beta[slot] = a ^ G.x;
+                    s_row[slot] = (uint16_t)tid;
+                    if (RC) s_coef[slot] = cr * inv_na;
+                    else { s_coef[2 * slot] = cr * inv_na; s_coef[2 * slot + 1] = -ci * inv_na; }
+                }
+            }
+            __syncthreads();
+            const int n = s_n;
+            // ---- stage B1: project every packet into the SOURCE basis (general K4: minimum, character, stabiliser norm) --
+            if (project) {
+                for (int e = tid; e < n; e += kBlock) {
+                    W rep; double chr, chi, stab;
+                    if constexpr (FERMI) fermi_state_info_w<W, PM1>(sbs, elems, (W)s_beta[e], rep, chr, chi, stab);
+                    else state_info_w<W, PM1>(sbs, elems, (W)s_beta[e], rep, chr, chi, stab);
+                    const double n2 = stab * sbs.inv_order;
+                    if (!(n2 > 1e-12)) { s_row[e] = 0xffff; continue; } // zero norm in the source sector: contributes nothing
+                    const double nb = sqrt(n2);
+                    s_beta[e] = (uint64_t)rep;
+                    if (RC) s_coef[e] = s_coef[e] * chr * nb;
+                    else { // times chi1(g0) = conj(chr, chi), times n1(rep)
+                        const double hr = s_coef[2 * e], hi = s_coef[2 * e + 1];
+                        s_coef[2 * e] = (hr * chr + hi * chi) * nb;
+                        s_coef[2 * e + 1] = (hi * chr - hr * chi) * nb;
+                    }
+                }
+            }
+            // ---- stage B2: representative -> source index, then the gathers (a thread's loads issued before any is used) --
+            {
+                uint64_t key[kGCCross], bucket[kGCCross];
+                uint32_t tag[kGCCross];
+                ulonglong2 first[kGCCross];
+                int64_t idx[kGCCross];
+                bool live[kGCCross];
+#pragma unroll
+                for (int k = 0; k < kGCCross; ++k) {
+                    const int e = tid + k * kBlock;
+                    live[k] = e < n && s_row[e] != 0xffff;
+                    key[k] = live[k] ? s_beta[e] : 0;
+                    idx[k] = -1;
+                    bucket[k] = 0; tag[k] = 0;
+                    first[k] = make_ulonglong2(kGtEmpty, kGtEmpty);
+                    if (live[k] && table && !(gt.L < 64 && (key[k] >> gt.L) != 0)) {
+                        gt_split(gt, key[k], bucket[k], tag[k]);
+                        first[k] = *(ulonglong2 const *)(gt.entries + 2 * bucket[k]);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < kGCCross; ++k) {
+                    if (!live[k]) continue;
+                    if (table) {
+                        const uint32_t pay = gt_resolve(gt, gt.entries, bucket[k], tag[k], first[k]);
+                        idx[k] = pay == 0xffffffffu ? -1 : (int64_t)pay;
+                    } else idx[k] = cross_index(six, key[k]);
+                    if (idx[k] < 0 || idx[k] >= six.count) { idx[k] = -1; atomicExch(err, 1); } // an image that is not in the source basis
+                    else ++found;
+                }
+                if (!count) {
+                    double xr[kGCCross], xi[kGCCross];
+#pragma unroll
+                    for (int k = 0; k < kGCCross; ++k) {
+                        xr[k] = 0.0; xi[k] = 0.0;
+                        if (idx[k] >= 0) {
+                            if (CPLX) { xr[k] = x[2 * idx[k]]; xi[k] = x[2 * idx[k] + 1]; } else xr[k] = x[idx[k]];
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < kGCCross; ++k) {
+                        if (idx[k] < 0) continue;
+                        const int e = tid + k * kBlock;
+                        double hr, hi = 0.0;
+                        if (RC) hr = s_coef[e]; else { hr = s_coef[2 * e]; hi = s_coef[2 * e + 1]; }
+                        const int r = s_row[e];
+                        if (CPLX) {
+                            atomicAdd(&s_acc[2 * r], hr * xr[k] - hi * xi[k]);
+                            atomicAdd(&s_acc[2 * r + 1], hr * xi[k] + hi * xr[k]);
+                        } else atomicAdd(&s_acc[r], hr * xr[k]);
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (count) { if (found) atomicAdd(count, found); }
+        else if (valid) {
+            if (CPLX) { y[2 * i] = s_acc[2 * tid]; y[2 * i + 1] = s_acc[2 * tid + 1]; } else y[i] = s_acc[tid];
+        }
+        __syncthreads();
+    }
+}

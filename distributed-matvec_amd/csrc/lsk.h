@@ -555,6 +555,12 @@ char const *lsk_cross_kernel_name(void);
 int lsk_cross_pull(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
                    lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, void const *x, void *y,
                    double tiny, unsigned long long *d_count, int *d_err, void *stream);
+/* the same for a projected fermionic source (k_cross_fermi.hip, k_cross_pull_fermi: the packets are projected with the signed
+ * characters chi(g) sign(g, a) of lsk_fermi.hpp); lsk_cross_pull hands src.fermi here.  Always the static index table. */
+char const *lsk_cross_fermi_kernel_name(void);
+int lsk_cross_fermi_pull(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
+                         lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, void const *x, void *y,
+                         double tiny, unsigned long long *d_count, int *d_err, void *stream);
 
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */

@@ -287,7 +287,7 @@ def _spectral_function_cross(config, operator, target, state, num_moments, energ
         raise ValueError("operator: an api.Operator (on the source basis) or the index of one of the config's observables")
     dtype = dtype or torch.float64
     tbasis = _target_basis(target)
-    A.mapsSector(tbasis, explain=True)
+    A.mapsSector(tbasis, explain=True, signs=True)
     h_t = api.Operator.fromSpec(tbasis, _config.OperatorSpec(_terms_of(h)))
     if not h_t.isHermitian:
         raise ValueError("kpm: the Hamiltonian is not Hermitian (Chebyshev moments need a real spectrum)")
@@ -332,7 +332,9 @@ def spectral_function(config, operator, state=None, num_moments: int = 256, ener
     (dict or YAML path), or an api.Basis -- e.g. momentum k + q for S^z_q on a ground state of momentum k.  The operator is then
     compiled on (and psi lives in) the config's own basis, the source; v0 = A psi is an api.CrossSectorPlan, and the config's
     `hamiltonian:` is re-compiled on the target basis, where the bounds and the moments are computed; KpmResult.target_state is
-    v0.  Sectors with complex characters need dtype=torch.complex128."""
+    v0.  Sectors with complex characters need dtype=torch.complex128.  Projected fermionic bases are sectors like any other here:
+    c+_k / c_k from an N-particle ground state of momentum k0 into the N +- 1 sector of momentum k0 +- k is the photoemission
+    spectrum A(k, w), n_q and S^z_q give N(q, w) and S^z(q, w)."""
     import torch
 
     if target is not None:

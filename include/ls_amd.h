@@ -459,10 +459,12 @@ int ls_amd_hashed_to_block(int64_t n, uint8_t const *d_masks, int num_locales, i
  * there -- so y is assigned without atomics.  DESIGN.md section 6b.
  *
  * Scope: spin-1/2 bases, projected or not, on both sides, with the SAME generator permutations in the same order (any sectors,
- * any inversion characters, any Hamming weights), and the unprojected fermionic bases of ls_hs_create_basis (spinless N -> N',
- * spinful (N, N_up) -> (N', N_up'); the Jordan-Wigner signs are in the terms' sign masks).  One partition.  Refused with their own
- * messages: projected fermionic bases on either side (permutation signs in the projection; a follow-up next to k_fermi), bases of
- * different number_sites, particle types or generators, spin inversion on one side only. */
+ * any inversion characters, any Hamming weights); the unprojected fermionic bases of ls_hs_create_basis (spinless N -> N',
+ * spinful (N, N_up) -> (N', N_up'); the Jordan-Wigner signs are in the terms' sign masks); and the PROJECTED fermionic bases
+ * (spinless, spinful with spin_flip) with the same generators on both sides, up to 60 modes: their permutation signs enter the
+ * projection of every image (k_cross_pull_fermi, csrc/k_cross_fermi.hip: the same kernel body with fermi_state_info_w) and the
+ * covariance rule (ls_amd_operator_maps_sector_signed).  One partition.  Refused with their own messages: bases of different
+ * number_sites, particle types or generators, spin inversion on one side only, projected fermionic bases above 60 modes. */
 typedef struct ls_amd_cross ls_amd_cross;
 /* A new operator on the same basis whose terms are the conjugate transpose: (v, m, r, x, s) becomes
  * (conj(v) (-1)^popcount(x & s), m, r ^ (x & m), x, s).  Host only (no device).  Release with ls_hs_destroy_operator.  NULL on
@@ -476,8 +478,19 @@ ls_hs_operator *ls_amd_operator_adjoint(ls_hs_operator const *op);
  * to 1e-12 max|v|.  No state is sampled.  Hamming weights and particle numbers are NOT examined (ls_amd_cross_check reports an
  * image outside the source basis at run time).  The refusals listed under Scope above come back as -1 with their own messages. */
 int ls_amd_operator_maps_sector(ls_hs_operator const *op, ls_hs_basis const *target_basis);
+/* The same question with PERMUTATION SIGNS: for bases without them (spins, unprojected fermions) exactly
+ * ls_amd_operator_maps_sector; for projected fermionic bases (spinless, or spinful over their 2 L modes, where the lifted site
+ * generators and the half swap of spin_flip are the generators) the covariance under U_g|a> = sign(g, a)|g.a>.  Both bases must
+ * have the same particle type, number_sites and generator permutations in the same order; sectors, particle numbers and
+ * number_up may differ; at most 64 modes.  Exact and host only, no state is sampled: a term (v, m, r, x, s) with x inside m is
+ * conjugated inside the term format -- ((-1)^c v, g.m, g.r, g.x, g.(s ^ lin)), lin and c from the sign table of g (host.c) -- and
+ * compared in a canonical form that absorbs the Jordan-Wigner string J(x) = XOR_{j in x} ((1 << j) - 1) of its flip mask, so that
+ * c+_k over 64 modes costs one entry per site.  -1 with a message that names the generator as above, or "flips modes outside its
+ * projector mask" (x not inside m), or "not a fermionic operator" (a sign mask that differs from J(x) on more than 12 modes
+ * outside m).  ls_amd_cross_create runs this rule. */
+int ls_amd_operator_maps_sector_signed(ls_hs_operator const *op, ls_hs_basis const *target_basis);
 /* The plan of y = A x: `op_on_source` is A on the source basis, d_src_reps / d_dst_reps the ascending representatives of the
- * source / target basis in HBM (borrowed until ls_amd_cross_destroy).  Creation runs ls_amd_operator_maps_sector, builds the
+ * source / target basis in HBM (borrowed until ls_amd_cross_destroy).  Creation runs ls_amd_operator_maps_sector_signed, builds the
  * adjoint's device term groups (terms without a flip are a group like any other: row i of the target is not column i of the
  * source), the norms of the target rows, and the source look-up: the static index table of a projected source (shared with
  * matvec plans over the same array), the closed-form index of a complete unprojected one (identity, combinadic, product) or a
@@ -490,7 +503,7 @@ int ls_amd_cross_apply(ls_amd_cross *plan, void const *d_x, void *d_y, void *str
  * source norm was not found among the source's representatives -- A leaves the target's weight sector, say; y is then not A x.
  * The run-time counterpart of ls_amd_plan_check's "invalid index". */
 int ls_amd_cross_check(ls_amd_cross *plan, void *stream);
-char const *ls_amd_cross_kernel_name(ls_amd_cross const *plan); /* "k_cross_pull" */
+char const *ls_amd_cross_kernel_name(ls_amd_cross const *plan); /* "k_cross_pull"; "k_cross_pull_fermi" for projected fermionic bases */
 /* the (target row, flip mask) pairs that contribute: a coefficient of A+ above the rounding residue of cancelling terms
  * (1e-13 sum |v|) whose image has non-zero norm in the source sector */
 int64_t ls_amd_cross_nnz(ls_amd_cross const *plan);
