@@ -5475,3 +5475,186 @@ int64_t ls_amd_cross_nnz(ls_amd_cross const *cx) {
     if (!cx) { set_error("ls_amd_cross_nnz: NULL plan"); return -1; }
     return cx->nnz;
 }
+
+/* ============================================================================================ */
+/* sector-state expansion (include/ls_amd.h: ls_amd_expand; csrc/k_expand.hip)     */
+/* ============================================================================================ */
+typedef struct expand_layout {
+    int L, weight, n_a, n_b, split, nb;
+    int na[LSK_EXPAND_MAX_NA];
+    int64_t rows[LSK_EXPAND_MAX_NA], cols[LSK_EXPAND_MAX_NA], off[LSK_EXPAND_MAX_NA], total;
+} expand_layout;
+
+/* the block table of a bipartition: host only.  The refusals of ls_amd_expand_create that need no device live here. */
+static int expand_layout_of(ls_hs_basis const *basis, uint64_t mask_a, expand_layout *lay) {
+    if (!basis) return set_error("ls_amd_expand: NULL basis");
+    if (basis->particle_type != LS_HS_SPIN)
+        return set_error("ls_amd_expand: fermionic bases are not supported -- the partial trace of fermions needs the mode-ordering signs of "
+                         "moving the modes of the subsystem in front of the others, which the expansion does not carry yet");
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    int const L = e->nbits, w = e->hamming_weight;
+    uint64_t const sites = L >= 64 ? ~0ULL : ((1ULL << L) - 1);
+    if (mask_a & ~sites) return set_error("ls_amd_expand: the subsystem mask 0x%llx has bits outside the %d sites", (unsigned long long)mask_a, L);
+    if (w >= LSK_BINOM_K) return set_error("ls_amd_expand: Hamming weight %d is beyond the binomial table (%d)", w, LSK_BINOM_K - 1);
+    memset(lay, 0, sizeof(*lay));
+    lay->L = L; lay->weight = w;
+    lay->n_a = __builtin_popcountll(mask_a);
+    lay->n_b = L - lay->n_a;
+    if (mask_a == (lay->n_a >= 64 ? ~0ULL : ((1ULL << lay->n_a) - 1))) lay->split = LSK_SPLIT_LOW;       /* (the empty A too) */
+    else if (mask_a == (sites & ~((1ULL << lay->n_b) - 1))) lay->split = LSK_SPLIT_HIGH;
+    else lay->split = LSK_SPLIT_GATHER;
+    if (w < 0) {
+        if (L > 40) return set_error("ls_amd_expand: %d sites without a fixed Hamming weight expand to 2^%d elements", L, L);
+        lay->nb = 1;
+        lay->na[0] = -1;
+        lay->rows[0] = (int64_t)1 << lay->n_a; lay->cols[0] = (int64_t)1 << lay->n_b;
+        lay->total = (int64_t)1 << L;
+        return 0;
+    }
+    for (int na = 0; na <= lay->n_a && na <= w; ++na) {
+        uint64_t const r = binom(lay->n_a, na), c = binom(lay->n_b, w - na);
+        if (r == 0 || c == 0) continue; /* empty blocks are omitted */
+        long double const sz = (long double)r * (long double)c;
+        if (sz + (long double)lay->total > 4.0e18L) return set_error("ls_amd_expand: the expansion has more than 2^62 elements");
+        int const i = lay->nb++;
+        lay->na[i] = na; lay->rows[i] = (int64_t)r; lay->cols[i] = (int64_t)c; lay->off[i] = lay->total;
+        lay->total += (int64_t)(r * c);
+    }
+    return 0;
+}
+
+int ls_amd_test_expand_layout(ls_hs_basis const *basis, uint64_t subsystem_mask, int capacity, int *n_a, int64_t *rows, int64_t *cols,
+                              int64_t *offsets, int64_t *total) {
+    expand_layout lay;
+    if (expand_layout_of(basis, subsystem_mask, &lay) != 0) return -1;
+    for (int i = 0; i < lay.nb && i < capacity; ++i) {
+        if (n_a) n_a[i] = lay.na[i];
+        if (rows) rows[i] = lay.rows[i];
+        if (cols) cols[i] = lay.cols[i];
+        if (offsets) offsets[i] = lay.off[i];
+    }
+    if (total) *total = lay.total;
+    return lay.nb;
+}
+
+struct ls_amd_expand {
+    lsk_basis bs;             /* device tables owned by the basis */
+    expand_layout lay;
+    uint64_t mask_a;
+    int pm1;                  /* every character is +-1: f64 allowed */
+    double *d_norms;          /* owned: n(r) of every row */
+    int64_t *d_tab;           /* owned: the block table by n_A (lsk_expand.tab); NULL without a fixed weight */
+    int *d_err;               /* owned */
+    uint64_t const *d_reps;   /* borrowed */
+    uint64_t const *d_binom;
+    int64_t n;
+};
+
+void ls_amd_expand_destroy(ls_amd_expand *ex) {
+    if (!ex) return;
+    if (ex->d_norms) lsk_free(ex->d_norms);
+    if (ex->d_tab) lsk_free(ex->d_tab);
+    if (ex->d_err) lsk_free(ex->d_err);
+    free(ex);
+}
+
+static int expand_setup(ls_amd_expand *ex, ls_hs_basis const *basis, void *stream) {
+    if (basis_device(basis, &ex->bs) != 0) return -1;
+    ex->pm1 = cross_every_char_pm1(basis);
+    if (device_binom(&ex->d_binom) != 0) return -1;
+    void *p = NULL;
+    DEV(lsk_malloc(&p, 4 * sizeof(int)));
+    ex->d_err = (int *)p;
+    DEV(lsk_memset_async(ex->d_err, 0, 4 * sizeof(int), stream));
+    DEV(lsk_malloc(&p, 8 * (size_t)(ex->n > 0 ? ex->n : 1)));
+    ex->d_norms = (double *)p;
+    /* the stabiliser norms, by the routine the matvec and cross-sector plans use (an unprojected basis: the identity alone, n = 1) */
+    DEV(lsk_norms(ex->bs, ex->n, ex->d_reps, ex->d_norms, stream));
+    if (ex->lay.weight >= 0) {
+        int64_t tab[2 * LSK_EXPAND_MAX_NA];
+        for (int i = 0; i < LSK_EXPAND_MAX_NA; ++i) { tab[i] = -1; tab[LSK_EXPAND_MAX_NA + i] = 0; }
+        for (int i = 0; i < ex->lay.nb; ++i) { tab[ex->lay.na[i]] = ex->lay.off[i]; tab[LSK_EXPAND_MAX_NA + ex->lay.na[i]] = ex->lay.cols[i]; }
+        if (upload(&p, tab, sizeof(tab)) != 0) return -1;
+        ex->d_tab = (int64_t *)p;
+    }
+    DEV(lsk_sync(stream));
+    return 0;
+}
+
+int ls_amd_expand_create(ls_amd_expand **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, uint64_t subsystem_mask,
+                         void *stream) {
+    if (out) *out = NULL;
+    if (!out || !basis) return set_error("ls_amd_expand_create: NULL %s", !out ? "handle" : "basis");
+    if (n < 0 || (n > 0 && !d_reps)) return set_error("ls_amd_expand_create: NULL representatives or a negative count");
+    expand_layout lay;
+    if (expand_layout_of(basis, subsystem_mask, &lay) != 0) return -1;
+    ls_amd_expand *ex = (ls_amd_expand *)calloc(1, sizeof(*ex));
+    ex->lay = lay;
+    ex->mask_a = subsystem_mask;
+    ex->d_reps = d_reps; ex->n = n;
+    if (expand_setup(ex, basis, stream) != 0) { ls_amd_expand_destroy(ex); return -1; }
+    *out = ex;
+    return 0;
+}
+
+int ls_amd_expand_num_blocks(ls_amd_expand const *ex) {
+    if (!ex) return set_error("ls_amd_expand_num_blocks: NULL plan");
+    return ex->lay.nb;
+}
+int ls_amd_expand_block(ls_amd_expand const *ex, int i, int *n_a, int64_t *rows, int64_t *cols, int64_t *offset) {
+    if (!ex) return set_error("ls_amd_expand_block: NULL plan");
+    if (i < 0 || i >= ex->lay.nb) return set_error("ls_amd_expand_block: block %d of %d", i, ex->lay.nb);
+    if (n_a) *n_a = ex->lay.na[i];
+    if (rows) *rows = ex->lay.rows[i];
+    if (cols) *cols = ex->lay.cols[i];
+    if (offset) *offset = ex->lay.off[i];
+    return 0;
+}
+int64_t ls_amd_expand_total(ls_amd_expand const *ex) {
+    if (!ex) { set_error("ls_amd_expand_total: NULL plan"); return -1; }
+    return ex->lay.total;
+}
+
+int ls_amd_expand_apply(ls_amd_expand *ex, ls_amd_dtype dtype, void const *d_psi, void *d_out, int first_block, int num_blocks, void *stream) {
+    if (!ex || !d_out || (!d_psi && ex && ex->n > 0)) return set_error("ls_amd_expand_apply: NULL %s", !ex ? "plan" : (!d_out ? "out" : "psi"));
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("ls_amd_expand_apply: unknown dtype %d", (int)dtype);
+    if (dtype == LS_AMD_F64 && !ex->pm1)
+        return set_error("ls_amd_expand_apply: f64 needs +-1 characters (complex characters: use c128)");
+    if (first_block < 0 || num_blocks < 0 || first_block + num_blocks > ex->lay.nb)
+        return set_error("ls_amd_expand_apply: blocks [%d, %d) of %d", first_block, first_block + num_blocks, ex->lay.nb);
+    if (num_blocks == 0) return 0;
+    int const cplx = dtype == LS_AMD_C128, last = first_block + num_blocks - 1;
+    size_t const elt = cplx ? 16 : 8;
+    int64_t const begin = ex->lay.off[first_block], end = ex->lay.off[last] + ex->lay.rows[last] * ex->lay.cols[last];
+    /* the selected blocks lie one after another: one clear, then the scatter assigns what the orbits reach */
+    DEV(lsk_memset_async((char *)d_out + (size_t)begin * elt, 0, (size_t)(end - begin) * elt, stream));
+    if (ex->n == 0) return 0;
+    lsk_expand k;
+    memset(&k, 0, sizeof(k));
+    k.mask_a = ex->mask_a;
+    k.n_a = ex->lay.n_a; k.n_b = ex->lay.n_b;
+    k.split = ex->lay.split;
+    k.na_lo = ex->lay.na[first_block]; k.na_hi = ex->lay.na[last];
+    k.tab = ex->d_tab;
+    k.cols = ex->lay.cols[0];
+    DEV(lsk_expand_push(ex->bs, k, ex->d_binom, cplx, ex->n, ex->d_reps, ex->d_norms, d_psi, d_out, ex->d_err, stream));
+    return 0;
+}
+
+int ls_amd_expand_check(ls_amd_expand *ex, void *stream) {
+    if (!ex) return set_error("ls_amd_expand_check: NULL plan");
+    int flag = 0, zero = 0;
+    DEV(lsk_sync(stream));
+    DEV(lsk_d2h(&flag, ex->d_err, sizeof(int)));
+    if (flag) {
+        DEV(lsk_h2d(ex->d_err, &zero, sizeof(int)));
+        return set_error("sector expansion: a representative or one of its images is not a state of the basis (another Hamming weight, "
+                         "or bits above the %d sites): the array does not belong to this basis", ex->lay.L);
+    }
+    return 0;
+}
+
+char const *ls_amd_expand_kernel_name(ls_amd_expand const *ex) {
+    if (!ex) { set_error("ls_amd_expand_kernel_name: NULL plan"); return NULL; }
+    return lsk_expand_kernel_name();
+}

@@ -562,6 +562,29 @@ int lsk_cross_fermi_pull(int n_groups, lsk_group const *groups, lsk_term const *
                          lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, void const *x, void *y,
                          double tiny, unsigned long long *d_count, int *d_err, void *stream);
 
+/* sector-state expansion (k_expand.hip): the vector psi on the representatives reps[0, n) of a spin basis, scattered over the orbits
+ * of the representatives into the matrix M[a, b] = <a, b|psi> of a bipartition -- the image s = g r of row r
+ * under group element g (and its flipped image under the spin inversion) receives conj(chi(g)) norms[r] psi[r], at
+ *     fixed weight:  tab[n_A] + rank(a) * tab[LSK_EXPAND_MAX_NA + n_A] + rank(b),  n_A = popcount(a)   (one block per n_A)
+ *     otherwise:     a * cols + b                                                                       (one block)
+ * where a / b are the bits of s on the sites of mask_a / on the other sites, compacted in ascending site order.  Plain stores, no
+ * atomics (equal targets receive equal values); `out` is cleared by the caller.  Images with n_A outside [na_lo, na_hi] are
+ * skipped.  *d_err is raised by a row or an image that is not a state of the basis (wrong weight, bits above number_sites);
+ * nothing is stored for it. */
+#define LSK_EXPAND_MAX_NA 65 /* n_A = 0 .. 64 */
+enum { LSK_SPLIT_LOW = 0 /* A = sites [0, n_a) */, LSK_SPLIT_HIGH = 1 /* A = sites [n_b, n_a + n_b) */, LSK_SPLIT_GATHER = 2 };
+typedef struct lsk_expand {
+    uint64_t mask_a;    /* the sites of A */
+    int n_a, n_b;       /* |A|, |B| */
+    int split;          /* LSK_SPLIT_* */
+    int na_lo, na_hi;   /* fixed weight: the blocks to write */
+    int64_t const *tab; /* fixed weight: device [2 * LSK_EXPAND_MAX_NA] -- first element of block n_A (-1: no such block), then its columns */
+    int64_t cols;       /* no fixed weight: 2^n_b */
+} lsk_expand;
+char const *lsk_expand_kernel_name(void);
+int lsk_expand_push(lsk_basis bs, lsk_expand ex, uint64_t const *d_binom, int cplx, int64_t n, uint64_t const *reps, double const *norms,
+                    void const *psi, void *out, int *d_err, void *stream);
+
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */
 int lsk_norms(lsk_basis bs, int64_t n, uint64_t const *reps, double *norms, void *stream);

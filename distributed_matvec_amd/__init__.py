@@ -6,5 +6,7 @@ __path__.insert(0, _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "
 
 from .api import *  # noqa: F401,F403,E402
 from . import api as _api  # noqa: E402
+from .entanglement import *  # noqa: F401,F403,E402
+from . import entanglement as _entanglement  # noqa: E402
 
-__all__ = _api.__all__
+__all__ = list(_api.__all__) + list(_entanglement.__all__)

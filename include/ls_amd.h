@@ -509,6 +509,49 @@ char const *ls_amd_cross_kernel_name(ls_amd_cross const *plan); /* "k_cross_pull
 int64_t ls_amd_cross_nnz(ls_amd_cross const *plan);
 void ls_amd_cross_destroy(ls_amd_cross *plan);
 
+/* sector-state expansion and bipartitions -----------------------------------------------------------------------------------------
+ * A state psi on the representatives of a symmetry sector (an eigenvector, say), expanded to its amplitudes on product states:
+ * with the basis vectors |r~> = P|r> / |P|r>| of the projector above and state_info(s) = (rep, character, norm) of a full-basis state s,
+ *     <s|psi> = conj(character(s)) norm(rep) psi[index(rep)]
+ * evaluated in the push form (k_expand_push, csrc/k_expand.hip): the image s = g r of representative r under group element g --
+ * a permutation, or a permutation times the global flip with character chi(g) inv -- receives conj(chi(g)) n(r) psi[r].  Plain
+ * stores: elements that reach the same s write the same value.  States of zero-norm orbits read 0.  DESIGN.md section 6c.
+ *
+ * Layout.  The subsystem A is the set of sites in `subsystem_mask`, B the other sites; a = the bits of s on the sites of A compacted
+ * in ascending site order, b likewise on B.  On a basis with fixed Hamming weight w the matrix M[a, b] = <a, b|psi> is block-diagonal
+ * in n_A = popcount(a): block n_A has C(|A|, n_A) rows and C(|B|, w - n_A) columns, row-major, row = the combinadic rank of a, column
+ * = that of b (ascending integer order on both sides).  Empty blocks are omitted; the blocks lie one after another in ONE buffer of
+ * ls_amd_expand_total elements, ordered by n_A.  Without a fixed weight there is a single 2^|A| x 2^|B| block, row a, column b
+ * (its n_A is reported as -1).  A = every site gives one block of one column: the vector over the ascending states of the same
+ * basis without symmetries.  M M+ is the reduced density matrix of A.
+ *
+ * Scope: spin-1/2 bases, projected or not, ONE partition (the whole sector on this device; up to 40 sites without a fixed weight).
+ * Refused with their own messages: fermionic bases of any kind (the partial trace of fermions needs mode-ordering signs), a mask
+ * with bits outside the sites. */
+typedef struct ls_amd_expand ls_amd_expand;
+/* d_reps: the n ascending representatives of `basis` in HBM (borrowed until ls_amd_expand_destroy).  Builds the norms n(r) -- by the
+ * routine of the matvec and cross-sector plans -- and the block table; synchronises `stream`. */
+int ls_amd_expand_create(ls_amd_expand **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, uint64_t subsystem_mask,
+                         void *stream);
+int ls_amd_expand_num_blocks(ls_amd_expand const *plan);
+/* block i (ordered by n_A): its n_A, shape, and the offset of its first element in the buffer (in elements); NULL outputs are skipped */
+int ls_amd_expand_block(ls_amd_expand const *plan, int i, int *n_a, int64_t *rows, int64_t *cols, int64_t *offset);
+int64_t ls_amd_expand_total(ls_amd_expand const *plan); /* elements of the whole buffer */
+/* d_out: the WHOLE buffer (ls_amd_expand_total elements of `dtype`); blocks [first_block, first_block + num_blocks) are cleared and
+ * ASSIGNED, every other element is left as it is.  d_psi: n elements of `dtype`.  LS_AMD_F64 needs +-1 characters (the rule of
+ * ls_amd_cross_create); anything else must be LS_AMD_C128.  Asynchronous on `stream`. */
+int ls_amd_expand_apply(ls_amd_expand *plan, ls_amd_dtype dtype, void const *d_psi, void *d_out, int first_block, int num_blocks,
+                        void *stream);
+/* synchronises `stream` and reports the device error flag: -1 when a representative or one of its images was not a state of the
+ * basis (another Hamming weight, bits above number_sites) -- such images are never stored */
+int ls_amd_expand_check(ls_amd_expand *plan, void *stream);
+char const *ls_amd_expand_kernel_name(ls_amd_expand const *plan); /* "k_expand_push" */
+void ls_amd_expand_destroy(ls_amd_expand *plan);
+/* Host-only test hook (no device): the block table of `basis` and `subsystem_mask` -- up to `capacity` entries of every non-NULL
+ * array, *total = the elements of the buffer; returns the number of blocks, -1 on the refusals above */
+int ls_amd_test_expand_layout(ls_hs_basis const *basis, uint64_t subsystem_mask, int capacity, int *n_a, int64_t *rows, int64_t *cols,
+                              int64_t *offsets, int64_t *total);
+
 /* test hooks: evaluate compiled host-side tables on the CPU (no device work) ------------------ */
 int ls_amd_basis_group_order(ls_hs_basis const *basis);
 /* 1 when the basis is a projected fermionic basis (spinless, or spinful with fixed number_up), i.e.
