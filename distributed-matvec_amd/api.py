@@ -25,7 +25,7 @@ __all__ = [
     "Basis", "Operator", "LsAmdError", "loadConfigFromYaml", "loadConfigFromDict", "enumerateStates",
     "arrFromBlockToHashed", "arrFromHashedToBlock", "matrixVectorProduct", "localMatrixVector",
     "localeIdxOf", "hash64_01", "MatvecPlan", "ReplicatedPlan", "build_library", "fillRandom",
-    "Communicator", "DistMatvec", "ReplMatvec", "block_axpby_dots", "CrossSectorPlan",
+    "Communicator", "DistMatvec", "ReplMatvec", "block_axpby_dots", "block_axpby_acc", "CrossSectorPlan",
 ]
 
 
@@ -416,6 +416,54 @@ def block_axpby_dots(w, x, y, alpha, beta, gamma, dots=None):
                                                    _dots_ptr(dots, K, "block_axpby_dots"), _stream_ptr()))
 
 
+def _as_block(t):
+    """a vector is a block of one column"""
+    return t.unsqueeze(1) if _torch().is_tensor(t) and t.dim() == 1 else t
+
+
+def _acc_args(who, blocks, z, c, want=None):
+    """the checks block_axpby_acc and matvec_block_axpby_acc share -> (blocks and z as (N, K) tensors, c as a complex)"""
+    torch = _torch()
+    blocks = [(name, _as_block(t)) for name, t in blocks]
+    z = _as_block(z)
+    x = blocks[0][1]
+    dtype = want if want is not None else (x.dtype if isinstance(x, torch.Tensor) else None)
+    for name, t in blocks + [("z", z)]:
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise _lib.LsAmdError(f"{who}: {name} must be a 1-D (N) or 2-D (N, K) tensor")
+        if t.device.type != "cuda":
+            raise _lib.LsAmdError(f"{who}: {name} must be a device tensor")
+    for name, t in blocks:
+        if t.dtype != dtype or t.dtype not in (torch.float64, torch.complex128):
+            raise _lib.LsAmdError(f"{who}: {name} is {t.dtype}" + (f", the plan computes in {want}" if want is not None else
+                                                                   f"; {', '.join(n for n, _ in blocks)} must all be float64 or all complex128"))
+    if z.dtype not in (torch.float64, torch.complex128):
+        raise _lib.LsAmdError(f"{who}: z is {z.dtype}: float64 or complex128")
+    c = complex(c)
+    if dtype == torch.complex128 and z.dtype == torch.float64:
+        raise _lib.LsAmdError(f"{who}: z is float64 next to complex128 vectors: the accumulator must be complex128")
+    if z.dtype == torch.float64 and c.imag != 0.0:
+        raise _lib.LsAmdError(f"{who}: z is float64 and c = {c!r} is not real: the accumulator must be complex128")
+    for name, t in blocks[1:] + [("z", z)]:
+        if tuple(t.shape) != tuple(x.shape):
+            raise _lib.LsAmdError(f"{who}: {name} {tuple(t.shape)} and {blocks[0][0]} {tuple(x.shape)} must have one shape")
+    return [t for _, t in blocks], z, c
+
+
+def block_axpby_acc(w, x, y, alpha, beta, gamma, z, c, dots=None):
+    """block_axpby_dots, and Z <- Z + c Y with the new Y in the same pass (ls_amd_block_axpby_acc): the epilogue of the accumulate
+    step of Chebyshev time evolution on its own, no plan.  w, x, y: float64 or complex128; z: the same, or complex128 next to
+    float64 (then c may be complex); strides of its own.  z must not overlap w, x or y."""
+    torch = _torch()
+    (x, w, y), z, c = _acc_args("block_axpby_acc", [("x", x), ("w", w), ("y", y)], z, c)
+    n, K = int(x.shape[0]), int(x.shape[1])
+    _lib.check(_lib.load().ls_amd_block_axpby_acc(int(x.dtype == torch.complex128), int(z.dtype == torch.complex128), n, K,
+                                                  C.c_void_p(w.data_ptr()), w.stride(0), w.stride(1), C.c_void_p(x.data_ptr()), x.stride(0),
+                                                  x.stride(1), C.c_void_p(y.data_ptr()), y.stride(0), y.stride(1), C.c_void_p(z.data_ptr()),
+                                                  z.stride(0), z.stride(1), float(alpha), float(beta), float(gamma), c.real, c.imag,
+                                                  _dots_ptr(dots, K, "block_axpby_acc"), _stream_ptr()))
+
+
 class MatvecPlan:
     """ls_amd_plan: binds an Operator to a partition layout (include/ls_amd.h)."""
 
@@ -563,6 +611,36 @@ class MatvecPlan:
     def axpby_kernel(self, K: int) -> str:
         """path matvec_block_axpby takes for K columns on this plan: "k_direct_cheb", "k_pull_gather_cheb" or "epilogue" """
         name = _lib.load().ls_amd_plan_axpby_kernel_name(self.h, int(K))
+        if name is None:
+            _lib.check(-1)
+        return name.decode()
+
+    def matvec_block_axpby_acc(self, x, y, alpha, beta, gamma, z, c, dots=None, check: bool = True):
+        """matvec_block_axpby, and Z[:, k] <- Z[:, k] + c Y[:, k] with the new Y where the kernel stores it
+        (ls_amd_matvec_block_axpby_acc): one order of the Chebyshev series of e^{-iHt} per call.  z: an (N, K) device tensor with
+        strides of its own, of the plan's dtype or complex128 (float64 only with a real c); it must not overlap x or y.  Vectors
+        are blocks of one column.  acc_kernel(K) names the path."""
+        torch = _torch()
+        if self.P != 1 or self.me >= 0:
+            raise _lib.LsAmdError(f"matvec_block_axpby_acc: one-partition plans only (this plan has P = {self.P}, my_partition = {self.me})")
+        want = torch.complex128 if self.cplx else torch.float64
+        (x, y), z, c = _acc_args("matvec_block_axpby_acc", [("x", x), ("y", y)], z, c, want=want)
+        n = self.reps[0].numel()
+        if x.shape[0] != n:
+            raise _lib.LsAmdError(f"matvec_block_axpby_acc: x {tuple(x.shape)}, y and z must all be ({n}, K)")
+        K = int(x.shape[1])
+        _lib.check(_lib.load().ls_amd_matvec_block_axpby_acc(self.h, K, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
+                                                             C.c_void_p(y.data_ptr()), y.stride(0), y.stride(1), float(alpha), float(beta),
+                                                             float(gamma), C.c_void_p(z.data_ptr()), z.stride(0), z.stride(1),
+                                                             int(z.dtype == torch.complex128), c.real, c.imag,
+                                                             _dots_ptr(dots, K, "matvec_block_axpby_acc"), _stream_ptr()))
+        if check:
+            self.check()
+
+    def acc_kernel(self, K: int) -> str:
+        """path matvec_block_axpby_acc takes for K columns on this plan: "epilogue", "k_direct_evolve" / "k_pull_gather_evolve"
+        (LS_AMD_ACC=fused) or "k_direct_cheb+k_axpby_acc" / "k_pull_gather_cheb+k_axpby_acc" (split, the default)"""
+        name = _lib.load().ls_amd_plan_acc_kernel_name(self.h, int(K))
         if name is None:
             _lib.check(-1)
         return name.decode()

@@ -4366,9 +4366,10 @@ static int axpby_strides(char const *who, int64_t n, int K, int64_t r, int64_t c
                          (long long)c, name, (long long)n, K);
     return 0;
 }
-static int axpby_overlap(size_t w, int64_t n, int K, void const *a, int64_t ar, int64_t ac, void const *b, int64_t br, int64_t bc) {
-    uintptr_t const a0 = (uintptr_t)a, a1 = a0 + w * (size_t)((n - 1) * ar + (int64_t)(K - 1) * ac + 1);
-    uintptr_t const b0 = (uintptr_t)b, b1 = b0 + w * (size_t)((n - 1) * br + (int64_t)(K - 1) * bc + 1);
+/* (wa, wb: the element widths of the two blocks -- the accumulator of the time-evolution step is c128 next to f64 vectors) */
+static int axpby_overlap(size_t wa, size_t wb, int64_t n, int K, void const *a, int64_t ar, int64_t ac, void const *b, int64_t br, int64_t bc) {
+    uintptr_t const a0 = (uintptr_t)a, a1 = a0 + wa * (size_t)((n - 1) * ar + (int64_t)(K - 1) * ac + 1);
+    uintptr_t const b0 = (uintptr_t)b, b1 = b0 + wb * (size_t)((n - 1) * br + (int64_t)(K - 1) * bc + 1);
     return a0 < b1 && b0 < a1;
 }
 
@@ -4388,8 +4389,8 @@ int ls_amd_block_axpby_dots(int cplx, int64_t n, int K, void const *d_w, int64_t
         axpby_strides(who, n, K, y_row, y_col, "Y") != 0)
         return -1;
     size_t const w = cplx ? 16 : 8;
-    if (axpby_overlap(w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
-    if (axpby_overlap(w, n, K, d_w, w_row, w_col, d_y, y_row, y_col)) return set_error("%s: W and Y overlap", who);
+    if (axpby_overlap(w, w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
+    if (axpby_overlap(w, w, n, K, d_w, w_row, w_col, d_y, y_row, y_col)) return set_error("%s: W and Y overlap", who);
     if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
     DEV(lsk_axpby_dots(cplx != 0, n, K, d_w, w_row, w_col, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta, gamma, d_dots,
                        d_dots ? d_dots + K : NULL, stream));
@@ -4436,7 +4437,7 @@ int ls_amd_matvec_block_axpby(ls_amd_plan *pl, int K, void const *d_x, int64_t x
     if (K == 1) { x_col = 0; y_col = 0; }
     if (axpby_strides(who, n, K, x_row, x_col, "X") != 0 || axpby_strides(who, n, K, y_row, y_col, "Y") != 0) return -1;
     size_t const w = pl->cplx ? 16 : 8;
-    if (axpby_overlap(w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
+    if (axpby_overlap(w, w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
     if (ls_amd_internal_check_y(pl, d_y) != 0) return -1;
     if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
     int const path = block_path(pl, K);
@@ -4480,6 +4481,171 @@ int ls_amd_matvec_block_axpby(ls_amd_plan *pl, int K, void const *d_x, int64_t x
         st = stage_begin(pl, ST_ROWS, stream);
         DEV(lsk_pull_gather_cheb(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, K, d_x, x_row, x_col, d_y, y_row, y_col,
                                  alpha, beta, gamma, d_dots, stream));
+        stage_end(pl, st, stream);
+    }
+    timing_end(pl, slot, stream);
+    return 0;
+}
+
+/* ============================================================================================ */
+/* accumulate step of Chebyshev time evolution (ls_amd_matvec_block_axpby_acc): the step above   */
+/* and Z += c Y with the new Y (k_evolve.hip)                                                    */
+/* ============================================================================================ */
+static char const *const g_acc_names[3] = { "epilogue", "k_direct_evolve", "k_pull_gather_evolve" };
+static char const *const g_acc_split_names[3] = { "epilogue", "k_direct_cheb+k_axpby_acc", "k_pull_gather_cheb+k_axpby_acc" };
+/* LS_AMD_ACC=fused|split, read at every call: on the two row-kernel paths, whether Z is accumulated inside the row kernel
+ * (k_direct_evolve / k_pull_gather_evolve) or by one streaming pass of k_axpby_acc behind the Chebyshev kernel of that path.
+ * Anything else: the default of DESIGN.md section 5, "Accumulate step" (ACC_SPLIT_DEFAULT per path, decided by measurement). */
+static int const ACC_SPLIT_DEFAULT[3] = { 0, 1, 1 };
+static int acc_split(int path) {
+    if (path == BLK_COLUMNS) return 0;
+    char const *e = getenv("LS_AMD_ACC");
+    if (e && strcmp(e, "fused") == 0) return 0;
+    if (e && strcmp(e, "split") == 0) return 1;
+    return ACC_SPLIT_DEFAULT[path];
+}
+char const *ls_amd_plan_acc_kernel_name(ls_amd_plan const *pl, int K) {
+    if (!pl) { set_error("ls_amd_plan_acc_kernel_name: plan is NULL"); return NULL; }
+    if (K < 1 || K > 64) { set_error("ls_amd_plan_acc_kernel_name: K = %d is outside [1, 64]", K); return NULL; }
+    int const path = block_path(pl, K);
+    return acc_split(path) ? g_acc_split_names[path] : g_acc_names[path];
+}
+
+/* what both entry points ask of Z and c (after K and n were checked and the column strides of K = 1 cleared) */
+static int acc_check_z(char const *who, int cplx, int z_cplx, int64_t n, int K, void const *d_z, int64_t z_row, int64_t z_col, double c_im) {
+    if (!d_z) return set_error("%s: Z is NULL", who);
+    if (cplx && !z_cplx) return set_error("%s: z_cplx = 0 with c128 vectors: Z must be c128 (an f64 accumulator cannot hold c Y)", who);
+    if (!z_cplx && c_im != 0.0) return set_error("%s: z_cplx = 0 with c_im = %g: an f64 Z needs a real c", who, c_im);
+    return axpby_strides(who, n, K, z_row, z_col, "Z");
+}
+
+int ls_amd_block_axpby_acc(int cplx, int z_cplx, int64_t n, int K, void const *d_w, int64_t w_row, int64_t w_col, void const *d_x,
+                           int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col, void *d_z, int64_t z_row, int64_t z_col,
+                           double alpha, double beta, double gamma, double c_re, double c_im, double *d_dots, void *stream) {
+    char const *const who = "ls_amd_block_axpby_acc";
+    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
+    if (n < 0) return set_error("%s: n = %lld is negative", who, (long long)n);
+    if (n == 0) {
+        if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+        return 0;
+    }
+    if (!d_w || !d_x || !d_y) return set_error("%s: W, X or Y is NULL", who);
+    if (K == 1) { w_col = 0; x_col = 0; y_col = 0; z_col = 0; }
+    if (acc_check_z(who, cplx != 0, z_cplx != 0, n, K, d_z, z_row, z_col, c_im) != 0) return -1;
+    if (axpby_strides(who, n, K, w_row, w_col, "W") != 0 || axpby_strides(who, n, K, x_row, x_col, "X") != 0 ||
+        axpby_strides(who, n, K, y_row, y_col, "Y") != 0)
+        return -1;
+    size_t const w = cplx ? 16 : 8, wz = z_cplx ? 16 : 8;
+    if (axpby_overlap(w, w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
+    if (axpby_overlap(w, w, n, K, d_w, w_row, w_col, d_y, y_row, y_col)) return set_error("%s: W and Y overlap", who);
+    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_y, y_row, y_col)) return set_error("%s: Z and Y overlap", who);
+    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_x, x_row, x_col)) return set_error("%s: Z and X overlap", who);
+    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_w, w_row, w_col)) return set_error("%s: Z and W overlap", who);
+    if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+    DEV(lsk_axpby_acc(cplx != 0, n, K, d_w, w_row, w_col, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta, gamma, d_z, z_row, z_col,
+                      z_cplx != 0, c_re, c_im, d_dots, d_dots ? d_dots + K : NULL, stream));
+    return 0;
+}
+
+/* axpby_columns with k_axpby_acc in place of k_axpby_dots: column k of Z is accumulated where column k of Y is finished */
+static int acc_columns(ls_amd_plan *pl, int K, char const *x, int64_t xr, int64_t xc, char *y, int64_t yr, int64_t yc, double alpha,
+                       double beta, double gamma, char *z, int64_t zr, int64_t zc, int z_cplx, double c_re, double c_im, double *d_dots,
+                       void *stream) {
+    int64_t const n = pl->parts[0].count;
+    size_t const w = pl->cplx ? 16 : 8, wz = z_cplx ? 16 : 8;
+    if (!pl->d_blk_cols && lsk_malloc(&pl->d_blk_cols, 2 * w * (size_t)n) != 0) return dev_error();
+    char *const col_x = (char *)pl->d_blk_cols, *const col_w = col_x + w * (size_t)n;
+    for (int k = 0; k < K; ++k) {
+        void const *xk = x + (size_t)k * (size_t)xc * w;
+        void const *xin = xk;
+        void *wout = col_w;
+        if (xr != 1) {
+            DEV(lsk_copy_strided(n, (int)w, xk, xr, col_x, 1, stream));
+            xin = col_x;
+        }
+        DEV(lsk_memset_async(col_w, 0, w * (size_t)n, stream));
+        if (ls_amd_matvec(pl, &xin, &wout, stream) != 0) return -1;
+        DEV(lsk_axpby_acc(pl->cplx, n, 1, col_w, 1, 0, xk, xr, 0, y + (size_t)k * (size_t)yc * w, yr, 0, alpha, beta, gamma,
+                          z + (size_t)k * (size_t)zc * wz, zr, 0, z_cplx, c_re, c_im, d_dots ? d_dots + k : NULL,
+                          d_dots ? d_dots + K + k : NULL, stream));
+    }
+    return 0;
+}
+
+int ls_amd_matvec_block_axpby_acc(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row,
+                                  int64_t y_col, double alpha, double beta, double gamma, void *d_z, int64_t z_row, int64_t z_col,
+                                  int z_cplx, double c_re, double c_im, double *d_dots, void *stream) {
+    char const *const who = "ls_amd_matvec_block_axpby_acc";
+    if (!pl) return set_error("%s: plan is NULL", who);
+    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
+    if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1)
+        return set_error("%s: one-partition plans only (this plan has P = %d, my_partition = %d)", who, pl->P, pl->me);
+    int64_t const n = pl->parts[0].count;
+    if (n <= 0) {
+        if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+        return 0;
+    }
+    if (!d_x || !d_y) return set_error("%s: X or Y is NULL", who);
+    if (K == 1) { x_col = 0; y_col = 0; z_col = 0; }
+    z_cplx = z_cplx != 0;
+    if (acc_check_z(who, pl->cplx, z_cplx, n, K, d_z, z_row, z_col, c_im) != 0) return -1;
+    if (axpby_strides(who, n, K, x_row, x_col, "X") != 0 || axpby_strides(who, n, K, y_row, y_col, "Y") != 0) return -1;
+    size_t const w = pl->cplx ? 16 : 8, wz = z_cplx ? 16 : 8;
+    if (axpby_overlap(w, w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
+    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_y, y_row, y_col)) return set_error("%s: Z and Y overlap", who);
+    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_x, x_row, x_col)) return set_error("%s: Z and X overlap", who);
+    if (ls_amd_internal_check_y(pl, d_y) != 0) return -1;
+    if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+    int const path = block_path(pl, K);
+    if (path == BLK_COLUMNS)
+        return acc_columns(pl, K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col, alpha, beta, gamma, (char *)d_z, z_row, z_col,
+                           z_cplx, c_re, c_im, d_dots, stream);
+    if (acc_split(path)) {
+        /* the Chebyshev kernel of the path, then Z += c Y in one streaming pass over the finished Y */
+        if (ls_amd_matvec_block_axpby(pl, K, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta, gamma, d_dots, stream) != 0) return -1;
+        DEV(lsk_axpby_acc(pl->cplx, n, K, NULL, 0, 0, NULL, 0, 0, d_y, y_row, y_col, 0.0, 0.0, 1.0, d_z, z_row, z_col, z_cplx, c_re, c_im, NULL,
+                          NULL, stream));
+        return 0;
+    }
+    part_state *ps = &pl->parts[0];
+    ls_amd_internal_count_matvec(pl);
+    if (path == BLK_DIRECT) {
+        lsk_tilemap tm;
+        if (block_tilemap(pl, &tm) != 0) return -1;
+        int const st = stage_begin(pl, ST_ROWS, stream);
+        int const slot = timing_begin(pl, stream);
+        DEV(lsk_direct_evolve(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, K, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta,
+                              gamma, d_z, z_row, z_col, z_cplx, c_re, c_im, d_dots,
+                              OEXT(pl->op)->is_hermitian ? pl->d_err : pl->d_err + 1, stream));
+        timing_end(pl, slot, stream);
+        stage_end(pl, st, stream);
+        return 0;
+    }
+    /* projected, indexed: slot-cache rows first, the others resolved chunk by chunk, exactly as ls_amd_matvec_block_axpby; every
+     * gather launch updates its own rows of Z and adds its rows' share to the dots */
+    lsk_pullidx ix;
+    memset(&ix, 0, sizeof(ix));
+    ix.tab = pl->gtab->tab;
+    int64_t const cached = pl->slot_cache && pl->slot_cache_valid ? pl->split_rows : 0;
+    int const slot = timing_begin(pl, stream);
+    if (cached > 0) {
+        int const st = stage_begin(pl, ST_ROWS, stream);
+        DEV(lsk_pull_gather_evolve(pl->dop, pl->dbs, pl->cplx, 0, cached, ps->d_reps, ps->d_norms, pl->pbuf, K, d_x, x_row, x_col, d_y,
+                                   y_row, y_col, alpha, beta, gamma, d_z, z_row, z_col, z_cplx, c_re, c_im, d_dots, stream));
+        stage_end(pl, st, stream);
+    }
+    if (cached < n && block_pbuf(pl) != 0) return -1;
+    for (int64_t r0 = cached; r0 < n; r0 += pl->blk_rows) {
+        int64_t const r1 = r0 + pl->blk_rows < n ? r0 + pl->blk_rows : n;
+        lsk_pullbuf pb = pl->blk_pbuf;
+        pb.row0 = r0;
+        int st = stage_begin(pl, ST_GENERATE, stream);
+        DEV(lsk_tile_pull_resolve(pl->dop, pl->dbs, r0, r1, ps->d_reps, ps->d_norms, ix, ps->d_reps, ps->count, pl->pull_halo, pb, pl->d_err,
+                                  stream));
+        stage_end(pl, st, stream);
+        st = stage_begin(pl, ST_ROWS, stream);
+        DEV(lsk_pull_gather_evolve(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, K, d_x, x_row, x_col, d_y, y_row, y_col,
+                                   alpha, beta, gamma, d_z, z_row, z_col, z_cplx, c_re, c_im, d_dots, stream));
         stage_end(pl, st, stream);
     }
     timing_end(pl, slot, stream);

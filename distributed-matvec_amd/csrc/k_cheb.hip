@@ -10,7 +10,8 @@
 // The two row loops are COPIES of the block kernels' loops, not shared with them: with the loop moved into a device function
 // template (epilogue policy as a parameter, by value or by reference, with and without __restrict__ on the parameters) the
 // compiler allocates the registers of all eight k_direct_blk instantiations differently, and their measured machine code
-// (kernel_isa.json) must stay what it is.  A change to one of the loops has to be made in both places.
+// (kernel_isa.json) must stay what it is.  A change to one of the loops has to be made in all three places
+// (k_evolve.hip holds a third copy of each, with the accumulate of the time-evolution step).
 // gamma == 0: Y is not read (it may hold NaN).  The dots are ADDED to d_dots by atomics: the caller clears them.
 #include <hip/hip_runtime.h>
 #include "k_pull_t.hpp" // pull_kinds, COEF_*, kNoSlot, pull_xcd_chunk (and lsk_dev.hpp)

@@ -496,6 +496,20 @@ int lsk_pull_gather_cheb(lsk_operator op, lsk_basis bs, int cplx, int64_t row0, 
 int lsk_axpby_dots(int cplx, int64_t n, int K, void const *w, int64_t wr, int64_t wc, void const *x, int64_t xr, int64_t xc,
                    void *y, int64_t yr, int64_t yc, double alpha, double beta, double gamma, double *d_xx, double *d_xy,
                    void *stream);
+/* ---- accumulate step of Chebyshev time evolution (ls_amd_matvec_block_axpby_acc; k_evolve.hip): the Chebyshev step above, and
+ * Z[i, k] += (c_re + i c_im) Y[i, k] with the new Y where it is stored.  Z: K columns of its own strides (in ITS elements), c128 when
+ * z_cplx != 0, else f64 (then c_im == 0 and f64 vectors).  The row kernels want a c128 Z 16-byte aligned. */
+int lsk_direct_evolve(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, lsk_tilemap tm, uint64_t const *reps, int K,
+                      void const *x, int64_t xr, int64_t xc, void *y, int64_t yr, int64_t yc, double alpha, double beta, double gamma,
+                      void *z, int64_t zr, int64_t zc, int z_cplx, double c_re, double c_im, double *d_dots, int *d_err, void *stream);
+int lsk_pull_gather_evolve(lsk_operator op, lsk_basis bs, int cplx, int64_t row0, int64_t row1, uint64_t const *reps,
+                           double const *norms, lsk_pullbuf buf, int K, void const *x, int64_t xr, int64_t xc, void *y,
+                           int64_t yr, int64_t yc, double alpha, double beta, double gamma, void *z, int64_t zr, int64_t zc, int z_cplx,
+                           double c_re, double c_im, double *d_dots, void *stream);
+/* the epilogue pass alone: Y <- alpha W + beta X + gamma Y, Z += c Y; the dots are ADDED to d_xx[k], d_xy[k] */
+int lsk_axpby_acc(int cplx, int64_t n, int K, void const *w, int64_t wr, int64_t wc, void const *x, int64_t xr, int64_t xc,
+                  void *y, int64_t yr, int64_t yc, double alpha, double beta, double gamma, void *z, int64_t zr, int64_t zc,
+                  int z_cplx, double c_re, double c_im, double *d_xx, double *d_xy, void *stream);
 /* out[i] = x[i] * norms[i] (f64 / c128): the owner-side prescaling of the indexed mode */
 int lsk_scale(int cplx, int64_t n, void const *x, double const *norms, void *out, void *stream);
 /* dst[perm[g] - base] = src[g] for every g with base <= perm[g] < base + count (8-byte elements): the rows one owner holds,

@@ -1,0 +1,324 @@
+"""Chebyshev time evolution (Tal-Ezer and Kosloff, J. Chem. Phys. 81, 3967): e^{-iHt} psi and e^{-tau H} psi at any basis size the
+matvec reaches.  With H~ = (H - b) / a mapped into [-1, 1] (a = (hi - lo) / 2, b = (hi + lo) / 2),
+
+    e^{-iHt} psi    = e^{-ibt} sum_n (2 - delta_n0) (-i)^n J_n(at) T_n(H~) psi,
+    e^{-tau H} psi  = e^{-lo tau} sum_n (2 - delta_n0) (-1)^n e^{-a tau} I_n(a tau) T_n(H~) psi,
+
+on the recurrence v_{n+1} = 2 H~ v_n - v_{n-1} of kpm.py.  One order of the series is one call of
+MatvecPlan.matvec_block_axpby_acc (ls_amd_matvec_block_axpby_acc): c_{n+1} v_{n+1} is added to the running sum Z in the pass that
+finishes v_{n+1} or in one streaming pass behind it, and a real recurrence feeds a complex sum without a complex
+copy of it.  The
+series is cut at the smallest order N whose discarded coefficients sum to at most eps (|T_n| <= 1: that sum bounds the error
+relative to |psi|); N grows like a t + O((a t)^(1/3)).  One-partition plans.  The coefficients are computed on the host in numpy."""
+from __future__ import annotations
+
+import cmath
+import math
+import time
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import kpm
+from ._lib import LsAmdError
+
+__all__ = ["bessel_series", "propagator_coefficients", "propagate", "evolve", "autocorrelation", "EvolveResult"]
+
+MAX_COLUMNS = 64
+_BIG = 1e250
+
+
+def bessel_series(x: float, eps: float, modified: bool = False) -> np.ndarray:
+    """J_n(x) -- modified: e^{-x} I_n(x), x >= 0 -- for n = 0..N, N the smallest order whose discarded tail 2 sum_{n > N} |.| is
+    <= eps.  Miller's downward recurrence f_{n-1} = (2n / x) f_n -+ f_{n+1} from an order far above |x|, rescaled whenever it
+    passes 1e250, normalised by J_0 + 2 sum_k J_2k = 1 (e^{-x} (I_0 + 2 sum_k I_k) = 1).  J_n(-x) = (-1)^n J_n(x)."""
+    x = float(x)
+    eps = float(eps)
+    if not math.isfinite(x):
+        raise ValueError(f"bessel_series: x = {x!r} is not finite")
+    if not eps > 0.0:
+        raise ValueError(f"bessel_series: eps = {eps!r} must be positive")
+    if modified and x < 0.0:
+        raise ValueError(f"bessel_series: x = {x!r} is negative (e^{{-x}} I_n(x) is computed for x >= 0)")
+    if x == 0.0:
+        return np.ones(1, dtype=np.float64)
+    ax = abs(x)
+    # far enough above the turning point n = |x| that f_M / f_N is below every double: the start values (0, 1) are then as good
+    # as the true ones
+    M = 2 * int(math.ceil(0.55 * ax + 15.0 * (ax ** (1.0 / 3.0) + 1.0) + 30.0))
+    f = np.zeros(M + 2, dtype=np.float64)
+    f[M] = 1.0
+    hi, cur = 0.0, 1.0  # f[n + 1], f[n]
+    sign = 1.0 if modified else -1.0
+    for n in range(M, 0, -1):
+        nxt = (2.0 * n / ax) * cur + sign * hi
+        hi, cur = cur, nxt
+        f[n - 1] = cur
+        if abs(cur) > _BIG:
+            f[n - 1:] *= 1.0 / _BIG
+            hi *= 1.0 / _BIG
+            cur *= 1.0 / _BIG
+    if modified:
+        norm = f[0] + 2.0 * f[1:].sum()
+    else:
+        norm = f[0] + 2.0 * f[2::2].sum()
+    f /= norm
+    if x < 0.0:
+        f[1::2] = -f[1::2]
+    tail = 2.0 * np.concatenate([np.cumsum(np.abs(f[::-1]))[::-1][1:], [0.0]])  # tail[N] = 2 sum_{n > N} |f_n|
+    N = int(np.argmax(tail <= eps))
+    return f[:N + 1].copy()
+
+
+def _check_bounds(bounds):
+    try:
+        lo, hi = float(bounds[0]), float(bounds[1])
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"bounds = {bounds!r}: need finite lo < hi") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+        raise ValueError(f"bounds = ({bounds[0]!r}, {bounds[1]!r}): need finite lo < hi")
+    return lo, hi
+
+
+def propagator_coefficients(t: float, bounds, eps: float = 1e-12, imaginary: bool = False, reference_energy=None):
+    """(c[0..N], prefactor) of  prefactor * sum_n c_n T_n(H~):
+    real time       c_n = (2 - delta_n0) (-i)^n J_n(a t)             (complex128), prefactor e^{-i b t}; t of either sign;
+    imaginary time  c_n = (2 - delta_n0) (-1)^n e^{-a t} I_n(a t)     (float64),    prefactor e^{-(lo - E_ref) t}, t >= 0:
+                    e^{-t (H - E_ref)}, E_ref = reference_energy or lo -- nothing in it can overflow.
+    N is the smallest order with 2 sum_{n > N} |J_n| <= eps (bessel_series)."""
+    lo, hi = _check_bounds(bounds)
+    t = float(t)
+    if not math.isfinite(t):
+        raise ValueError(f"t = {t!r} is not finite")
+    a, b = 0.5 * (hi - lo), 0.5 * (hi + lo)
+    if imaginary:
+        if t < 0.0:
+            raise ValueError(f"t = {t!r}: imaginary-time evolution needs t >= 0")
+        e_ref = lo if reference_energy is None else float(reference_energy)
+        f = bessel_series(a * t, eps, modified=True)
+        c = 2.0 * f
+        c[0] = f[0]
+        c[1::2] = -c[1::2]
+        return c, math.exp(-(lo - e_ref) * t)
+    f = bessel_series(a * t, eps)
+    c = (2.0 * f).astype(np.complex128)
+    c[0] = f[0]
+    c *= np.array([1.0, -1.0j, -1.0, 1.0j])[np.arange(len(f)) % 4]
+    return c, cmath.exp(-1j * b * t)
+
+
+def _check_operator(op):
+    """what propagate asks of its operator, before anything touches the device"""
+    if not op.plan.matrix.isHermitian:
+        raise ValueError("evolve: the Hamiltonian is not Hermitian (the Chebyshev propagator needs a real spectrum)")
+    if len(op.sizes) != 1:
+        raise LsAmdError("evolve: one-partition plans only")
+
+
+def propagate(op, state, t: float, bounds=None, eps: float = 1e-12, imaginary: bool = False, reference_energy=None, _info=None):
+    """e^{-iHt} state (imaginary: e^{-t (H - E_ref)} state, E_ref = reference_energy or bounds[0]) as a new device tensor: a
+    vector, or an (n, K) block of K <= 64 states.  op: a diagonalize.LocalOperator on one partition over a Hermitian operator;
+    bounds: (lo, hi) enclosing its spectrum (kpm.spectral_bounds(op) when None).  The recurrence runs in op.dtype; the sum is
+    complex128 in real time and op.dtype in imaginary time.  Three blocks of memory.  Every kpm.GUARD_EVERY orders the norms of
+    the recurrence are read back (the only host synchronisation): bounds that do not enclose the spectrum raise LsAmdError."""
+    import torch
+
+    cplx_state = bool(state.is_complex())
+    K = 1 if state.dim() == 1 else (int(state.shape[1]) if state.dim() == 2 else -1)
+    if K < 0:
+        raise LsAmdError(f"evolve: state {tuple(state.shape)} must be a vector or an (n, K) block")
+    if K > MAX_COLUMNS or K < 1:
+        raise LsAmdError(f"evolve: K = {K} columns: 1 <= K <= {MAX_COLUMNS}")
+    _check_operator(op)
+    if cplx_state and op.dtype != torch.complex128:
+        raise LsAmdError("evolve: the state is complex and the operator computes in float64: build the operator with "
+                         "dtype=torch.complex128")
+    if state.shape[0] != op.n_local:
+        raise LsAmdError(f"evolve: state {tuple(state.shape)} must have {op.n_local} rows")
+    if bounds is not None:
+        bounds = _check_bounds(bounds)
+    else:
+        bounds = _check_bounds(kpm.spectral_bounds(op))
+    lo, hi = bounds
+    a, b = 0.5 * (hi - lo), 0.5 * (hi + lo)
+    c, prefactor = propagator_coefficients(t, bounds, eps, imaginary, reference_energy)
+    N = len(c) - 1
+    zdtype = op.dtype if imaginary else torch.complex128
+    X = state.reshape(op.n_local, K).to(op.dtype).contiguous().clone()
+    Z = (X * (float(c[0]) if imaginary else complex(c[0]))).to(zdtype)
+    plan = op.plan
+    if N > 0:
+        Y = torch.empty_like(X)
+        dots = torch.zeros((N, 2 * K), dtype=torch.float64, device=X.device)
+        host = np.empty((N, 2 * K), dtype=np.float64)
+        checked = 0
+
+        def read_back(upto):
+            nonlocal checked
+            host[checked:upto] = dots[checked:upto].cpu().numpy()
+            plan.check()
+            kpm.check_guard(np.concatenate([host[:1], host[checked:upto]]), K, (lo, hi), first_step=checked - 1)
+            checked = upto
+
+        for s in range(N):
+            cn = complex(c[s + 1])
+            if s == 0:
+                plan.matvec_block_axpby_acc(X, Y, 1.0 / a, -b / a, 0.0, Z, cn, dots=dots[0], check=False)
+            else:
+                plan.matvec_block_axpby_acc(X, Y, 2.0 / a, -2.0 * b / a, -1.0, Z, cn, dots=dots[s], check=False)
+            X, Y = Y, X
+            op.matvecs += K
+            if (s + 1) % kpm.GUARD_EVERY == 0:
+                read_back(s + 1)
+        if checked < N:
+            read_back(N)
+    if prefactor != 1.0:
+        Z.mul_(prefactor)
+    if _info is not None:
+        _info["order"] = N
+        _info["bounds"] = bounds
+    return Z.reshape(-1) if state.dim() == 1 else Z
+
+
+@dataclass
+class EvolveResult:
+    times: np.ndarray         # [T] the output times
+    values: np.ndarray        # [T, n_obs, K] complex128: <psi_k(t)|O|psi_k(t)> (not divided by the norm)
+    norms: np.ndarray         # [T, K] float64: |psi_k(t)|
+    orders: np.ndarray        # [T] int: the order N of the segment that ends at times[j]
+    bounds: tuple             # (lo, hi) the spectrum was rescaled with
+    matvec_columns: int       # columns that went through H in the propagation (K per order)
+    kernel: str               # MatvecPlan.acc_kernel(K): "epilogue", "k_*_cheb+k_axpby_acc" (default) or "k_*_evolve" (LS_AMD_ACC=fused)
+    seconds: float = 0.0      # wall time of the driver
+    states: object = None     # keep_states: [T] device tensors, psi(times[j])
+
+
+def _observable(ob, obs, api):
+    if isinstance(ob, (int, np.integer)) and not isinstance(ob, bool):
+        if obs is None:
+            raise ValueError("observables: an index needs a config with an `observables:` section")
+        if not 0 <= int(ob) < len(obs):
+            raise ValueError(f"observable = {ob}: the config has {len(obs)} observables")
+        return obs[int(ob)]
+    if isinstance(ob, api.Operator):
+        return ob
+    raise ValueError("observables: api.Operator objects or indices into the config's observables")
+
+
+def evolve(config_or_op, state, times, observables=None, keep_states: bool = False, bounds=None, eps: float = 1e-12,
+           imaginary: bool = False, reference_energy=None):
+    """psi(t) = e^{-iHt} state (imaginary: e^{-t (H - E_ref)} state) at the ascending `times`, segment by segment from the
+    previous time, with <psi(t)|O|psi(t)> of every observable (api.Operator on the same basis, or an index into the config's
+    `observables:`) and the norms at every time.  config_or_op: a config (dict or YAML path) with a `hamiltonian:`, or a
+    diagonalize.LocalOperator.  state: a device vector or (n, K) block, K <= 64.  A real state under a real Hamiltonian with real
+    characters runs its first segment in float64 (the sum is complex128); the complex operator of the later segments is made
+    here.  -> EvolveResult."""
+    import torch
+
+    from . import api
+    from .diagonalize import LocalOperator
+
+    t0 = time.perf_counter()
+    ts = np.atleast_1d(np.asarray(times, dtype=np.float64))
+    if ts.ndim != 1 or ts.size == 0 or not np.isfinite(ts).all() or (np.diff(ts) < 0.0).any():
+        raise ValueError("times: a non-empty ascending sequence of finite numbers")
+    K = 1 if state.dim() == 1 else (int(state.shape[1]) if state.dim() == 2 else -1)
+    if K < 1 or K > MAX_COLUMNS:
+        raise LsAmdError(f"evolve: state {tuple(state.shape)} must be a vector or an (n, K) block, 1 <= K <= {MAX_COLUMNS}")
+    if bounds is not None:
+        bounds = _check_bounds(bounds)
+    obs = None
+    if isinstance(config_or_op, LocalOperator):
+        op0 = config_or_op
+        _check_operator(op0)
+        h, reps = op0.plan.matrix, op0.reps
+        ops = {op0.dtype: op0}
+        if state.is_complex() and op0.dtype != torch.complex128:
+            raise LsAmdError("evolve: the state is complex and the operator computes in float64: build the operator with "
+                             "dtype=torch.complex128")
+        first = op0.dtype
+    else:
+        from .entanglement import _complex_characters
+
+        loaded = kpm._load(config_or_op, observables=True)
+        basis, h = loaded[0], loaded[1]
+        obs = loaded[2]
+        reps, _ = api.enumerateStates(basis, 1)
+        real = h.isReal and not _complex_characters(basis) and not state.is_complex()
+        first = torch.float64 if real else torch.complex128
+        ops = {}
+    wanted = [_observable(ob, obs, api) for ob in (observables or [])]
+
+    def op_of(dtype):
+        if dtype not in ops:
+            ops[dtype] = LocalOperator(h, reps, dtype)
+        return ops[dtype]
+
+    oplans = {}
+
+    def expectation(j, psi):
+        block = psi.reshape(psi.shape[0], K)
+        out = np.empty((len(wanted), K), dtype=np.complex128)
+        tmp = None
+        for q, O in enumerate(wanted):
+            key = (q, block.dtype)
+            if key not in oplans:
+                oplans[key] = LocalOperator(O, reps, block.dtype)
+            tmp = torch.empty_like(block) if tmp is None else tmp
+            if K == 1:
+                oplans[key].matvec(block[:, 0], tmp[:, 0])
+            else:
+                oplans[key].matvec_block(block, tmp)
+            oplans[key].check()
+            out[q] = (block.conj() * tmp).sum(dim=0).cpu().numpy()
+        return out
+
+    op = op_of(first)
+    if bounds is None:
+        bounds = _check_bounds(kpm.spectral_bounds(op))
+    psi = state.to(first)
+    if psi.shape[0] != op.n_local:
+        raise LsAmdError(f"evolve: state {tuple(state.shape)} must have {op.n_local} rows")
+    T = len(ts)
+    values = np.zeros((T, len(wanted), K), dtype=np.complex128)
+    norms = np.zeros((T, K), dtype=np.float64)
+    orders = np.zeros(T, dtype=np.int64)
+    states = [] if keep_states else None
+    columns, kernel, prev = 0, None, 0.0
+    for j, tj in enumerate(ts):
+        dt = float(tj) - prev
+        if dt != 0.0:
+            if psi.is_complex() and op.dtype != torch.complex128:
+                op = op_of(torch.complex128)
+            info, before = {}, op.matvecs
+            psi = propagate(op, psi, dt, bounds=bounds, eps=eps, imaginary=imaginary, reference_energy=reference_energy, _info=info)
+            orders[j] = info["order"]
+            columns += op.matvecs - before
+            kernel = kernel or op.plan.acc_kernel(K)
+            prev = float(tj)
+        norms[j] = torch.linalg.vector_norm(psi.reshape(psi.shape[0], K), dim=0).cpu().numpy()
+        if wanted:
+            values[j] = expectation(j, psi)
+        if keep_states:
+            states.append(psi if dt != 0.0 else psi.clone())
+    res = EvolveResult(ts, values, norms, orders, bounds, columns, kernel or op.plan.acc_kernel(K), states=states)
+    res.seconds = time.perf_counter() - t0
+    return res
+
+
+def autocorrelation(moments, bounds, times, eps: float = 1e-12) -> np.ndarray:
+    """<v0|e^{-iHt}|v0> = e^{-ibt} sum_n c_n(t) mu_n from the undamped Chebyshev moments mu_n = <v0|T_n(H~)|v0> [M] (or [..., M])
+    that kpm.chebyshev_moments returns for the same bounds: the Loschmidt amplitude -- with v0 = A|psi>, <psi|A^+(t) A|psi> up to
+    the phase of |psi> -- at the times [T] -> complex128 [T] (or [..., T]).  Host only.  ValueError when there are fewer moments
+    than the order the series needs for `eps` at some time."""
+    mu = np.asarray(moments, dtype=np.float64)
+    lo, hi = _check_bounds(bounds)
+    ts = np.atleast_1d(np.asarray(times, dtype=np.float64))
+    M = mu.shape[-1]
+    out = np.empty(mu.shape[:-1] + (len(ts),), dtype=np.complex128)
+    for j, t in enumerate(ts):
+        c, pref = propagator_coefficients(float(t), (lo, hi), eps)
+        if len(c) > M:
+            raise ValueError(f"autocorrelation: t = {float(t)!r} needs {len(c)} moments for eps = {eps!r}, {M} were given")
+        out[..., j] = pref * (mu[..., :len(c)] @ c)
+    return out

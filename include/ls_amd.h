@@ -341,6 +341,26 @@ char const *ls_amd_plan_axpby_kernel_name(ls_amd_plan const *plan, int K);
 int ls_amd_block_axpby_dots(int cplx, int64_t n, int K, void const *d_w, int64_t w_row, int64_t w_col, void const *d_x, int64_t x_row,
                             int64_t x_col, void *d_y, int64_t y_row, int64_t y_col, double alpha, double beta, double gamma,
                             double *d_dots, void *stream);
+/* The accumulate step of Chebyshev time evolution: ls_amd_matvec_block_axpby, and the running sum of the series where the new Y
+ * is stored,
+ *     Z[i,k] <- Z[i,k] + (c_re + i c_im) * Y[i,k]   (the new Y),
+ * so that e^{-iHt} psi = sum_n c_n T_n(H~) psi costs one pass per order.  Z: K columns of n rows with strides of its own (in its
+ * own elements), c128 when z_cplx != 0, else f64.  Element types (X / Y, Z): (f64, f64) with c_im == 0, (f64, c128), (c128, c128);
+ * an f64 Z on a c128 plan is refused.  Z must not overlap X or Y; under LS_AMD_ACC=fused a c128 Z on a row-kernel path is 16-byte aligned.  Y, the dots, gamma == 0, the
+ * paths and the environment exactly as ls_amd_matvec_block_axpby. */
+int ls_amd_matvec_block_axpby_acc(ls_amd_plan *plan, int K, void const *d_x, int64_t x_row, int64_t x_col,
+                                  void *d_y, int64_t y_row, int64_t y_col, double alpha, double beta, double gamma,
+                                  void *d_z, int64_t z_row, int64_t z_col, int z_cplx, double c_re, double c_im,
+                                  double *d_dots, void *stream);
+/* "epilogue" (matvec into scratch, then k_axpby_acc); on the two row-kernel paths LS_AMD_ACC=fused gives "k_direct_evolve" /
+ * "k_pull_gather_evolve" (Z accumulated inside the row kernel), LS_AMD_ACC=split "k_direct_cheb+k_axpby_acc" /
+ * "k_pull_gather_cheb+k_axpby_acc" (the Chebyshev kernel, then one accumulate pass); unset: split, the faster one as measured */
+char const *ls_amd_plan_acc_kernel_name(ls_amd_plan const *plan, int K);
+/* the epilogue alone, no plan: Y <- alpha W + beta X + gamma Y, Z <- Z + c Y, and the two dots.  Z must not overlap W, X or Y. */
+int ls_amd_block_axpby_acc(int cplx, int z_cplx, int64_t n, int K, void const *d_w, int64_t w_row, int64_t w_col, void const *d_x,
+                           int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col, void *d_z, int64_t z_row,
+                           int64_t z_col, double alpha, double beta, double gamma, double c_re, double c_im, double *d_dots,
+                           void *stream);
 int ls_amd_plan_check(ls_amd_plan *plan, void *stream);
 
 /* ------------------------------------------------------------------------------------------
