@@ -64,6 +64,11 @@ class LsHsOperator(C.Structure):
     ]
 
 
+class LsAmdCsr(C.Structure):  # ls_amd_csr (include/ls_amd.h): the matrix of a cross-sector plan, library-owned device arrays
+    _fields_ = [("rows", C.c_int64), ("cols", C.c_int64), ("nnz", C.c_int64), ("dtype", C.c_int),
+                ("d_row_ptr", C.c_void_p), ("d_col", C.c_void_p), ("d_val", C.c_void_p)]
+
+
 class YamlConfig(C.Structure):  # ls_hs_yaml_config (include/ls_hs.h; /root/reference/src/FFI.chpl:121-126)
     _fields_ = [("basis", C.POINTER(LsHsBasis)), ("hamiltonian", C.POINTER(LsHsOperator)), ("number_observables", C.c_int),
                 ("observables", C.POINTER(C.POINTER(LsHsOperator)))]
@@ -167,6 +172,9 @@ def load():
         "ls_amd_cross_kernel_name": (C.c_char_p, [vp]),
         "ls_amd_cross_nnz": (C.c_int64, [vp]),
         "ls_amd_cross_destroy": (None, [vp]),
+        "ls_amd_cross_csr_bytes": (C.c_int64, [vp]),
+        "ls_amd_cross_csr": (C.c_int, [vp, C.c_int64, C.POINTER(LsAmdCsr), vp]),
+        "ls_amd_csr_free": (None, [C.POINTER(LsAmdCsr)]),
         "ls_amd_expand_create": (C.c_int, [C.POINTER(vp), bp, vp, C.c_int64, C.c_uint64, vp]),
         "ls_amd_expand_num_blocks": (C.c_int, [vp]),
         "ls_amd_expand_block": (C.c_int, [vp, C.c_int, c_intp, c_i64p, c_i64p, c_i64p]),

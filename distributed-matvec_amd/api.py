@@ -14,6 +14,7 @@ uint64 arrays are held as torch.int64 tensors (bit-identical).
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -26,6 +27,7 @@ __all__ = [
     "arrFromBlockToHashed", "arrFromHashedToBlock", "matrixVectorProduct", "localMatrixVector",
     "localeIdxOf", "hash64_01", "MatvecPlan", "ReplicatedPlan", "build_library", "fillRandom",
     "Communicator", "DistMatvec", "ReplMatvec", "block_axpby_dots", "block_axpby_acc", "CrossSectorPlan",
+    "CsrMatrix",
 ]
 
 
@@ -220,6 +222,28 @@ class Operator:
         _lib.raise_pending_halt()
         return rc == 0
 
+    def to_csr(self, reps, dtype=None, max_bytes: int = 8 << 30) -> "CsrMatrix":
+        """the matrix of this operator on its own basis, rows and columns in the order of `reps` (its ascending representatives: a
+        1-D int64 device tensor, or a list of one -- one partition), as canonical CSR on the device: a CrossSectorPlan with
+        self.basis on both sides, exported (CrossSectorPlan.to_csr).  dtype None: float64 when the operator is real and every
+        character of the basis is +-1, else complex128."""
+        torch = _torch()
+        if isinstance(reps, (list, tuple)):
+            if len(reps) != 1:
+                raise LsAmdError(f"Operator.to_csr: one partition (the whole sector on this device), got {len(reps)} blocks of representatives")
+            reps = reps[0]
+        if dtype is None:
+            dtype = torch.float64 if self.isReal and not _complex_characters(self.basis) else torch.complex128
+        plan = CrossSectorPlan(self, reps, self.basis, reps, dtype)
+        try:
+            return plan.to_csr(max_bytes=max_bytes)
+        finally:
+            plan.destroy()
+
+    def to_dense(self, reps, dtype=None, max_bytes: int = 8 << 30):
+        """to_csr(...).to_dense(...): the (n, n) device matrix; max_bytes bounds the export and the dense matrix alike"""
+        return self.to_csr(reps, dtype=dtype, max_bytes=max_bytes).to_dense(max_bytes=max_bytes)
+
     # host-pointer entry points of the kernel table ----------------------------------------------
     def __matmul__(self, x: np.ndarray) -> np.ndarray:
         """kernels->matrix_vector_product (ls_chpl_matrix_vector_product, DMV:1095-1110) on host
@@ -332,6 +356,58 @@ def _adopt(ptr: int, count: int, torch_dtype):
         if ptr:
             L.ls_amd_free(C.c_void_p(ptr))
     return t
+
+
+def _complex_characters(basis: Basis) -> bool:
+    """whether some character of the basis' group is not +-1 (host only)"""
+    L = _lib.load()
+    re, im = C.c_double(), C.c_double()
+    for g in range(int(L.ls_amd_basis_group_order(basis.payload))):
+        L.ls_amd_basis_group_character(basis.payload, g, C.byref(re), C.byref(im))
+        if im.value != 0.0 or abs(re.value) != 1.0:
+            return True
+    return False
+
+
+@dataclass
+class CsrMatrix:
+    """A sparse matrix in canonical CSR form (include/ls_amd.h, ls_amd_csr): shape = (rows, columns); crow_indices int64
+    [rows + 1]; col_indices int64 [nnz], strictly ascending inside every row; values float64 or complex128 [nnz].  What
+    CrossSectorPlan.to_csr and Operator.to_csr return (device tensors); any three tensors on one device do."""
+    shape: tuple
+    crow_indices: object
+    col_indices: object
+    values: object
+
+    @property
+    def nnz(self) -> int:
+        return int(self.col_indices.numel())
+
+    @property
+    def dtype(self):
+        return self.values.dtype
+
+    def row_indices(self):
+        """the row of every entry (int64 [nnz])"""
+        torch = _torch()
+        counts = self.crow_indices[1:] - self.crow_indices[:-1]
+        return torch.repeat_interleave(torch.arange(self.shape[0], dtype=torch.int64, device=counts.device), counts, output_size=self.nnz)
+
+    def to_dense(self, max_bytes: int = 8 << 30):
+        """the (rows, columns) matrix on the device of the arrays, by an indexed store (no sparse kernels of torch)"""
+        torch = _torch()
+        rows, cols = int(self.shape[0]), int(self.shape[1])
+        need = rows * cols * self.values.element_size()
+        if need > max_bytes:
+            raise LsAmdError(f"CsrMatrix.to_dense: the dense {rows} x {cols} matrix needs {need} bytes, max_bytes is {max_bytes}")
+        out = torch.zeros((rows, cols), dtype=self.values.dtype, device=self.values.device)
+        if self.nnz:
+            out[self.row_indices(), self.col_indices] = self.values
+        return out
+
+    def to_torch(self):
+        """the same arrays as a torch.sparse_csr_tensor"""
+        return _torch().sparse_csr_tensor(self.crow_indices, self.col_indices, self.values, size=tuple(self.shape))
 
 
 def enumerateStates(basis: Basis, numLocales: int = 1):
@@ -776,6 +852,34 @@ class CrossSectorPlan:
 
     def check(self):
         _lib.check(_lib.load().ls_amd_cross_check(self.h, _stream_ptr()))
+
+    @property
+    def csr_bytes(self) -> int:
+        """upper bound of the peak device bytes of to_csr (ls_amd_cross_csr_bytes; host only)"""
+        return int(_lib.load().ls_amd_cross_csr_bytes(self.h))
+
+    def to_csr(self, max_bytes: int = 8 << 30) -> CsrMatrix:
+        """the matrix apply multiplies by, (n_dst, n_src), as canonical CSR on the device (ls_amd_cross_csr): built in O(nnz) by the
+        plan's own kernel in an emitting mode; the images of a row that meet in one source state are summed, sums that cancel are
+        dropped (so nnz <= self.nnz); two exports are bitwise equal.  LsAmdError when csr_bytes exceeds max_bytes (nothing is
+        allocated), or when an image lies outside the source basis (the error of check())."""
+        torch = _torch()
+        L = _lib.load()
+        m = _lib.LsAmdCsr()
+        _lib.check(L.ls_amd_cross_csr(self.h, int(max_bytes), C.byref(m), _stream_ptr()))
+        try:
+            # (copies; _adopt frees the library's array whatever happens)
+            ptrs = [(m.d_row_ptr, m.rows + 1, torch.int64), (m.d_col, m.nnz, torch.int64), (m.d_val, m.nnz, self.dtype)]
+            m.d_row_ptr = m.d_col = m.d_val = None
+            out = []
+            for k, (ptr, count, dt) in enumerate(ptrs):
+                ptrs[k] = None
+                out.append(_adopt(ptr, int(count), dt))
+        finally:
+            for rest in ptrs:
+                if rest is not None and rest[0]:
+                    L.ls_amd_free(C.c_void_p(rest[0]))
+        return CsrMatrix((int(m.rows), int(m.cols)), out[0], out[1], out[2])
 
 
 class _BorrowedPlan(MatvecPlan):

@@ -5642,6 +5642,86 @@ int64_t ls_amd_cross_nnz(ls_amd_cross const *cx) {
     return cx->nnz;
 }
 
+/* ---- the matrix of a plan as canonical CSR (include/ls_amd.h: ls_amd_cross_csr; csrc/k_csr.hip) ---- */
+/* peak device bytes of an export: the raw and the final (column, value) arrays -- the final ones are no longer than the raw ones,
+ * which hold ls_amd_cross_nnz entries -- three arrays of n_dst + 1 offsets, and the scratch of the scans (one partial sum per
+ * 1024 elements at the least; bounded by 1 / 64 of the scanned array plus a page) */
+int64_t ls_amd_cross_csr_bytes(ls_amd_cross const *cx) {
+    if (!cx) { set_error("ls_amd_cross_csr_bytes: NULL plan"); return -1; }
+    int64_t const entry = 8 + (cx->cplx ? 16 : 8), rows = 8 * (cx->n_dst + 1);
+    return 2 * cx->nnz * entry + 3 * rows + rows / 64 + 4096;
+}
+
+void ls_amd_csr_free(ls_amd_csr *m) {
+    if (!m) return;
+    if (m->d_row_ptr) lsk_free(m->d_row_ptr);
+    if (m->d_col) lsk_free(m->d_col);
+    if (m->d_val) lsk_free(m->d_val);
+    memset(m, 0, sizeof(*m));
+}
+
+static int cross_csr_run(ls_amd_cross *cx, ls_amd_csr *out, void **tmp, void *stream) {
+    /* tmp[0] cnt, tmp[1] off (n_dst + 1 each), tmp[2] raw columns, tmp[3] raw values: freed by the caller */
+    int64_t const n = cx->n_dst;
+    size_t const vb = cx->cplx ? 16 : 8;
+    int64_t raw = 0, nnz = 0;
+    lsk_gtab const gt = cx->gtab ? cx->gtab->tab : no_gtab();
+    int const empty = cx->n_groups == 0 || cx->n_src == 0 || n == 0;
+    void *p = NULL;
+    DEV(lsk_malloc(&p, 8 * (size_t)(n + 1)));
+    out->d_row_ptr = (int64_t *)p;
+    if (empty) { DEV(lsk_memset_async(out->d_row_ptr, 0, 8 * (size_t)(n + 1), stream)); }
+    else {
+        DEV(lsk_malloc(&tmp[0], 8 * (size_t)(n + 1)));
+        DEV(lsk_malloc(&tmp[1], 8 * (size_t)(n + 1)));
+        DEV(lsk_memset_async(tmp[0], 0, 8 * (size_t)(n + 1), stream)); /* (element n stays 0: the scan's last element is the sum) */
+        DEV(lsk_cross_emit(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, gt, cx->cplx, n, cx->d_dst_reps,
+                           cx->d_norms, cx->tiny, NULL, (int64_t *)tmp[0], NULL, NULL, cx->d_err, stream));
+        DEV(lsk_exclusive_scan_i64(n + 1, (int64_t const *)tmp[0], (int64_t *)tmp[1], stream));
+        DEV(lsk_sync(stream));
+        DEV(lsk_d2h(&raw, (int64_t *)tmp[1] + n, sizeof(raw)));
+        if (raw != cx->nnz) return set_error("ls_amd_cross_csr: the counting pass found %lld packets, the plan %lld", (long long)raw, (long long)cx->nnz);
+    }
+    if (raw > 0) {
+        DEV(lsk_malloc(&tmp[2], 8 * (size_t)raw));
+        DEV(lsk_malloc(&tmp[3], vb * (size_t)raw));
+        DEV(lsk_cross_emit(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, gt, cx->cplx, n, cx->d_dst_reps,
+                           cx->d_norms, cx->tiny, (int64_t const *)tmp[1], NULL, (int64_t *)tmp[2], tmp[3], cx->d_err, stream));
+        DEV(lsk_csr_merge(cx->cplx, n, (int64_t const *)tmp[1], (int64_t *)tmp[2], tmp[3], (int64_t *)tmp[0], stream));
+        DEV(lsk_exclusive_scan_i64(n + 1, (int64_t const *)tmp[0], out->d_row_ptr, stream));
+        DEV(lsk_sync(stream));
+        DEV(lsk_d2h(&nnz, out->d_row_ptr + n, sizeof(nnz)));
+        if (nnz < 0 || nnz > raw) return set_error("ls_amd_cross_csr: %lld entries out of %lld packets", (long long)nnz, (long long)raw);
+    } else if (!empty) DEV(lsk_memset_async(out->d_row_ptr, 0, 8 * (size_t)(n + 1), stream));
+    /* (never NULL, so that a matrix without entries still has three arrays) */
+    DEV(lsk_malloc(&p, 8 * (size_t)(nnz > 0 ? nnz : 1)));
+    out->d_col = (int64_t *)p;
+    DEV(lsk_malloc(&p, vb * (size_t)(nnz > 0 ? nnz : 1)));
+    out->d_val = p;
+    if (nnz > 0)
+        DEV(lsk_csr_write(cx->cplx, n, (int64_t const *)tmp[1], (int64_t const *)tmp[2], tmp[3], out->d_row_ptr, out->d_col, out->d_val, stream));
+    out->nnz = nnz;
+    /* an image outside the source basis: the matrix is not the operator's (synchronises) */
+    return ls_amd_cross_check(cx, stream);
+}
+
+int ls_amd_cross_csr(ls_amd_cross *cx, int64_t max_bytes, ls_amd_csr *out, void *stream) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!cx || !out) return set_error("ls_amd_cross_csr: NULL %s", !cx ? "plan" : "output");
+    int64_t const need = ls_amd_cross_csr_bytes(cx);
+    if (need > max_bytes)
+        return set_error("ls_amd_cross_csr: the export needs up to %lld bytes of device memory (%lld rows, %lld packets), max_bytes is %lld",
+                         (long long)need, (long long)cx->n_dst, (long long)cx->nnz, (long long)max_bytes);
+    out->rows = cx->n_dst; out->cols = cx->n_src;
+    out->dtype = cx->cplx ? LS_AMD_C128 : LS_AMD_F64;
+    void *tmp[4] = {NULL, NULL, NULL, NULL};
+    int const rc = cross_csr_run(cx, out, tmp, stream);
+    if (rc != 0) (void)lsk_sync(stream); /* nothing in flight may still write what is freed now */
+    for (int k = 0; k < 4; ++k) if (tmp[k]) lsk_free(tmp[k]);
+    if (rc != 0) ls_amd_csr_free(out);
+    return rc;
+}
+
 /* ============================================================================================ */
 /* sector-state expansion (include/ls_amd.h: ls_amd_expand; csrc/k_expand.hip)     */
 /* ============================================================================================ */

@@ -1,7 +1,8 @@
 // k_cross_t.hpp -- the cross-sector pull kernel k_cross_pull as a template header: k_cross.hip instantiates
 // it for the bases without permutation signs (FERMI = false), k_cross_fermi.hip for the projected fermionic ones (FERMI = true; the
 // plans call that family "k_cross_pull_fermi").  Moved out of k_cross.hip unchanged (the machine code of the 10 spin kinds is the
-// same, instruction for instruction); it gained ONE compile-time switch, FERMI, which makes stage B1 project a packet with the signed characters
+// same, instruction for instruction); it gained two compile-time switches: the emitting mode of the CSR export (on the word type,
+// see cross_emit_w below; instantiated in k_csr.hip), and FERMI, which makes stage B1 project a packet with the signed characters
 // chi(g) sign(g, a) of lsk_fermi.hpp (fermi_state_info_w) instead of state_info_w.  Nothing else in the formula changes: chr, chi
 // and stab then carry sign(g0, beta) and the signed stabiliser sum, and the zero-norm test drops the orbits whose signed sum
 // vanishes (which happens in ANY fermionic sector).  The branch is discarded at compile time by the spin instantiations.
@@ -29,14 +30,36 @@ __device__ __forceinline__ int64_t cross_index(lsk_index const &ix, uint64_t s) 
     return search_index(ix, s);
 }
 
-template <typename W, bool PM1, bool CPLX, bool REAL, bool FERMI>
+// The compile-time mode of the kernel rides on its word type, so that the apply kernels keep their five template arguments, their
+// names and their machine code: W = uint32_t / uint64_t multiplies every packet that reached a source row by x and adds it to its
+// row of y (or counts the packets, count != NULL); W = cross_emit_w<uint32_t / uint64_t> hands (row, source index, coefficient) out
+// instead -- the CSR export of k_csr.hip.  Stages A, B1, B2 are the same text for both.  The emitting mode
+// reads its arguments from the same parameter list:
+//     x      int64_t const [n_dst + 1]: first raw slot of every target row, then the number of slots; nullptr: the counting pass
+//     count  counting pass: int64_t [n_dst], the packets of every target row;  fill: int64_t [slots], the source index of every packet
+//     y      fill: the coefficient of every packet, 1 (f64) or 2 (c128) doubles
+template <typename T> struct cross_emit_w { using word = T; };
+template <typename T> struct cross_word { using word = T; static constexpr bool emit = false; };
+template <typename T> struct cross_word<cross_emit_w<T>> { using word = T; static constexpr bool emit = true; };
+
+template <typename WM, bool PM1, bool CPLX, bool REAL, bool FERMI>
 __global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group const *__restrict__ groups,
                                                        lsk_term const *__restrict__ terms, lsk_basis sbs,
                                                        lsk_group_elem const *__restrict__ elems, lsk_index six, lsk_gtab gt,
                                                        int64_t n_dst, uint64_t const *__restrict__ dst_reps,
                                                        double const *__restrict__ dst_norms, double const *__restrict__ x,
                                                        double *__restrict__ y, double tiny, unsigned long long *count, int *err) {
+    using W = typename cross_word<WM>::word;
+    constexpr bool EMIT = cross_word<WM>::emit;
     constexpr bool RC = REAL && PM1; // the coefficient stays real: real terms and +-1 source characters
+    // EMIT: a row's packets are numbered in ascending group order whatever slot of the list they took -- the group of every
+    // packet (s_g, relative to the pass), the groups of the pass that reached a source row (s_mask, one word per row) and the row's
+    // next raw slot (s_base) give packet (row, g) the slot s_base[row] + popcount(s_mask[row] below g): no order of arrival enters
+    __shared__ uint8_t s_g[EMIT ? kCapCross : 1];
+    __shared__ uint32_t s_mask[EMIT ? kBlock : 1];
+    __shared__ int64_t s_base[EMIT ? kBlock : 1];
+    int64_t const *const e_off = (int64_t const *)x;
+    int64_t *const e_out = (int64_t *)count;
     __shared__ uint64_t s_beta[kCapCross];
     __shared__ double s_coef[kCapCross * (RC ? 1 : 2)];
     __shared__ uint16_t s_row[kCapCross];
@@ -56,10 +79,14 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group c
             const double na = dst_norms[i];
             inv_na = na > 0.0 ? 1.0 / na : 0.0;
         }
-        if (CPLX) { s_acc[2 * tid] = 0.0; s_acc[2 * tid + 1] = 0.0; } else s_acc[tid] = 0.0;
+        if constexpr (!EMIT) { if (CPLX) { s_acc[2 * tid] = 0.0; s_acc[2 * tid + 1] = 0.0; } else s_acc[tid] = 0.0; }
         unsigned long long found = 0;
         for (int g0 = 0; g0 < n_groups; g0 += kGCCross) {
             if (tid == 0) s_n = 0;
+            if constexpr (EMIT) { // (the fills of the pass before are behind its closing barrier)
+                s_base[tid] = g0 == 0 ? (valid && e_off ? e_off[i] : 0) : s_base[tid] + __popc(s_mask[tid]);
+                s_mask[tid] = 0;
+            }
             __syncthreads();
             // ---- stage A: the adjoint's groups of every row -> packets (state, conj(c) / n2(r'), row) ------------------
             const int g1 = min(g0 + kGCCross, n_groups);
@@ -77,6 +104,7 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group c
                     const int slot = base + __popcll(ball & ((1ULL << lane) - 1));
                     s_beta[slot] = a ^ G.x;
                     s_row[slot] = (uint16_t)tid;
+                    if constexpr (EMIT) s_g[slot] = (uint8_t)(g - g0);
                     if (RC) s_coef[slot] = cr * inv_na;
                     else { s_coef[2 * slot] = cr * inv_na; s_coef[2 * slot + 1] = -ci * inv_na; }
                 }
@@ -131,7 +159,26 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group c
                     if (idx[k] < 0 || idx[k] >= six.count) { idx[k] = -1; atomicExch(err, 1); } // an image that is not in the source basis
                     else ++found;
                 }
-                if (!count) {
+                if constexpr (EMIT) {
+#pragma unroll
+                    for (int k = 0; k < kGCCross; ++k)
+                        if (idx[k] >= 0) atomicOr(&s_mask[s_row[tid + k * kBlock]], 1u << s_g[tid + k * kBlock]);
+                    __syncthreads();
+                    if (e_off) {
+                        const int64_t slots = e_off[n_dst];
+#pragma unroll
+                        for (int k = 0; k < kGCCross; ++k) {
+                            if (idx[k] < 0) continue;
+                            const int e = tid + k * kBlock;
+                            const int r = s_row[e];
+                            const int64_t slot = s_base[r] + __popc(s_mask[r] & ((1u << s_g[e]) - 1u));
+                            if (slot < 0 || slot >= slots) { atomicExch(err, 1); continue; } // (the counting pass saw another matrix)
+                            e_out[slot] = idx[k];
+                            if (CPLX) { y[2 * slot] = RC ? s_coef[e] : s_coef[2 * e]; y[2 * slot + 1] = RC ? 0.0 : s_coef[2 * e + 1]; }
+                            else y[slot] = s_coef[e];
+                        }
+                    }
+                } else if (!count) {
                     double xr[kGCCross], xi[kGCCross];
 #pragma unroll
                     for (int k = 0; k < kGCCross; ++k) {
@@ -156,7 +203,8 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group c
             }
             __syncthreads();
         }
-        if (count) { if (found) atomicAdd(count, found); }
+        if constexpr (EMIT) { if (valid && !e_off) e_out[i] = s_base[tid] + __popc(s_mask[tid]); }
+        else if (count) { if (found) atomicAdd(count, found); }
         else if (valid) {
             if (CPLX) { y[2 * i] = s_acc[2 * tid]; y[2 * i + 1] = s_acc[2 * tid + 1]; } else y[i] = s_acc[tid];
         }

@@ -576,6 +576,23 @@ int lsk_cross_fermi_pull(int n_groups, lsk_group const *groups, lsk_term const *
                          lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, void const *x, void *y,
                          double tiny, unsigned long long *d_count, int *d_err, void *stream);
 
+/* the matrix of a cross-sector plan in CSR form (k_csr.hip).  lsk_cross_emit runs stages A, B1, B2 of
+ * k_cross_pull (the arguments of lsk_cross_pull; either family) and, instead of gathering from x, hands every packet that reached a
+ * source row out: off == NULL counts them per target row (cnt[i], i < n_dst); otherwise (off: n_dst + 1 entries, the exclusive scan
+ * of the counts and their sum) packet k of row i -- k counts the row's packets in ascending group order -- is stored as
+ * col[off[i] + k] = source index, val[off[i] + k] = its coefficient (1 or 2 doubles).  Plain stores, every slot written once; a
+ * slot at or beyond off[n_dst] raises *d_err and is not stored. */
+int lsk_cross_emit(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six, lsk_gtab gt,
+                   int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, double tiny, int64_t const *off,
+                   int64_t *cnt, int64_t *col, void *val, int *d_err, void *stream);
+/* one wave per row over the raw entries [off[i], off[i + 1]): the first entry of every column receives the sum of the column's
+ * entries, added in ascending position; every other entry, and a sum with |sum| <= 1e-12 sum |s|, is marked col = -2 - col.
+ * cnt[i] = the entries left. */
+int lsk_csr_merge(int cplx, int64_t n_rows, int64_t const *off, int64_t *col, void *val, int64_t *cnt, void *stream);
+/* the entries lsk_csr_merge left, in ascending column order: entry of rank k of row i -> out[row_ptr[i] + k] */
+int lsk_csr_write(int cplx, int64_t n_rows, int64_t const *off, int64_t const *col, void const *val, int64_t const *row_ptr,
+                  int64_t *out_col, void *out_val, void *stream);
+
 /* sector-state expansion (k_expand.hip): the vector psi on the representatives reps[0, n) of a spin basis, scattered over the orbits
  * of the representatives into the matrix M[a, b] = <a, b|psi> of a bipartition -- the image s = g r of row r
  * under group element g (and its flipped image under the spin inversion) receives conj(chi(g)) norms[r] psi[r], at

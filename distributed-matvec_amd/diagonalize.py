@@ -650,6 +650,78 @@ def diagonalize(config, num_evals: int = 1, eps: float = 1e-6, num_partitions: i
     return r
 
 
+@dataclass
+class SpectrumResult:
+    """full_spectrum: every eigenvalue of one sector (ascending, numpy); the eigenvectors as the columns of a device (n, n) tensor
+    over the representatives, or None; the representatives (device int64); n; wall seconds of the whole call"""
+    eigenvalues: object
+    eigenvectors: object
+    representatives: object
+    dimension: int
+    seconds: float = 0.0
+
+
+def _unprojected_dimension(basis):
+    """the number of states of a basis without symmetries, from its quantum numbers alone (host only); None for a projected basis,
+    whose dimension is known once its representatives are enumerated"""
+    if basis.requiresProjection():
+        return None
+    L, n, up, kind = basis.numberSites(), basis.numberParticles(), basis.numberUp(), basis.particleType()
+    if kind == 1:  # spinful fermions: (N, N_up) product basis, N alone over the 2 L modes, or everything
+        if up >= 0 and n >= 0:
+            return math.comb(L, up) * math.comb(L, n - up)
+        return math.comb(2 * L, n) if n >= 0 else 4 ** L
+    fixed = n if kind == 2 else up  # spinless fermions: particles; spins: the Hamming weight
+    return math.comb(L, fixed) if fixed >= 0 else 2 ** L
+
+
+def _refuse_dimension(n, max_dim, itemsize):
+    if n > max_dim:
+        raise ValueError(f"full_spectrum: the sector has {n} states, the dense matrix {n * n * itemsize} bytes; max_dim is {max_dim} "
+                         "(the few lowest levels of a larger sector: diagonalize())")
+
+
+def full_spectrum(config, eigenvectors: bool = False, dtype=None, max_dim: int = 32768):
+    """Every eigenvalue (eigenvectors=True: and eigenvector) of the configured Hamiltonian (dict or YAML path) on its sector: the
+    representatives are enumerated, the sector matrix is exported in O(nnz) (Operator.to_csr), made dense and handed to
+    torch.linalg.eigvalsh / eigh on the device.  dtype None: float64 for a real operator and +-1 characters, else complex128.
+    ValueError before anything is allocated for a Hamiltonian that is not Hermitian and for a sector of more than max_dim states
+    (an unprojected basis is refused from its quantum numbers, before a device is asked for; a projected one once its
+    representatives are counted); LsAmdError when the exported matrix is not Hermitian to 1e-12 max|H|."""
+    import numpy as np
+    import torch
+
+    from . import api
+
+    t0 = time.perf_counter()
+    load = api.loadConfigFromYaml if isinstance(config, str) else api.loadConfigFromDict
+    basis, h = load(config, hamiltonian=True)
+    if not h.isHermitian:
+        raise ValueError("full_spectrum: the Hamiltonian is not Hermitian (a dense Hermitian solver is used)")
+    if isinstance(max_dim, bool) or not isinstance(max_dim, int) or max_dim < 1:
+        raise ValueError(f"max_dim = {max_dim!r}: a positive integer")
+    if dtype is None:
+        dtype = torch.float64 if h.isReal and not api._complex_characters(basis) else torch.complex128
+    itemsize = 16 if dtype in (torch.complex128, "c128") else 8
+    known = _unprojected_dimension(basis)
+    if known is not None:
+        _refuse_dimension(known, max_dim, itemsize)
+    reps, _ = api.enumerateStates(basis, 1)
+    n = int(reps[0].numel())
+    _refuse_dimension(n, max_dim, itemsize)
+    H = h.to_dense(reps, dtype=dtype, max_bytes=max(8 << 30, 2 * n * n * itemsize))
+    scale = float(H.abs().max()) if n else 0.0
+    defect = float((H - H.mH).abs().max()) if n else 0.0
+    if defect > 1e-12 * scale:
+        raise api.LsAmdError(f"full_spectrum: the sector matrix is not Hermitian: max|H - H^+| = {defect:.3e}, max|H| = {scale:.3e}")
+    if eigenvectors:
+        vals, vecs = torch.linalg.eigh(H)
+    else:
+        vals, vecs = torch.linalg.eigvalsh(H), None
+    vals = vals.cpu().numpy().astype(np.float64)
+    return SpectrumResult(vals, vecs, reps[0], n, time.perf_counter() - t0)
+
+
 def diagonalize_distributed(config, group=None, num_evals: int = 1, eps: float = 1e-6, dtype=None, output: str | None = None,
                             exchange: str = "auto", max_basis: int = 24, verbose: bool = False):
     """`Diagonalize.main` (Diagonalize.chpl:258-332) with one process per GPU: every rank enumerates the basis on its device,

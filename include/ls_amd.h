@@ -529,6 +529,30 @@ char const *ls_amd_cross_kernel_name(ls_amd_cross const *plan); /* "k_cross_pull
 int64_t ls_amd_cross_nnz(ls_amd_cross const *plan);
 void ls_amd_cross_destroy(ls_amd_cross *plan);
 
+/* The matrix of a plan, M[i, j] = the number ls_amd_cross_apply multiplies x[j] by in row i (y = M x; rows: the target's
+ * representatives, columns: the source's), as canonical CSR in library-owned device arrays:
+ *     d_row_ptr  int64 [rows + 1]   d_row_ptr[0] = 0, d_row_ptr[rows] = nnz; row i holds the entries [d_row_ptr[i], d_row_ptr[i + 1])
+ *     d_col      int64 [nnz]        strictly ascending inside every row, 0 <= col < cols
+ *     d_val      dtype [nnz]        double, or (re, im) pairs of doubles
+ * (d_col and d_val are allocated, never NULL, when nnz = 0).  The packets of a row that reach the same source state are summed in
+ * ascending order of the adjoint's flip-mask groups, and a sum that cancels -- |sum s| <= 1e-12 sum |s| -- is no entry, so
+ * nnz <= ls_amd_cross_nnz.  No atomics, no order of arrival: two exports of one plan are the same bytes.  Built in O(nnz) by the
+ * plan's own kernel in an emitting mode and two per-row passes (csrc/k_csr.hip); synchronises `stream`. */
+typedef struct ls_amd_csr {
+    int64_t rows, cols, nnz;
+    ls_amd_dtype dtype;
+    int64_t *d_row_ptr, *d_col;
+    void *d_val;
+} ls_amd_csr;
+/* upper bound of the peak device bytes of ls_amd_cross_csr -- the raw and the final entries, the row offsets -- from
+ * ls_amd_cross_nnz, the number of target rows and the dtype; needs no device.  -1: NULL plan. */
+int64_t ls_amd_cross_csr_bytes(ls_amd_cross const *plan);
+/* Fills *out (cleared first).  -1 with a message that names both numbers, before anything is allocated, when
+ * ls_amd_cross_csr_bytes exceeds max_bytes; -1 with the message of ls_amd_cross_check when an image of A+ with non-zero source norm
+ * is not in the source basis (nothing is left allocated).  Release with ls_amd_csr_free. */
+int ls_amd_cross_csr(ls_amd_cross *plan, int64_t max_bytes, ls_amd_csr *out, void *stream);
+void ls_amd_csr_free(ls_amd_csr *m); /* frees the three arrays and clears *m; NULL and cleared structs are fine */
+
 /* sector-state expansion and bipartitions -----------------------------------------------------------------------------------------
  * A state psi on the representatives of a symmetry sector (an eigenvector, say), expanded to its amplitudes on product states:
  * with the basis vectors |r~> = P|r> / |P|r>| of the projector above and state_info(s) = (rep, character, norm) of a full-basis state s,
