@@ -5725,23 +5725,21 @@ int ls_amd_cross_csr(ls_amd_cross *cx, int64_t max_bytes, ls_amd_csr *out, void 
 /* ============================================================================================ */
 /* sector-state expansion (include/ls_amd.h: ls_amd_expand; csrc/k_expand.hip)     */
 /* ============================================================================================ */
+#define EXPAND_MAX_BLOCKS LSK_EXPAND_FERMI_TAB /* fixed weight: n_A = 0 .. 64; the spinful product basis: (n_up, n_dn), 0 .. 32 each */
 typedef struct expand_layout {
     int L, weight, n_a, n_b, split, nb;
-    int na[LSK_EXPAND_MAX_NA];
-    int64_t rows[LSK_EXPAND_MAX_NA], cols[LSK_EXPAND_MAX_NA], off[LSK_EXPAND_MAX_NA], total;
+    int kind, half, au, ad, n_up, n_dn; /* fermionic plans: LSK_EXPAND_FERMI_*; PRODUCT: L, the up / down modes of A, (N_up, N_down) */
+    int na[EXPAND_MAX_BLOCKS];          /* n_A of the block (PRODUCT: n_up + n_dn; -1 without a fixed number) */
+    int nd[EXPAND_MAX_BLOCKS];          /* PRODUCT: n_dn of the block; -1 on every other layout of a fermionic plan */
+    int64_t rows[EXPAND_MAX_BLOCKS], cols[EXPAND_MAX_BLOCKS], off[EXPAND_MAX_BLOCKS], total;
 } expand_layout;
 
-/* the block table of a bipartition: host only.  The refusals of ls_amd_expand_create that need no device live here. */
-static int expand_layout_of(ls_hs_basis const *basis, uint64_t mask_a, expand_layout *lay) {
-    if (!basis) return set_error("ls_amd_expand: NULL basis");
-    if (basis->particle_type != LS_HS_SPIN)
-        return set_error("ls_amd_expand: fermionic bases are not supported -- the partial trace of fermions needs the mode-ordering signs of "
-                         "moving the modes of the subsystem in front of the others, which the expansion does not carry yet");
-    struct ls_amd_basis_ext const *e = BEXT(basis);
-    int const L = e->nbits, w = e->hamming_weight;
+/* the layout of a basis of L-bit words with Hamming weight w (-1: every word): one block per n_A, or one 2^|A| x 2^|B| block.
+ * `who` / `noun` word the refusals of the spin entry points ("sites") and of the fermionic ones ("modes"). */
+static int expand_layout_weight(expand_layout *lay, char const *who, char const *noun, int L, int w, uint64_t mask_a) {
     uint64_t const sites = L >= 64 ? ~0ULL : ((1ULL << L) - 1);
-    if (mask_a & ~sites) return set_error("ls_amd_expand: the subsystem mask 0x%llx has bits outside the %d sites", (unsigned long long)mask_a, L);
-    if (w >= LSK_BINOM_K) return set_error("ls_amd_expand: Hamming weight %d is beyond the binomial table (%d)", w, LSK_BINOM_K - 1);
+    if (mask_a & ~sites) return set_error("%s: the subsystem mask 0x%llx has bits outside the %d %s", who, (unsigned long long)mask_a, L, noun);
+    if (w >= LSK_BINOM_K) return set_error("%s: Hamming weight %d is beyond the binomial table (%d)", who, w, LSK_BINOM_K - 1);
     memset(lay, 0, sizeof(*lay));
     lay->L = L; lay->weight = w;
     lay->n_a = __builtin_popcountll(mask_a);
@@ -5750,22 +5748,72 @@ static int expand_layout_of(ls_hs_basis const *basis, uint64_t mask_a, expand_la
     else if (mask_a == (sites & ~((1ULL << lay->n_b) - 1))) lay->split = LSK_SPLIT_HIGH;
     else lay->split = LSK_SPLIT_GATHER;
     if (w < 0) {
-        if (L > 40) return set_error("ls_amd_expand: %d sites without a fixed Hamming weight expand to 2^%d elements", L, L);
+        if (L > 40) return set_error("%s: %d %s without a fixed Hamming weight expand to 2^%d elements", who, L, noun, L);
+        lay->kind = LSK_EXPAND_FERMI_ALL;
         lay->nb = 1;
-        lay->na[0] = -1;
+        lay->na[0] = -1; lay->nd[0] = -1;
         lay->rows[0] = (int64_t)1 << lay->n_a; lay->cols[0] = (int64_t)1 << lay->n_b;
         lay->total = (int64_t)1 << L;
         return 0;
     }
+    lay->kind = LSK_EXPAND_FERMI_FIXED;
     for (int na = 0; na <= lay->n_a && na <= w; ++na) {
         uint64_t const r = binom(lay->n_a, na), c = binom(lay->n_b, w - na);
         if (r == 0 || c == 0) continue; /* empty blocks are omitted */
         long double const sz = (long double)r * (long double)c;
-        if (sz + (long double)lay->total > 4.0e18L) return set_error("ls_amd_expand: the expansion has more than 2^62 elements");
+        if (sz + (long double)lay->total > 4.0e18L) return set_error("%s: the expansion has more than 2^62 elements", who);
         int const i = lay->nb++;
-        lay->na[i] = na; lay->rows[i] = (int64_t)r; lay->cols[i] = (int64_t)c; lay->off[i] = lay->total;
+        lay->na[i] = na; lay->nd[i] = -1; lay->rows[i] = (int64_t)r; lay->cols[i] = (int64_t)c; lay->off[i] = lay->total;
         lay->total += (int64_t)(r * c);
     }
+    return 0;
+}
+
+/* the block table of a bipartition: host only.  The refusals of ls_amd_expand_create that need no device live here. */
+static int expand_layout_of(ls_hs_basis const *basis, uint64_t mask_a, expand_layout *lay) {
+    if (!basis) return set_error("ls_amd_expand: NULL basis");
+    if (basis->particle_type != LS_HS_SPIN)
+        return set_error("ls_amd_expand: fermionic bases are not supported here -- the partial trace of fermions needs the mode-ordering signs of "
+                         "moving the modes of the subsystem in front of the others, which ls_amd_fermi_expand_create carries");
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    return expand_layout_weight(lay, "ls_amd_expand", "sites", e->nbits, e->hamming_weight, mask_a);
+}
+
+/* ... of a fermionic basis (ls_amd_fermi_expand_create).  Spinless bases, and spinful ones with number_up unset (spinless over their
+ * 2 L modes), take the layout above over their modes; the spinful (N, N_up) product basis one block per (n_up, n_dn) of the up and
+ * down modes of A, ordered lexicographically: rows C(|A_up|, n_up) C(|A_dn|, n_dn), columns C(L - |A_up|, N_up - n_up)
+ * C(L - |A_dn|, N_dn - n_dn) (include/ls_amd.h). */
+static int fermi_expand_layout_of(ls_hs_basis const *basis, uint64_t mask_a, expand_layout *lay) {
+    char const *who = "ls_amd_fermi_expand";
+    if (!basis) return set_error("%s: NULL basis", who);
+    if (basis->particle_type == LS_HS_SPIN)
+        return set_error("%s: a spin-1/2 basis has no mode-ordering signs: it is expanded by ls_amd_expand_create (SectorExpansion)", who);
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    if (basis->spin_inversion != 0) return set_error("%s: a fermionic basis has no spin inversion", who);
+    if (!e->product) return expand_layout_weight(lay, who, "modes", e->nbits, e->hamming_weight, mask_a);
+    int const L = basis->number_sites, M = 2 * L; /* L <= 32 */
+    uint64_t const modes = M >= 64 ? ~0ULL : ((1ULL << M) - 1), low = (1ULL << L) - 1;
+    if (mask_a & ~modes) return set_error("%s: the subsystem mask 0x%llx has bits outside the %d modes", who, (unsigned long long)mask_a, M);
+    memset(lay, 0, sizeof(*lay));
+    lay->L = M; lay->weight = -1;
+    lay->kind = LSK_EXPAND_FERMI_PRODUCT;
+    lay->half = L; lay->n_up = e->prod_up; lay->n_dn = e->prod_dn;
+    lay->n_a = __builtin_popcountll(mask_a);
+    lay->n_b = M - lay->n_a;
+    lay->au = __builtin_popcountll(mask_a & low); lay->ad = lay->n_a - lay->au;
+    if (mask_a == (lay->n_a >= 64 ? ~0ULL : ((1ULL << lay->n_a) - 1))) lay->split = LSK_SPLIT_LOW;
+    else if (mask_a == (modes & ~((1ULL << lay->n_b) - 1))) lay->split = LSK_SPLIT_HIGH;
+    else lay->split = LSK_SPLIT_GATHER;
+    for (int nu = 0; nu <= lay->au && nu <= lay->n_up; ++nu)
+        for (int nd = 0; nd <= lay->ad && nd <= lay->n_dn; ++nd) {
+            long double const r = (long double)binom(lay->au, nu) * (long double)binom(lay->ad, nd);
+            long double const c = (long double)binom(L - lay->au, lay->n_up - nu) * (long double)binom(L - lay->ad, lay->n_dn - nd);
+            if (r == 0 || c == 0) continue; /* empty blocks are omitted */
+            if (r * c + (long double)lay->total > 4.0e18L) return set_error("%s: the expansion has more than 2^62 elements", who);
+            int const i = lay->nb++;
+            lay->na[i] = nu + nd; lay->nd[i] = nd; lay->rows[i] = (int64_t)r; lay->cols[i] = (int64_t)c; lay->off[i] = lay->total;
+            lay->total += (int64_t)r * (int64_t)c;
+        }
     return 0;
 }
 
@@ -5783,13 +5831,38 @@ int ls_amd_test_expand_layout(ls_hs_basis const *basis, uint64_t subsystem_mask,
     return lay.nb;
 }
 
+int ls_amd_test_fermi_expand_layout(ls_hs_basis const *basis, uint64_t mode_mask, int capacity, int *n_up, int *n_dn, int64_t *rows,
+                                    int64_t *cols, int64_t *offsets, int64_t *total) {
+    expand_layout lay;
+    if (fermi_expand_layout_of(basis, mode_mask, &lay) != 0) return -1;
+    for (int i = 0; i < lay.nb && i < capacity; ++i) {
+        if (n_up) n_up[i] = lay.nd[i] < 0 ? lay.na[i] : lay.na[i] - lay.nd[i];
+        if (n_dn) n_dn[i] = lay.nd[i];
+        if (rows) rows[i] = lay.rows[i];
+        if (cols) cols[i] = lay.cols[i];
+        if (offsets) offsets[i] = lay.off[i];
+    }
+    if (total) *total = lay.total;
+    return lay.nb;
+}
+
+/* test hook (no device): sigma(state) = +-1 of the bipartition A = mode_mask_a | the other modes of a word of `modes` modes, by the
+ * device code's host run (fermi_split_parity, lsk_fermi.hpp); 0 on bad arguments */
+int ls_amd_test_fermi_split_parity(uint64_t mode_mask_a, int modes, uint64_t state) {
+    if (modes < 1 || modes > 64) return 0;
+    uint64_t const all = modes >= 64 ? ~0ULL : ((1ULL << modes) - 1);
+    if ((mode_mask_a & ~all) || (state & ~all)) return 0;
+    return lsk_test_fermi_split_parity(state, mode_mask_a, all & ~mode_mask_a) ? -1 : 1;
+}
+
 struct ls_amd_expand {
     lsk_basis bs;             /* device tables owned by the basis */
     expand_layout lay;
     uint64_t mask_a;
     int pm1;                  /* every character is +-1: f64 allowed */
+    int fermi;                /* a plan of ls_amd_fermi_expand_create: k_expand_push_fermi */
     double *d_norms;          /* owned: n(r) of every row */
-    int64_t *d_tab;           /* owned: the block table by n_A (lsk_expand.tab); NULL without a fixed weight */
+    int64_t *d_tab;           /* owned: the block table by n_A (lsk_expand.tab) or by (n_up, n_dn) (lsk_expand_fermi.tab); NULL without a fixed weight */
     int *d_err;               /* owned */
     uint64_t const *d_reps;   /* borrowed */
     uint64_t const *d_binom;
@@ -5816,7 +5889,13 @@ static int expand_setup(ls_amd_expand *ex, ls_hs_basis const *basis, void *strea
     ex->d_norms = (double *)p;
     /* the stabiliser norms, by the routine the matvec and cross-sector plans use (an unprojected basis: the identity alone, n = 1) */
     DEV(lsk_norms(ex->bs, ex->n, ex->d_reps, ex->d_norms, stream));
-    if (ex->lay.weight >= 0) {
+    if (ex->fermi && ex->lay.kind == LSK_EXPAND_FERMI_PRODUCT) {
+        int64_t tab[LSK_EXPAND_FERMI_TAB];
+        for (int i = 0; i < LSK_EXPAND_FERMI_TAB; ++i) tab[i] = -1;
+        for (int i = 0; i < ex->lay.nb; ++i) tab[(ex->lay.na[i] - ex->lay.nd[i]) * (ex->lay.ad + 1) + ex->lay.nd[i]] = ex->lay.off[i];
+        if (upload(&p, tab, sizeof(tab)) != 0) return -1;
+        ex->d_tab = (int64_t *)p;
+    } else if (ex->lay.weight >= 0) {
         int64_t tab[2 * LSK_EXPAND_MAX_NA];
         for (int i = 0; i < LSK_EXPAND_MAX_NA; ++i) { tab[i] = -1; tab[LSK_EXPAND_MAX_NA + i] = 0; }
         for (int i = 0; i < ex->lay.nb; ++i) { tab[ex->lay.na[i]] = ex->lay.off[i]; tab[LSK_EXPAND_MAX_NA + ex->lay.na[i]] = ex->lay.cols[i]; }
@@ -5843,6 +5922,21 @@ int ls_amd_expand_create(ls_amd_expand **out, ls_hs_basis const *basis, uint64_t
     return 0;
 }
 
+int ls_amd_fermi_expand_create(ls_amd_expand **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, uint64_t mode_mask,
+                               void *stream) {
+    if (out) *out = NULL;
+    if (!out || !basis) return set_error("ls_amd_fermi_expand_create: NULL %s", !out ? "handle" : "basis");
+    if (n < 0 || (n > 0 && !d_reps)) return set_error("ls_amd_fermi_expand_create: NULL representatives or a negative count");
+    ls_amd_expand *ex = (ls_amd_expand *)calloc(1, sizeof(*ex));
+    if (fermi_expand_layout_of(basis, mode_mask, &ex->lay) != 0) { free(ex); return -1; }
+    ex->fermi = 1;
+    ex->mask_a = mode_mask;
+    ex->d_reps = d_reps; ex->n = n;
+    if (expand_setup(ex, basis, stream) != 0) { ls_amd_expand_destroy(ex); return -1; }
+    *out = ex;
+    return 0;
+}
+
 int ls_amd_expand_num_blocks(ls_amd_expand const *ex) {
     if (!ex) return set_error("ls_amd_expand_num_blocks: NULL plan");
     return ex->lay.nb;
@@ -5851,6 +5945,17 @@ int ls_amd_expand_block(ls_amd_expand const *ex, int i, int *n_a, int64_t *rows,
     if (!ex) return set_error("ls_amd_expand_block: NULL plan");
     if (i < 0 || i >= ex->lay.nb) return set_error("ls_amd_expand_block: block %d of %d", i, ex->lay.nb);
     if (n_a) *n_a = ex->lay.na[i];
+    if (rows) *rows = ex->lay.rows[i];
+    if (cols) *cols = ex->lay.cols[i];
+    if (offset) *offset = ex->lay.off[i];
+    return 0;
+}
+int ls_amd_fermi_expand_block(ls_amd_expand const *ex, int i, int *n_up, int *n_dn, int64_t *rows, int64_t *cols, int64_t *offset) {
+    if (!ex) return set_error("ls_amd_fermi_expand_block: NULL plan");
+    if (!ex->fermi) return set_error("ls_amd_fermi_expand_block: the plan of a spin basis (ls_amd_expand_block)");
+    if (i < 0 || i >= ex->lay.nb) return set_error("ls_amd_fermi_expand_block: block %d of %d", i, ex->lay.nb);
+    if (n_up) *n_up = ex->lay.nd[i] < 0 ? ex->lay.na[i] : ex->lay.na[i] - ex->lay.nd[i];
+    if (n_dn) *n_dn = ex->lay.nd[i];
     if (rows) *rows = ex->lay.rows[i];
     if (cols) *cols = ex->lay.cols[i];
     if (offset) *offset = ex->lay.off[i];
@@ -5875,6 +5980,24 @@ int ls_amd_expand_apply(ls_amd_expand *ex, ls_amd_dtype dtype, void const *d_psi
     /* the selected blocks lie one after another: one clear, then the scatter assigns what the orbits reach */
     DEV(lsk_memset_async((char *)d_out + (size_t)begin * elt, 0, (size_t)(end - begin) * elt, stream));
     if (ex->n == 0) return 0;
+    if (ex->fermi) {
+        expand_layout const *lay = &ex->lay;
+        lsk_expand_fermi f;
+        memset(&f, 0, sizeof(f));
+        f.mask_a = ex->mask_a; f.mask_b = ex->bs.site_mask & ~ex->mask_a;
+        f.n_a = lay->n_a; f.n_b = lay->n_b;
+        f.split = lay->split;
+        f.kind = lay->kind;
+        f.half = lay->half; f.au = lay->au; f.ad = lay->ad; f.n_up = lay->n_up; f.n_dn = lay->n_dn;
+        if (lay->kind == LSK_EXPAND_FERMI_PRODUCT) { /* lexicographic in (n_up, n_dn) = ascending in the key */
+            f.lo = (lay->na[first_block] - lay->nd[first_block]) * (lay->ad + 1) + lay->nd[first_block];
+            f.hi = (lay->na[last] - lay->nd[last]) * (lay->ad + 1) + lay->nd[last];
+        } else { f.lo = lay->na[first_block]; f.hi = lay->na[last]; }
+        f.tab = ex->d_tab;
+        f.cols = lay->cols[0];
+        DEV(lsk_expand_fermi_push(ex->bs, f, ex->d_binom, cplx, ex->n, ex->d_reps, ex->d_norms, d_psi, d_out, ex->d_err, stream));
+        return 0;
+    }
     lsk_expand k;
     memset(&k, 0, sizeof(k));
     k.mask_a = ex->mask_a;
@@ -5894,6 +6017,9 @@ int ls_amd_expand_check(ls_amd_expand *ex, void *stream) {
     DEV(lsk_d2h(&flag, ex->d_err, sizeof(int)));
     if (flag) {
         DEV(lsk_h2d(ex->d_err, &zero, sizeof(int)));
+        if (ex->fermi)
+            return set_error("sector expansion: a representative or one of its images is not a state of the basis (another particle number "
+                             "of the word or of a species, or bits above the %d modes): the array does not belong to this basis", ex->lay.L);
         return set_error("sector expansion: a representative or one of its images is not a state of the basis (another Hamming weight, "
                          "or bits above the %d sites): the array does not belong to this basis", ex->lay.L);
     }
@@ -5902,5 +6028,5 @@ int ls_amd_expand_check(ls_amd_expand *ex, void *stream) {
 
 char const *ls_amd_expand_kernel_name(ls_amd_expand const *ex) {
     if (!ex) { set_error("ls_amd_expand_kernel_name: NULL plan"); return NULL; }
-    return lsk_expand_kernel_name();
+    return ex->fermi ? lsk_expand_fermi_kernel_name() : lsk_expand_kernel_name();
 }

@@ -7,6 +7,7 @@
 // stabiliser), so plain stores are enough.  States of zero-norm orbits receive nothing: the host clears the blocks first.
 // Lane mapping: one ROW per lane, the element loop outside -- the element descriptor (network masks, character) is wave-uniform and
 // stays in scalar registers, as in state_info_w; blockIdx.y deals the elements to several blocks when there are few row tiles.
+// Spin-1/2 bases; the fermionic variant with the orbit sign and the sign of the bipartition is k_expand_push_fermi (k_expand_fermi.hip).
 #include "lsk_dev.hpp"
 
 extern "C" char const *lsk_expand_kernel_name(void) { return "k_expand_push"; }
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_expand_push(lsk_basis bs, lsk_group_
 extern "C" int lsk_expand_push(lsk_basis bs, lsk_expand ex, uint64_t const *d_binom, int cplx, int64_t n, uint64_t const *reps,
                                double const *norms, void const *psi, void *out, int *d_err, void *stream) {
     if (n <= 0) return 0;
-    if (bs.fermi) { snprintf(g_err, sizeof(g_err), "%s: fermionic bases are not expanded (mode-ordering signs)", __func__); return -1; }
+    if (bs.fermi) { snprintf(g_err, sizeof(g_err), "%s: fermionic bases are not expanded here (mode-ordering signs: lsk_expand_fermi_push)", __func__); return -1; }
     if (!cplx && !bs.chars_pm1) { snprintf(g_err, sizeof(g_err), "%s: f64 needs +-1 characters", __func__); return -1; }
     const bool fixed = bs.hamming_weight >= 0;
     if (fixed && (!ex.tab || bs.hamming_weight >= LSK_BINOM_K)) { snprintf(g_err, sizeof(g_err), "%s: no block table, or a weight beyond the binomial table", __func__); return -1; }

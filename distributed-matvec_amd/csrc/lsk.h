@@ -616,6 +616,38 @@ char const *lsk_expand_kernel_name(void);
 int lsk_expand_push(lsk_basis bs, lsk_expand ex, uint64_t const *d_binom, int cplx, int64_t n, uint64_t const *reps, double const *norms,
                     void const *psi, void *out, int *d_err, void *stream);
 
+/* the same for fermionic bases (k_expand_fermi.hip, k_expand_push_fermi): the image s = g r receives
+ *     sigma(s) conj(chi(g)) sign(g, r) norms[r] psi[r]
+ * with sign(g, r) of lsk_fermi.hpp (projected bases; a basis without a group has the identity alone) and sigma(s) the sign of
+ * carrying the modes of A in front of those of B (fermi_split_parity).  No spin inversion.  Block layouts:
+ *     ALL:      no fixed particle number -- a * cols + b                                                       (one block)
+ *     FIXED:    the table and the formula of lsk_expand                                                         (one block per n_A)
+ *     PRODUCT:  the spinful (N_up, N_down) basis over 2 `half` modes, A = `au` up modes + `ad` down modes       (one block per (n_up, n_dn))
+ *               a = a_dn << au | a_up, b = b_dn << (half - au) | b_up;  tab[n_up * (ad + 1) + n_dn] + row * cols + col,
+ *               row = rank(a_dn) C(au, n_up) + rank(a_up),  col = rank(b_dn) C(half - au, N_up - n_up) + rank(b_up),
+ *               cols = C(half - au, N_up - n_up) C(half - ad, N_dn - n_dn)
+ * Images whose block key (n_A; n_up * (ad + 1) + n_dn) is outside [lo, hi] are skipped.  *d_err is raised by a row or an image that is
+ * not a state of the basis (bits above the modes, another particle number in the word or in one of its halves); nothing is stored
+ * for it. */
+enum { LSK_EXPAND_FERMI_ALL = 0, LSK_EXPAND_FERMI_FIXED = 1, LSK_EXPAND_FERMI_PRODUCT = 2 };
+#define LSK_EXPAND_FERMI_TAB (33 * 33) /* PRODUCT: n_up, n_dn = 0 .. 32 */
+typedef struct lsk_expand_fermi {
+    uint64_t mask_a, mask_b; /* the modes of A, and all the others */
+    int n_a, n_b;            /* |A|, |B| */
+    int split;               /* LSK_SPLIT_* */
+    int kind;                /* LSK_EXPAND_FERMI_* */
+    int lo, hi;              /* the block keys to write */
+    int half, au, ad;        /* PRODUCT: L; the up / down modes of A */
+    int n_up, n_dn;          /* PRODUCT: the particle numbers of the halves */
+    int64_t const *tab;      /* FIXED: as lsk_expand.tab; PRODUCT: device [(au + 1) * (ad + 1)] first elements (-1: no such block) */
+    int64_t cols;            /* ALL: 2^n_b */
+} lsk_expand_fermi;
+char const *lsk_expand_fermi_kernel_name(void);
+int lsk_expand_fermi_push(lsk_basis bs, lsk_expand_fermi ex, uint64_t const *d_binom, int cplx, int64_t n, uint64_t const *reps,
+                          double const *norms, void const *psi, void *out, int *d_err, void *stream);
+/* parity of sigma(n) (host run of the device code) */
+int lsk_test_fermi_split_parity(uint64_t n, uint64_t mask_a, uint64_t mask_b);
+
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */
 int lsk_norms(lsk_basis bs, int64_t n, uint64_t const *reps, double *norms, void *stream);

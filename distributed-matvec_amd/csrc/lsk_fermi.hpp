@@ -13,7 +13,8 @@
 // rotation / reflection has a closed form per half (the LSK_ELEM_LIFT kinds of lsk.h) instead of a network and one table load per
 // particle.
 // Everything here is a template or __host__ __device__: k_fermi.hip uses it, k_pull_t.hpp compiles it into the fermionic
-// k_pull_t instantiations, and lsk_test_fermi_parity runs the same code on the host.
+// k_pull_t instantiations, and lsk_test_fermi_parity runs the same code on the host.  k_expand_fermi.hip takes the element signs
+// and the sign of a bipartition (fermi_split_parity, below) from here; lsk_test_fermi_split_parity is its host run.
 #pragma once
 #include "lsk.h"
 
@@ -69,6 +70,25 @@ __host__ __device__ __forceinline__ int fermi_parity(lsk_group_elem const &e, ui
     const int lo = k ? fermi_popc<W>(w & (W)(((W)1 << k) - 1)) : 0;
     const int hi = fermi_popc<W>(w) - lo;
     return par ^ (lo & hi & 1);
+}
+
+// The sign of a bipartition (k_expand_fermi.hip).  |n> = c+_{k1} ... c+_{kN} |0>, k1 < ... < kN, and
+// |a>_A |b>_B := (prod_{k in A, ascending} c+_k) (prod_{k in B, ascending} c+_k) |0> -- the modes of A in front -- differ by
+//   sigma(n) = (-1)^#{(i, j): i in A, j in B, both occupied, j < i}:
+// every occupied mode of B that stands in front of an occupied mode of A is carried past it.  With prefix(y) = the word whose bit i
+// is the parity of the bits of y below i (log2(width) shift-xor steps), the exponent is popcount(n & mask_a & prefix(n & mask_b)).
+template <typename W> __host__ __device__ __forceinline__ W fermi_prefix_parity(W y) {
+    y = (W)(y << 1); // exclusive: bit i collects the bits strictly below i
+    y ^= (W)(y << 1);
+    y ^= (W)(y << 2);
+    y ^= (W)(y << 4);
+    y ^= (W)(y << 8);
+    y ^= (W)(y << 16);
+    if (sizeof(W) == 8) y ^= (W)((uint64_t)y << 32);
+    return y;
+}
+template <typename W> __host__ __device__ __forceinline__ int fermi_split_parity(W n, W mask_a, W mask_b) {
+    return fermi_popc<W>(n & mask_a & fermi_prefix_parity<W>(n & mask_b)) & 1;
 }
 
 // apply_elem_w with the LIFT kinds: rotate / reverse both h-bit halves in registers, optionally exchange them.  Reversing the

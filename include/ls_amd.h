@@ -569,9 +569,9 @@ void ls_amd_csr_free(ls_amd_csr *m); /* frees the three arrays and clears *m; NU
  * (its n_A is reported as -1).  A = every site gives one block of one column: the vector over the ascending states of the same
  * basis without symmetries.  M M+ is the reduced density matrix of A.
  *
- * Scope: spin-1/2 bases, projected or not, ONE partition (the whole sector on this device; up to 40 sites without a fixed weight).
- * Refused with their own messages: fermionic bases of any kind (the partial trace of fermions needs mode-ordering signs), a mask
- * with bits outside the sites. */
+ * Scope: ONE partition (the whole sector on this device; up to 40 sites without a fixed weight).  ls_amd_expand_create takes
+ * spin-1/2 bases, projected or not, and refuses with their own messages fermionic bases of any kind (the partial trace of fermions
+ * needs mode-ordering signs: ls_amd_fermi_expand_create below carries them) and a mask with bits outside the sites. */
 typedef struct ls_amd_expand ls_amd_expand;
 /* d_reps: the n ascending representatives of `basis` in HBM (borrowed until ls_amd_expand_destroy).  Builds the norms n(r) -- by the
  * routine of the matvec and cross-sector plans -- and the block table; synchronises `stream`. */
@@ -589,12 +589,44 @@ int ls_amd_expand_apply(ls_amd_expand *plan, ls_amd_dtype dtype, void const *d_p
 /* synchronises `stream` and reports the device error flag: -1 when a representative or one of its images was not a state of the
  * basis (another Hamming weight, bits above number_sites) -- such images are never stored */
 int ls_amd_expand_check(ls_amd_expand *plan, void *stream);
-char const *ls_amd_expand_kernel_name(ls_amd_expand const *plan); /* "k_expand_push" */
+char const *ls_amd_expand_kernel_name(ls_amd_expand const *plan); /* "k_expand_push"; "k_expand_push_fermi" for a fermionic plan */
 void ls_amd_expand_destroy(ls_amd_expand *plan);
 /* Host-only test hook (no device): the block table of `basis` and `subsystem_mask` -- up to `capacity` entries of every non-NULL
  * array, *total = the elements of the buffer; returns the number of blocks, -1 on the refusals above */
 int ls_amd_test_expand_layout(ls_hs_basis const *basis, uint64_t subsystem_mask, int capacity, int *n_a, int64_t *rows, int64_t *cols,
                               int64_t *offsets, int64_t *total);
+
+
+/* Fermionic bases (k_expand_push_fermi, csrc/k_expand_fermi.hip): spinless fermions, spinful fermions with N alone fixed (spinless
+ * over their 2 L modes), and the spinful (N, N_up) product basis, each projected or not, with or without the up <-> down flip.  The
+ * subsystem is a set of MODES (bits of the state word: mode (i, up) = bit i, mode (i, down) = bit i + L).  Two signs enter:
+ *   the orbit sign -- U_g |r> = sign(g, r) |g r> (include/ls_hs.h), so the image s = g r receives conj(chi(g)) sign(g, r) n(r) psi[r];
+ *     elements that reach the same s still store the same value (n(r) > 0 forces chi(g) sign(g, r) = 1 on the stabiliser);
+ *   the bipartition sign -- with |n> = c+_{k1} ... c+_{kN} |0>, k1 < ... < kN, and |a>_A |b>_B := (prod_{k in A, ascending} c+_k)
+ *     (prod_{k in B, ascending} c+_k) |0>, the modes of A in front:  |n> = sigma(n) |a>|b>,
+ *         sigma(n) = (-1)^#{(i, j): i in A, j in B, both occupied, j < i},     M[a, b] = sigma(n) <n|psi>.
+ *     M M+ is then the fermionic reduced density matrix: Tr(rho_A O_A) = <psi|O_A|psi> for every operator on A written by
+ *     Jordan-Wigner over A's own modes (in ascending order).
+ * Layout.  Spinless bases, and spinful ones with N alone fixed: the layout above over the modes -- one block per n_A at fixed N, one
+ * 2^|A| x 2^|B| block otherwise (up to 40 modes).  The product basis: A = A_up (its modes below L) + A_dn; one block per
+ * (n_up, n_dn) = the particles on A_up and A_dn, ordered lexicographically, empty blocks omitted, all in one buffer:
+ *     rows C(|A_up|, n_up) C(|A_dn|, n_dn),   columns C(L - |A_up|, N_up - n_up) C(L - |A_dn|, N_dn - n_dn),
+ * rows and columns in ascending integer order of the compacted words a and b (modes in ascending order, so the up modes are low):
+ * rank_dn C(|A_up|, n_up) + rank_up on each side.  A = every mode gives the vector over the ascending states of the unprojected
+ * basis.  An image that is not a state of the basis (a half with another particle number) raises the error flag and is dropped.
+ * The handle works with ls_amd_expand_apply / _check / _num_blocks / _block / _total / _kernel_name / _destroy; on a product plan
+ * ls_amd_expand_block reports n_a = n_up + n_dn.  LS_AMD_F64 needs +-1 characters.  Spin-1/2 bases are refused by name. */
+int ls_amd_fermi_expand_create(ls_amd_expand **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, uint64_t mode_mask,
+                               void *stream);
+/* block i of a fermionic plan: (n_up, n_dn) on the product layout; n_up = n_A (-1 without a fixed number) and n_dn = -1 on the others */
+int ls_amd_fermi_expand_block(ls_amd_expand const *plan, int i, int *n_up, int *n_dn, int64_t *rows, int64_t *cols, int64_t *offset);
+/* Host-only test hooks (no device): the block table of a fermionic basis and `mode_mask`, as ls_amd_test_expand_layout, with the
+ * refusals that need no device (spin bases, a mask outside the modes, a particle number beyond the binomial table, more than 40
+ * modes without a fixed number); and sigma(state) = +-1 for the bipartition A = mode_mask_a of a word of `modes` modes, by the host
+ * run of the device code (0 on bad arguments: modes outside [1, 64], bits of the mask or the state outside the modes) */
+int ls_amd_test_fermi_expand_layout(ls_hs_basis const *basis, uint64_t mode_mask, int capacity, int *n_up, int *n_dn, int64_t *rows,
+                                    int64_t *cols, int64_t *offsets, int64_t *total);
+int ls_amd_test_fermi_split_parity(uint64_t mode_mask_a, int modes, uint64_t state);
 
 /* test hooks: evaluate compiled host-side tables on the CPU (no device work) ------------------ */
 int ls_amd_basis_group_order(ls_hs_basis const *basis);
