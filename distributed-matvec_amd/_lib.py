@@ -188,6 +188,13 @@ def load():
         "ls_amd_fermi_expand_block": (C.c_int, [vp, C.c_int, c_intp, c_intp, c_i64p, c_i64p, c_i64p]),
         "ls_amd_test_fermi_expand_layout": (C.c_int, [bp, C.c_uint64, C.c_int, c_intp, c_intp, c_i64p, c_i64p, c_i64p, c_i64p]),
         "ls_amd_test_fermi_split_parity": (C.c_int, [C.c_uint64, C.c_int, C.c_uint64]),
+        "ls_amd_corr_create": (C.c_int, [C.POINTER(vp), bp, vp, C.c_int64, vp]),
+        "ls_amd_corr_modes": (C.c_int, [vp]),
+        "ls_amd_corr_densities": (C.c_int, [vp, C.c_int, vp, c_f64p, c_f64p, C.c_int, vp]),
+        "ls_amd_corr_hoppings": (C.c_int, [vp, C.c_int, vp, c_f64p, C.c_int, vp]),
+        "ls_amd_corr_kernel_name": (C.c_char_p, [vp, C.c_int]),
+        "ls_amd_corr_destroy": (None, [vp]),
+        "ls_amd_test_corr_symmetrize": (C.c_int, [bp, C.c_int, c_f64p, c_f64p]),
         "ls_amd_fill_random": (C.c_int, [C.c_int64, vp, C.c_uint64, C.c_int, vp, vp]),
         "ls_amd_diag": (C.c_int, [vp, vp, vp, vp]),
         "ls_amd_generate": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),

@@ -5476,10 +5476,68 @@ static int cross_every_char_pm1(ls_hs_basis const *b) {
     return 1;
 }
 
+/* how the images of a kernel are looked up among the n ascending states d_reps of `basis` (device form: dev): a projected basis
+ * through the static index table of the array (shared with the matvec plans over it), an unprojected one through a closed form where
+ * the array is the whole identity / fixed-weight / product basis in order, else through a prefix table and a search (*d_table, owned
+ * by the caller).  d_err: a device flag that is clear on entry and on return.  `who` words the refusals. */
+static int sector_lookup(char const *who, ls_hs_basis const *basis, lsk_basis const *dev, uint64_t const *d_reps, int64_t n, int *d_err,
+                         lsk_index *six, uint32_t **d_table, ls_amd_gtab **gtab, void *stream) {
+    struct ls_amd_basis_ext const *es = BEXT(basis);
+    int const L = es->nbits;
+    uint64_t const *d_binom;
+    if (device_binom(&d_binom) != 0) return -1;
+    memset(six, 0, sizeof(*six));
+    six->kind = LSK_INDEX_SEARCH;
+    six->count = n;
+    six->reps = d_reps;
+    six->binom = d_binom;
+    six->dir_sites = L;
+    six->dir_weight = es->hamming_weight;
+    if (n >= 0xffffffffLL) return set_error("%s: source bases with >= 2^32 - 1 states are not supported", who);
+    if (dev->fermi && L > 60)
+        return set_error("%s: projected fermionic bases of more than 60 modes are not supported (%d modes: the static index table "
+                         "of the source does not fit, as for their matvec plans)", who, L);
+    if (dev->proj != LSK_PROJ_NONE) {
+        if (n > 0 && ls_amd_internal_gtab_acquire(gtab, L, d_reps, n, NULL, 1, stream) != 0) return -1;
+    } else if (n > 0) {
+        int const h = es->hamming_weight;
+        int closed = 0, zero = 0, flag = 0;
+        if (h < 0 && L < 63 && n == ((int64_t)1 << L)) { six->kind = LSK_INDEX_IDENTITY; closed = 1; }
+        else if (h >= 0 && (uint64_t)n == binom(L, h)) {
+            DEV(lsk_check_combinadic(*six, h, n, d_reps, d_err, stream));
+            DEV(lsk_sync(stream));
+            DEV(lsk_d2h(&flag, d_err, sizeof(int)));
+            DEV(lsk_h2d(d_err, &zero, sizeof(int)));
+            if (!flag) { six->kind = LSK_INDEX_COMBINADIC; closed = 1; }
+        } else if (es->product) {
+            lsk_index pix = *six;
+            pix.kind = LSK_INDEX_PRODUCT;
+            pix.prod_sites = basis->number_sites; pix.prod_up = es->prod_up; pix.prod_dn = es->prod_dn;
+            pix.prod_na = (int64_t)binom(basis->number_sites, es->prod_up);
+            if (n == pix.prod_na * (int64_t)binom(basis->number_sites, es->prod_dn)) {
+                DEV(lsk_check_product(pix, n, d_reps, d_err, stream));
+                DEV(lsk_sync(stream));
+                DEV(lsk_d2h(&flag, d_err, sizeof(int)));
+                DEV(lsk_h2d(d_err, &zero, sizeof(int)));
+                if (!flag) { *six = pix; closed = 1; }
+            }
+        }
+        if (!closed) {
+            part_state ps;
+            memset(&ps, 0, sizeof(ps));
+            ps.count = n;
+            ps.d_reps = (uint64_t *)d_reps;
+            if (build_search_index(&ps, L, stream) != 0) return -1;
+            *d_table = ps.d_table;
+            six->shift = ps.index.shift;
+            six->table = ps.index.table;
+        }
+    }
+    return 0;
+}
+
 static int cross_setup(ls_amd_cross *cx, ls_hs_operator const *op, ls_hs_basis const *target, void *stream) {
     ls_hs_basis const *src = op->basis;
-    struct ls_amd_basis_ext const *es = BEXT(src);
-    int const L = es->nbits;
     lsk_basis dst;
     if (basis_device(src, &cx->src) != 0 || basis_device(target, &dst) != 0) return -1;
     /* the adjoint's device groups: the diagonal terms are the group with flip mask 0 (row i of the target is not column i of the
@@ -5520,55 +5578,7 @@ static int cross_setup(ls_amd_cross *cx, ls_hs_operator const *op, ls_hs_basis c
     cx->d_norms = (double *)p;
     DEV(lsk_norms(dst, cx->n_dst, cx->d_dst_reps, cx->d_norms, stream));
     /* the source look-up */
-    uint64_t const *d_binom;
-    if (device_binom(&d_binom) != 0) return -1;
-    memset(&cx->six, 0, sizeof(cx->six));
-    cx->six.kind = LSK_INDEX_SEARCH;
-    cx->six.count = cx->n_src;
-    cx->six.reps = cx->d_src_reps;
-    cx->six.binom = d_binom;
-    cx->six.dir_sites = L;
-    cx->six.dir_weight = es->hamming_weight;
-    if (cx->n_src >= 0xffffffffLL) return set_error("cross-sector: source bases with >= 2^32 - 1 states are not supported");
-    if (cx->src.fermi && L > 60)
-        return set_error("cross-sector: projected fermionic bases of more than 60 modes are not supported (%d modes: the static index table "
-                         "of the source does not fit, as for their matvec plans)", L);
-    if (cx->src.proj != LSK_PROJ_NONE) {
-        if (cx->n_src > 0 && ls_amd_internal_gtab_acquire(&cx->gtab, L, cx->d_src_reps, cx->n_src, NULL, 1, stream) != 0) return -1;
-    } else if (cx->n_src > 0) {
-        int const h = es->hamming_weight;
-        int closed = 0, zero = 0, flag = 0;
-        if (h < 0 && L < 63 && cx->n_src == ((int64_t)1 << L)) { cx->six.kind = LSK_INDEX_IDENTITY; closed = 1; }
-        else if (h >= 0 && (uint64_t)cx->n_src == binom(L, h)) {
-            DEV(lsk_check_combinadic(cx->six, h, cx->n_src, cx->d_src_reps, cx->d_err, stream));
-            DEV(lsk_sync(stream));
-            DEV(lsk_d2h(&flag, cx->d_err, sizeof(int)));
-            DEV(lsk_h2d(cx->d_err, &zero, sizeof(int)));
-            if (!flag) { cx->six.kind = LSK_INDEX_COMBINADIC; closed = 1; }
-        } else if (es->product) {
-            lsk_index pix = cx->six;
-            pix.kind = LSK_INDEX_PRODUCT;
-            pix.prod_sites = src->number_sites; pix.prod_up = es->prod_up; pix.prod_dn = es->prod_dn;
-            pix.prod_na = (int64_t)binom(src->number_sites, es->prod_up);
-            if (cx->n_src == pix.prod_na * (int64_t)binom(src->number_sites, es->prod_dn)) {
-                DEV(lsk_check_product(pix, cx->n_src, cx->d_src_reps, cx->d_err, stream));
-                DEV(lsk_sync(stream));
-                DEV(lsk_d2h(&flag, cx->d_err, sizeof(int)));
-                DEV(lsk_h2d(cx->d_err, &zero, sizeof(int)));
-                if (!flag) { cx->six = pix; closed = 1; }
-            }
-        }
-        if (!closed) {
-            part_state ps;
-            memset(&ps, 0, sizeof(ps));
-            ps.count = cx->n_src;
-            ps.d_reps = (uint64_t *)cx->d_src_reps;
-            if (build_search_index(&ps, L, stream) != 0) return -1;
-            cx->d_table = ps.d_table;
-            cx->six.shift = ps.index.shift;
-            cx->six.table = ps.index.table;
-        }
-    }
+    if (sector_lookup("cross-sector", src, &cx->src, cx->d_src_reps, cx->n_src, cx->d_err, &cx->six, &cx->d_table, &cx->gtab, stream) != 0) return -1;
     /* counting pass: the packets that reach a source row (ls_amd_cross_nnz); whether some do not is left to the first apply */
     unsigned long long count = 0;
     if (cx->n_groups > 0 && cx->n_dst > 0 && cx->n_src > 0) {
@@ -6029,4 +6039,233 @@ int ls_amd_expand_check(ls_amd_expand *ex, void *stream) {
 char const *ls_amd_expand_kernel_name(ls_amd_expand const *ex) {
     if (!ex) { set_error("ls_amd_expand_kernel_name: NULL plan"); return NULL; }
     return ex->fermi ? lsk_expand_fermi_kernel_name() : lsk_expand_kernel_name();
+}
+
+/* ============================================================================================ */
+/* two-point correlation matrices (include/ls_amd.h: ls_amd_corr; csrc/k_corr.hip) */
+/* ============================================================================================ */
+/* The device sums over the representatives alone (the RAW matrices); C[i][j] = |G|^-1 sum_g R[g(i)][g(j)] over the whole group is
+ * this host pass of |G| M^2 operations.  g(i) = the position of the bit of g(1 << i).  The elements that contain the global spin
+ * inversion send bit b -> 1 - b: on the densities D -> 1 - d_i - d_j + D_ij (d -> 1 - d; a normalised state), on the hoppings
+ * (i, j) -> (j, i) (and the diagonal, which holds the densities, -> 1 - d).
+ * kind 0: raw / out = the one-point row d[M], then D[M][M];  kind 1: G[M][M] as (re, im) pairs. */
+static int corr_symmetrize(ls_hs_basis const *basis, int kind, double const *raw, double *out) {
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    int const M = e->nbits, order = e->order, inv = basis->spin_inversion != 0;
+    size_t const len = kind == 0 ? (size_t)M + (size_t)M * M : 2 * (size_t)M * M;
+    int *img = (int *)malloc(sizeof(int) * (size_t)M);
+    double *acc = (double *)calloc(len, sizeof(double));
+    if (!img || !acc) { free(img); free(acc); return set_error("ls_amd_corr: out of host memory"); }
+    for (int g = 0; g < order; ++g) {
+        for (int s = 0; s < M; ++s) img[s] = __builtin_ctzll(host_apply_elem(&e->elems[g], 1ULL << s, M));
+        if (kind == 0) {
+            double const *d = raw, *D = raw + M;
+            for (int i = 0; i < M; ++i) acc[i] += inv ? 1.0 : d[img[i]]; /* d + (1 - d) */
+            for (int i = 0; i < M; ++i)
+                for (int j = 0; j < M; ++j) {
+                    double const v = D[(size_t)img[i] * M + img[j]];
+                    acc[M + (size_t)i * M + j] += inv ? 1.0 - d[img[i]] - d[img[j]] + 2.0 * v : v;
+                }
+        } else {
+            for (int i = 0; i < M; ++i)
+                for (int j = 0; j < M; ++j) {
+                    double const *a = raw + 2 * ((size_t)img[i] * M + img[j]), *b = raw + 2 * ((size_t)img[j] * M + img[i]);
+                    double *o = acc + 2 * ((size_t)i * M + j);
+                    if (!inv) { o[0] += a[0]; o[1] += a[1]; }
+                    else if (i == j) { o[0] += 1.0; } /* G_ii + (1 - G_ii) */
+                    else { o[0] += a[0] + b[0]; o[1] += a[1] + b[1]; }
+                }
+        }
+    }
+    double const scale = 1.0 / ((double)order * (inv ? 2.0 : 1.0));
+    for (size_t k = 0; k < len; ++k) out[k] = acc[k] * scale;
+    free(img); free(acc);
+    return 0;
+}
+
+/* the refusals of ls_amd_corr_create that need no device */
+static int corr_preconditions(char const *who, ls_hs_basis const *basis) {
+    if (!basis) return set_error("%s: NULL basis", who);
+    if (!reg_get(basis)) return set_error("%s: the basis is not built by this library (ls_amd_adopt_basis first)", who);
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    if (e->fermi && e->nbits > 60)
+        return set_error("%s: projected fermionic bases of more than 60 modes are not supported (%d modes: the static index table does "
+                         "not fit, as for their matvec and cross-sector plans)", who, e->nbits);
+    return 0;
+}
+
+int ls_amd_test_corr_symmetrize(ls_hs_basis const *basis, int kind, double const *raw, double *out) {
+    if (corr_preconditions("ls_amd_test_corr_symmetrize", basis) != 0) return -1;
+    if (kind != 0 && kind != 1) return set_error("ls_amd_test_corr_symmetrize: kind %d is neither 0 (densities) nor 1 (hoppings)", kind);
+    if (!raw || !out) return set_error("ls_amd_test_corr_symmetrize: NULL %s", !raw ? "raw matrix" : "output");
+    return corr_symmetrize(basis, kind, raw, out);
+}
+
+struct ls_amd_corr {
+    ls_hs_basis const *basis; /* borrowed */
+    lsk_basis bs;             /* device tables owned by the basis */
+    lsk_index six;
+    uint32_t *d_table;        /* owned: prefix table of a searched (unprojected, incomplete) array */
+    ls_amd_gtab *gtab;        /* shared: static index table of a projected basis */
+    double *d_norms;          /* owned: n(r) of every row */
+    int *d_err;               /* owned */
+    uint64_t const *d_reps;   /* borrowed */
+    int64_t n;
+    int M, pm1, jw;           /* modes; every character is +-1: f64 allowed; fermionic: the hoppings carry the Jordan-Wigner sign */
+    int n_dpairs, n_hpairs;   /* i <= j; ordered i != j (inside one species on the spinful product basis) */
+    uint16_t *h_dpairs, *h_hpairs, *d_dpairs, *d_hpairs; /* owned: i | j << 8 */
+    double *d_partial, *d_out, *h_out; /* owned: the partial sums of the blocks, the sums, and their host copy */
+};
+
+void ls_amd_corr_destroy(ls_amd_corr *pl) {
+    if (!pl) return;
+    if (pl->d_table) lsk_free(pl->d_table);
+    if (pl->d_norms) lsk_free(pl->d_norms);
+    if (pl->d_err) lsk_free(pl->d_err);
+    if (pl->d_dpairs) lsk_free(pl->d_dpairs);
+    if (pl->d_hpairs) lsk_free(pl->d_hpairs);
+    if (pl->d_partial) lsk_free(pl->d_partial);
+    if (pl->d_out) lsk_free(pl->d_out);
+    if (pl->gtab) ls_amd_internal_gtab_release(pl->gtab);
+    free(pl->h_dpairs); free(pl->h_hpairs); free(pl->h_out);
+    free(pl);
+}
+
+static int corr_setup(ls_amd_corr *pl, void *stream) {
+    struct ls_amd_basis_ext const *e = BEXT(pl->basis);
+    int const M = pl->M;
+    if (basis_device(pl->basis, &pl->bs) != 0) return -1;
+    pl->pm1 = cross_every_char_pm1(pl->basis);
+    pl->jw = pl->basis->particle_type != LS_HS_SPIN;
+    /* the pairs: densities i <= j; hoppings every ordered i != j -- on the spinful (N, N_up) product basis inside one species only
+     * (the others change N_up: exactly zero, and their images are no states of the basis) */
+    pl->h_dpairs = (uint16_t *)malloc(sizeof(uint16_t) * (size_t)(M * (M + 1) / 2));
+    pl->h_hpairs = (uint16_t *)malloc(sizeof(uint16_t) * (size_t)(M * M));
+    int const half = pl->basis->number_sites;
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < M; ++j) {
+            if (i <= j) pl->h_dpairs[pl->n_dpairs++] = (uint16_t)(i | j << 8);
+            if (i != j && !(e->product && (i < half) != (j < half))) pl->h_hpairs[pl->n_hpairs++] = (uint16_t)(i | j << 8);
+        }
+    void *p = NULL;
+    if (upload(&p, pl->h_dpairs, sizeof(uint16_t) * (size_t)pl->n_dpairs) != 0) return -1;
+    pl->d_dpairs = (uint16_t *)p;
+    if (pl->n_hpairs > 0) {
+        if (upload(&p, pl->h_hpairs, sizeof(uint16_t) * (size_t)pl->n_hpairs) != 0) return -1;
+        pl->d_hpairs = (uint16_t *)p;
+    }
+    size_t const vals = (size_t)(pl->n_dpairs > 2 * pl->n_hpairs ? pl->n_dpairs : 2 * pl->n_hpairs);
+    pl->h_out = (double *)malloc(8 * vals);
+    DEV(lsk_malloc(&p, 8 * vals * (size_t)lsk_corr_blocks(pl->n)));
+    pl->d_partial = (double *)p;
+    DEV(lsk_malloc(&p, 8 * vals));
+    pl->d_out = (double *)p;
+    DEV(lsk_malloc(&p, 4 * sizeof(int)));
+    pl->d_err = (int *)p;
+    DEV(lsk_memset_async(pl->d_err, 0, 4 * sizeof(int), stream));
+    DEV(lsk_malloc(&p, 8 * (size_t)pl->n));
+    pl->d_norms = (double *)p;
+    /* the stabiliser norms, by the routine the matvec, cross-sector and expansion plans use */
+    DEV(lsk_norms(pl->bs, pl->n, pl->d_reps, pl->d_norms, stream));
+    DEV(lsk_sync(stream));
+    return sector_lookup("ls_amd_corr_create", pl->basis, &pl->bs, pl->d_reps, pl->n, pl->d_err, &pl->six, &pl->d_table, &pl->gtab, stream);
+}
+
+int ls_amd_corr_create(ls_amd_corr **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, void *stream) {
+    if (out) *out = NULL;
+    if (!out) return set_error("ls_amd_corr_create: NULL handle");
+    if (corr_preconditions("ls_amd_corr_create", basis) != 0) return -1;
+    if (n <= 0 || !d_reps) return set_error("ls_amd_corr_create: NULL representatives or no rows (n = %lld)", (long long)n);
+    if (n >= 0xffffffffLL) return set_error("ls_amd_corr_create: bases with >= 2^32 - 1 states are not supported");
+    ls_amd_corr *pl = (ls_amd_corr *)calloc(1, sizeof(*pl));
+    pl->basis = basis;
+    pl->M = NBITS(basis);
+    pl->d_reps = d_reps; pl->n = n;
+    if (corr_setup(pl, stream) != 0) { ls_amd_corr_destroy(pl); return -1; }
+    *out = pl;
+    return 0;
+}
+
+int ls_amd_corr_modes(ls_amd_corr const *pl) {
+    if (!pl) return set_error("ls_amd_corr_modes: NULL plan");
+    return pl->M;
+}
+
+static int corr_dtype(char const *who, ls_amd_corr const *pl, ls_amd_dtype dtype, void const *d_psi) {
+    if (!pl || !d_psi) return set_error("%s: NULL %s", who, !pl ? "plan" : "psi");
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
+    if (dtype == LS_AMD_F64 && !pl->pm1) return set_error("%s: f64 needs +-1 characters (complex characters: use c128)", who);
+    return 0;
+}
+
+/* the raw densities into raw[M + M * M] (the one-point row, then the symmetric D); synchronises the stream */
+static int corr_raw_densities(ls_amd_corr *pl, int cplx, void const *d_psi, double *raw, void *stream) {
+    int const M = pl->M;
+    DEV(lsk_corr_diag(M, pl->n_dpairs, pl->d_dpairs, cplx, pl->n, pl->d_reps, d_psi, pl->d_partial, pl->d_out, stream));
+    DEV(lsk_sync(stream));
+    DEV(lsk_d2h(pl->h_out, pl->d_out, 8 * (size_t)pl->n_dpairs));
+    for (int k = 0; k < pl->n_dpairs; ++k) {
+        int const i = pl->h_dpairs[k] & 0xff, j = pl->h_dpairs[k] >> 8;
+        raw[M + (size_t)i * M + j] = raw[M + (size_t)j * M + i] = pl->h_out[k];
+        if (i == j) raw[i] = pl->h_out[k];
+    }
+    return 0;
+}
+
+int ls_amd_corr_densities(ls_amd_corr *pl, ls_amd_dtype dtype, void const *d_psi, double *h_d, double *h_dd, int symmetrize, void *stream) {
+    if (corr_dtype("ls_amd_corr_densities", pl, dtype, d_psi) != 0) return -1;
+    int const M = pl->M;
+    size_t const len = (size_t)M + (size_t)M * M;
+    double *raw = (double *)malloc(8 * 2 * len), *res = raw + len;
+    int rc = corr_raw_densities(pl, dtype == LS_AMD_C128, d_psi, raw, stream);
+    if (rc == 0 && symmetrize) rc = corr_symmetrize(pl->basis, 0, raw, res);
+    else res = raw;
+    if (rc == 0) {
+        if (h_d) memcpy(h_d, res, 8 * (size_t)M);
+        if (h_dd) memcpy(h_dd, res + M, 8 * (size_t)M * M);
+    }
+    free(raw);
+    return rc;
+}
+
+int ls_amd_corr_hoppings(ls_amd_corr *pl, ls_amd_dtype dtype, void const *d_psi, double *h_g, int symmetrize, void *stream) {
+    if (corr_dtype("ls_amd_corr_hoppings", pl, dtype, d_psi) != 0) return -1;
+    if (!h_g) return set_error("ls_amd_corr_hoppings: NULL output");
+    int const M = pl->M, cplx = dtype == LS_AMD_C128;
+    size_t const len = 2 * (size_t)M * M;
+    double *dens = (double *)malloc(8 * ((size_t)M + (size_t)M * M)), *raw = (double *)calloc(len, 8);
+    int rc = corr_raw_densities(pl, cplx, d_psi, dens, stream);
+    if (rc == 0 && pl->n_hpairs > 0) {
+        rc = lsk_corr_hop(pl->bs, pl->six, pl->gtab ? pl->gtab->tab : no_gtab(), pl->jw, pl->n_hpairs, pl->d_hpairs, cplx, pl->n, pl->d_reps,
+                          pl->d_norms, d_psi, pl->d_partial, pl->d_out, pl->d_err, stream) != 0 ? dev_error() : 0;
+        int flag = 0, zero = 0;
+        if (rc == 0 && (lsk_sync(stream) != 0 || lsk_d2h(&flag, pl->d_err, sizeof(int)) != 0)) rc = dev_error();
+        if (rc == 0 && flag) {
+            if (lsk_h2d(pl->d_err, &zero, sizeof(int)) != 0) rc = dev_error();
+            else rc = set_error("correlations: the image of a representative under a hopping has non-zero norm and is not in the basis (the "
+                                "array of representatives does not belong to this basis or is not the whole sector: another Hamming weight, "
+                                "a truncated array)");
+        }
+        if (rc == 0 && lsk_d2h(pl->h_out, pl->d_out, 8 * (size_t)pl->n_hpairs * (cplx ? 2 : 1)) != 0) rc = dev_error();
+    }
+    if (rc == 0) {
+        for (int k = 0; k < pl->n_hpairs; ++k) {
+            size_t const at = 2 * ((size_t)(pl->h_hpairs[k] & 0xff) * M + (pl->h_hpairs[k] >> 8));
+            raw[at] = cplx ? pl->h_out[2 * k] : pl->h_out[k];
+            raw[at + 1] = cplx ? pl->h_out[2 * k + 1] : 0.0;
+        }
+        for (int i = 0; i < M; ++i) raw[2 * ((size_t)i * M + i)] = dens[i];
+        if (symmetrize) rc = corr_symmetrize(pl->basis, 1, raw, h_g);
+        else memcpy(h_g, raw, 8 * len);
+    }
+    free(dens); free(raw);
+    return rc;
+}
+
+char const *ls_amd_corr_kernel_name(ls_amd_corr const *pl, int which) {
+    if (!pl) { set_error("ls_amd_corr_kernel_name: NULL plan"); return NULL; }
+    if (which == 0) return lsk_corr_diag_kernel_name();
+    if (which == 1) return pl->bs.fermi ? lsk_corr_hop_fermi_kernel_name() : lsk_corr_hop_kernel_name();
+    set_error("ls_amd_corr_kernel_name: kernel %d is neither 0 (densities) nor 1 (hoppings)", which);
+    return NULL;
 }

@@ -648,6 +648,31 @@ int lsk_expand_fermi_push(lsk_basis bs, lsk_expand_fermi ex, uint64_t const *d_b
 /* parity of sigma(n) (host run of the device code) */
 int lsk_test_fermi_split_parity(uint64_t n, uint64_t mask_a, uint64_t mask_b);
 
+/* two-point correlation matrices of a sector state (k_corr.hip, k_corr_fermi.hip): sums over the
+ * representatives reps[0, n) alone -- the host averages them over the group afterwards.  A pair is the 16-bit word i | j << 8 of
+ * two bits of the state word.  Both routines reduce in two steps without floating-point atomics: one partial per (block, pair) in
+ * `partial`, then a sum over the blocks in ascending order into `out` (device; n_pairs values of 1 (f64) or, for the hoppings of a
+ * c128 vector, 2 doubles); the grid is a function of n and of the kernel's residency on the device, so equal inputs give equal bytes.
+ * `partial` holds lsk_corr_blocks(n) * n_pairs values (the most blocks either kernel launches). */
+int lsk_corr_blocks(int64_t n);
+/* densities: out[p] = sum_r |psi_r|^2 [bits i and j of reps[r] set]  (k_corr_diag; i == j: the one-point function) */
+char const *lsk_corr_diag_kernel_name(void);
+int lsk_corr_diag(int modes, int n_pairs, uint16_t const *pairs, int cplx, int64_t n, uint64_t const *reps, void const *psi,
+                  double *partial, double *out, void *stream);
+/* hoppings: out[p] = sum over the rows r with bit i set and bit j clear of
+ *     conj(psi_r) / norms[r] * [jw: (-1)^popcount(r & between(i, j))] * chi(g0) [sign(g0, s)] n(rep s) psi[index(rep s)],  s = r ^ 1 << i ^ 1 << j,
+ * the matrix element of k_cross_pull (stages B1 / B2; bs, six, gt as there: gt.entries != NULL looks the representative up in the
+ * static index table, else `six` does) between the row and its image.  Images of zero norm contribute nothing; an image of
+ * non-zero norm that is not among reps raises *d_err and contributes nothing.  bs.fermi runs k_corr_hop_fermi. */
+char const *lsk_corr_hop_kernel_name(void);
+char const *lsk_corr_hop_fermi_kernel_name(void);
+int lsk_corr_hop(lsk_basis bs, lsk_index six, lsk_gtab gt, int jw, int n_pairs, uint16_t const *pairs, int cplx, int64_t n,
+                 uint64_t const *reps, double const *norms, void const *psi, double *partial, double *out, int *d_err, void *stream);
+int lsk_corr_hop_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, int jw, int n_pairs, uint16_t const *pairs, int cplx, int64_t n,
+                       uint64_t const *reps, double const *norms, void const *psi, double *partial, double *out, int *d_err, void *stream);
+/* out[q] = partial[q] + partial[m + q] + ... over `blocks` rows of m values, in that order */
+int lsk_corr_sum(int blocks, int m, double const *partial, double *out, void *stream);
+
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */
 int lsk_norms(lsk_basis bs, int64_t n, uint64_t const *reps, double *norms, void *stream);

@@ -8,7 +8,10 @@ from .api import *  # noqa: F401,F403,E402
 from . import api as _api  # noqa: E402
 from .entanglement import *  # noqa: F401,F403,E402
 from . import entanglement as _entanglement  # noqa: E402
+from . import correlations  # noqa: E402  (the module keeps its name here too: its driver is correlations.correlations)
+from .correlations import (CorrelationPlan, FermionCorrelations, SpinCorrelations, fermion_correlations, spin_correlations,  # noqa: F401,E402
+                           structure_factor)
 from . import evolve  # noqa: E402  (the module keeps its name here: its driver is evolve.evolve)
 from .evolve import EvolveResult, autocorrelation, bessel_series, propagate, propagator_coefficients  # noqa: F401,E402
 
-__all__ = list(_api.__all__) + list(_entanglement.__all__) + [n for n in evolve.__all__ if n != "evolve"]
+__all__ = list(_api.__all__) + list(_entanglement.__all__) + [n for n in correlations.__all__ if n != "correlations"] + [n for n in evolve.__all__ if n != "evolve"]

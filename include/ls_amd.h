@@ -628,6 +628,42 @@ int ls_amd_test_fermi_expand_layout(ls_hs_basis const *basis, uint64_t mode_mask
                                     int64_t *cols, int64_t *offsets, int64_t *total);
 int ls_amd_test_fermi_split_parity(uint64_t mode_mask_a, int modes, uint64_t state);
 
+/* ---- two-point correlation matrices of a sector state (csrc/k_corr.hip, k_corr_fermi.hip) ---------------
+ * For a NORMALISED state psi on the n representatives of `basis` (projected or not), over the M bits of a state word (the sites
+ * of a spin or spinless basis; the 2 L modes of a spinful one, mode (i, up) = bit i, mode (i, down) = bit i + L):
+ *   densities   d[i] = <b_i>,  D[i][j] = <b_i b_j>,  b_i = bit i of the product state (bit 1 = spin down / an occupied mode), so
+ *               <sigma^z_i sigma^z_j> = 1 - 2 d_i - 2 d_j + 4 D_ij and <n_i n_j> = D_ij                          (k_corr_diag)
+ *   hoppings    G[i][j] = <B+_i B_j>, B_j clears bit j and B+_i sets bit i: sigma^-_i sigma^+_j on a spin basis (sigma^+ clears a
+ *               bit), c+_i c_j on a fermionic one -- there the kernel multiplies the Jordan-Wigner sign
+ *               (-1)^popcount(state & between(i, j)) in, the mode order of the state word.  G[i][i] = d[i].   (k_corr_hop)
+ * The operators are not invariant under the sector's group, the state is: the device sums over the representatives alone,
+ *   R[i][j] = sum_r conj(psi_r) / n(r) (O_ij psi^)(r),   psi^(s) = conj(chi(s)) [sign] n(rep s) psi[index(rep s)]
+ * (the conventions of ls_amd_cross / ls_amd_expand), and the host averages, C[i][j] = |G|^-1 sum_g R[g(i)][g(j)] -- |G| M^2
+ * operations; an element with the global spin inversion acts as D -> 1 - d_i - d_j + D_ij, (i, j) -> (j, i) on the hoppings.
+ * symmetrize = 0 returns R itself.  Neither kernel uses floating-point atomics: one partial sum per (block, pair), added in block
+ * order, so two calls on the same input return the same bytes.  On the spinful (N, N_up) product basis only the pairs inside one
+ * species are evaluated, the others are exactly zero.
+ * Scope: ONE partition, one state.  ls_amd_corr_create refuses by name a NULL basis, a basis this library does not know
+ * (ls_amd_adopt_basis), n <= 0 or NULL representatives, and projected fermionic bases above 60 modes (the limit of
+ * ls_amd_cross_create).  It builds the norms by the routine the matvec, cross-sector and expansion plans use and shares the static
+ * index table with the plans over the same array.  LS_AMD_F64 needs +-1 characters (the rule of ls_amd_cross_create). */
+typedef struct ls_amd_corr ls_amd_corr;
+int ls_amd_corr_create(ls_amd_corr **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, void *stream);
+int ls_amd_corr_modes(ls_amd_corr const *plan); /* M */
+/* d_psi: n elements of `dtype` in HBM.  h_d: M doubles, h_dd: M * M doubles (row i, column j), HOST memory, either may be NULL.
+ * Synchronises `stream`. */
+int ls_amd_corr_densities(ls_amd_corr *plan, ls_amd_dtype dtype, void const *d_psi, double *h_d, double *h_dd, int symmetrize, void *stream);
+/* h_g: M * M (re, im) pairs in HOST memory, row i column j = <B+_i B_j>, diagonal = the densities.  Synchronises `stream`; -1 with
+ * a message when the image of a row has non-zero norm and is not among the representatives (the array is not the whole sector of
+ * this basis) -- the error flag of ls_amd_cross_check; nothing is returned then. */
+int ls_amd_corr_hoppings(ls_amd_corr *plan, ls_amd_dtype dtype, void const *d_psi, double *h_g, int symmetrize, void *stream);
+/* which = 0: "k_corr_diag"; 1: "k_corr_hop", or "k_corr_hop_fermi" on a projected fermionic basis (signed characters) */
+char const *ls_amd_corr_kernel_name(ls_amd_corr const *plan, int which);
+void ls_amd_corr_destroy(ls_amd_corr *plan);
+/* Host-only test hook (no device): the group average alone.  kind 0: raw / out = the one-point row d[M] followed by D[M][M];
+ * kind 1: G[M][M] as (re, im) pairs. */
+int ls_amd_test_corr_symmetrize(ls_hs_basis const *basis, int kind, double const *raw, double *out);
+
 /* test hooks: evaluate compiled host-side tables on the CPU (no device work) ------------------ */
 int ls_amd_basis_group_order(ls_hs_basis const *basis);
 /* 1 when the basis is a projected fermionic basis (spinless, or spinful with fixed number_up), i.e.
