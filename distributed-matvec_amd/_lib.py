@@ -195,6 +195,13 @@ def load():
         "ls_amd_corr_kernel_name": (C.c_char_p, [vp, C.c_int]),
         "ls_amd_corr_destroy": (None, [vp]),
         "ls_amd_test_corr_symmetrize": (C.c_int, [bp, C.c_int, c_f64p, c_f64p]),
+        "ls_amd_expect_create": (C.c_int, [C.POINTER(vp), bp, C.POINTER(op), C.c_int, vp, C.c_int64, vp]),
+        "ls_amd_expect_values": (C.c_int, [vp, C.c_int, vp, c_f64p, vp]),
+        "ls_amd_expect_num_terms": (C.c_int, [vp]),
+        "ls_amd_expect_num_groups": (C.c_int, [vp]),
+        "ls_amd_expect_kernel_name": (C.c_char_p, [vp]),
+        "ls_amd_expect_destroy": (None, [vp]),
+        "ls_amd_test_expect_average": (C.c_int64, [bp, op, C.c_int64, c_f64p, c_u64p, c_u64p, c_u64p, c_u64p]),
         "ls_amd_fill_random": (C.c_int, [C.c_int64, vp, C.c_uint64, C.c_int, vp, vp]),
         "ls_amd_diag": (C.c_int, [vp, vp, vp, vp]),
         "ls_amd_generate": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),

@@ -6269,3 +6269,327 @@ char const *ls_amd_corr_kernel_name(ls_amd_corr const *pl, int which) {
     set_error("ls_amd_corr_kernel_name: kernel %d is neither 0 (densities) nor 1 (hoppings)", which);
     return NULL;
 }
+
+/* ============================================================================================ */
+/* expectation values of arbitrary operators (include/ls_amd.h: ls_amd_expect; csrc/k_expect.hip) */
+/* ============================================================================================ */
+/* <psi|O|psi> = |G|^-1 sum_g R[U_g O U_g^-1], R[A] = sum_r conj(psi_r) / n(r) (A psi^)(r) over the representatives alone.  The host
+ * conjugates every term by every element of the group -- inside the term format -- and the device evaluates R of the unique results.
+ * One entry = one conjugated term of operator k, scaled by |G|^-1, in canonical form: r inside m, the sign bits inside m (where the
+ * state is fixed) folded into the coefficient. */
+typedef struct { uint64_t x, m, r, s; int k; double re, im; } expect_entry;
+static int expect_key_cmp(expect_entry const *a, expect_entry const *b) {
+    if (a->x != b->x) return a->x < b->x ? -1 : 1;
+    if (a->m != b->m) return a->m < b->m ? -1 : 1;
+    if (a->r != b->r) return a->r < b->r ? -1 : 1;
+    if (a->s != b->s) return a->s < b->s ? -1 : 1;
+    return 0;
+}
+static int expect_entry_cmp(void const *pa, void const *pb) {
+    expect_entry const *a = (expect_entry const *)pa, *b = (expect_entry const *)pb;
+    int const c = expect_key_cmp(a, b);
+    return c != 0 ? c : (a->k > b->k) - (a->k < b->k);
+}
+/* adjoint != 0: the row-wise orientation of ls_amd_operator_adjoint without the conjugation of v -- <b|A|b ^ x> is tested on the row b */
+static expect_entry expect_canonical(raw_term t, int k, int adjoint, double scale) {
+    t.r &= t.m;
+    if (adjoint) {
+        if (__builtin_popcountll(t.x & t.s) & 1) { t.re = -t.re; t.im = -t.im; }
+        t.r ^= t.x & t.m;
+    }
+    if (__builtin_popcountll(t.r & t.s) & 1) { t.re = -t.re; t.im = -t.im; }
+    expect_entry e = {t.x, t.m, t.r, t.s & ~t.m, k, t.re * scale, t.im * scale};
+    return e;
+}
+/* appends the |G| conjugates U_g t U_g^-1 / |G| of the n raw terms t (|G| counts the inversion doubling) to *buf */
+static int expect_conjugates(char const *who, ls_hs_basis const *basis, raw_term const *t, int n, int k, int adjoint, expect_entry **buf,
+                             size_t *len, size_t *cap) {
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    int const L = e->nbits, order = e->order > 0 ? e->order : 1, inv = basis->spin_inversion != 0;
+    double const scale = 1.0 / ((double)order * (inv ? 2.0 : 1.0));
+    if (e->fermi)
+        for (int i = 0; i < n; ++i)
+            if (t[i].x & ~t[i].m)
+                return set_error("%s: a term flips modes outside its projector mask (x = 0x%llx is not inside m = 0x%llx): not a product "
+                                 "of creation and annihilation operators", who, (unsigned long long)t[i].x, (unsigned long long)t[i].m);
+    size_t const need = *len + (size_t)order * (inv ? 2 : 1) * (size_t)n;
+    if (need > *cap) {
+        size_t const c = need > 2 * *cap ? need : 2 * *cap;
+        expect_entry *nb = (expect_entry *)realloc(*buf, sizeof(expect_entry) * (c > 0 ? c : 1));
+        if (!nb) return set_error("%s: out of host memory", who);
+        *buf = nb; *cap = c;
+    }
+    int p[64];
+    uint64_t tab[64], nbr[64];
+    for (int g = 0; g < order; ++g) {
+        int ident = 1;
+        if (e->elems && e->order > 0) { /* p[i] = the bit that element g carries to position i: (g.w)[i] = w[p[i]] */
+            for (int s = 0; s < L; ++s) p[__builtin_ctzll(host_apply_elem(&e->elems[g], 1ULL << s, L))] = s;
+        } else for (int s = 0; s < L; ++s) p[s] = s;
+        for (int s = 0; s < L; ++s) ident &= p[s] == s;
+        if (e->fermi && !ident) perm_sign_table(p, L, tab, nbr);
+        for (int i = 0; i < n; ++i) {
+            raw_term c = t[i];
+            c.r &= c.m;
+            if (!ident) {
+                if (e->fermi) c = signed_conjugate(c, p, L, tab, nbr);
+                else { c.m = permute_mask(p, L, c.m); c.r = permute_mask(p, L, c.r); c.x = permute_mask(p, L, c.x); c.s = permute_mask(p, L, c.s); }
+            }
+            (*buf)[(*len)++] = expect_canonical(c, k, adjoint, scale);
+            if (inv) { /* the same element with the global flip: ((-1)^popcount(s) v, m, r ^ m, x, s) */
+                raw_term f = c;
+                if (__builtin_popcountll(f.s) & 1) { f.re = -f.re; f.im = -f.im; }
+                f.r ^= f.m;
+                (*buf)[(*len)++] = expect_canonical(f, k, adjoint, scale);
+            }
+        }
+    }
+    return 0;
+}
+/* sorts by (key, k), adds the coefficients of equal (key, k) in that order and drops what cancels (|w| <= 1e-15 vmax[k]: the rounding
+ * residue of at most |G| summands of modulus vmax / |G|); returns the entries left */
+static size_t expect_merge(expect_entry *buf, size_t len, double const *vmax) {
+    qsort(buf, len, sizeof(expect_entry), expect_entry_cmp);
+    size_t w = 0;
+    for (size_t i = 0; i < len;) {
+        expect_entry acc = buf[i];
+        size_t j = i + 1;
+        while (j < len && expect_entry_cmp(&buf[i], &buf[j]) == 0) { acc.re += buf[j].re; acc.im += buf[j].im; ++j; }
+        if (hypot(acc.re, acc.im) > 1e-15 * vmax[acc.k]) buf[w++] = acc;
+        i = j;
+    }
+    return w;
+}
+static double raw_vmax(raw_term const *t, int n) {
+    double v = 0.0;
+    for (int i = 0; i < n; ++i) { double const a = hypot(t[i].re, t[i].im); if (a > v) v = a; }
+    return v;
+}
+static int expect_operator_check(char const *who, ls_hs_basis const *basis, ls_hs_operator const *op, int k) {
+    if (!op) return set_error("%s: operator %d is NULL", who, k);
+    if (!reg_get(op)) return set_error("%s: operator %d is unknown (ls_amd_adopt_operator first)", who, k);
+    if (op->basis != basis) return set_error("%s: operator %d is an operator of another basis (build it on the basis of the plan)", who, k);
+    return 0;
+}
+
+int64_t ls_amd_test_expect_average(ls_hs_basis const *basis, ls_hs_operator const *op, int64_t cap, double *v, uint64_t *m, uint64_t *r,
+                                   uint64_t *x, uint64_t *s) {
+    char const *who = "ls_amd_test_expect_average";
+    if (corr_preconditions(who, basis) != 0) return -1;
+    if (expect_operator_check(who, basis, op, 0) != 0) return -1;
+    if (cap > 0 && (!v || !m || !r || !x || !s)) return set_error("%s: NULL output", who);
+    raw_term *t = NULL;
+    int const n = operator_raw_terms(op, &t);
+    double const vmax = raw_vmax(t, n);
+    expect_entry *buf = NULL;
+    size_t len = 0, room = 0;
+    int const rc = expect_conjugates(who, basis, t, n, 0, 0, &buf, &len, &room);
+    free(t);
+    if (rc != 0) { free(buf); return -1; }
+    len = expect_merge(buf, len, &vmax);
+    for (size_t i = 0; i < len && (int64_t)i < cap; ++i) {
+        v[2 * i] = buf[i].re; v[2 * i + 1] = buf[i].im;
+        m[i] = buf[i].m; r[i] = buf[i].r; x[i] = buf[i].x; s[i] = buf[i].s;
+    }
+    free(buf);
+    return (int64_t)len;
+}
+
+struct ls_amd_expect {
+    ls_hs_basis const *basis; /* borrowed */
+    lsk_basis bs;             /* device tables owned by the basis */
+    lsk_index six;
+    uint32_t *d_table;        /* owned: prefix table of a searched (unprojected, incomplete) array */
+    ls_amd_gtab *gtab;        /* shared: static index table of a projected basis */
+    double *d_norms;          /* owned: n(r) of every row */
+    int *d_err;               /* owned */
+    uint64_t const *d_reps;   /* borrowed */
+    int64_t n;
+    int pm1, n_ops, n_terms, n_groups, n_chunks;
+    lsk_expect_cons cons;
+    lsk_expect_group *h_groups, *d_groups; /* owned: sorted by flip mask, at most LSK_EXPECT_CHUNK terms each */
+    lsk_expect_term *d_terms;              /* owned: the unique device terms, in group order */
+    int *chunk_first;                      /* owned [n_chunks + 1]: the groups of every launch */
+    size_t n_comb;                         /* value[k] = sum over the entries with comb_k == k of comb_w * R[comb_u] */
+    int *comb_k, *comb_u;
+    double *comb_w;                        /* (re, im) */
+    double *d_partial, *d_out, *h_out;     /* owned: the partial sums of the blocks of one chunk; R of every term, and its host copy */
+};
+
+void ls_amd_expect_destroy(ls_amd_expect *pl) {
+    if (!pl) return;
+    if (pl->d_table) lsk_free(pl->d_table);
+    if (pl->d_norms) lsk_free(pl->d_norms);
+    if (pl->d_err) lsk_free(pl->d_err);
+    if (pl->d_groups) lsk_free(pl->d_groups);
+    if (pl->d_terms) lsk_free(pl->d_terms);
+    if (pl->d_partial) lsk_free(pl->d_partial);
+    if (pl->d_out) lsk_free(pl->d_out);
+    if (pl->gtab) ls_amd_internal_gtab_release(pl->gtab);
+    free(pl->h_groups); free(pl->chunk_first); free(pl->comb_k); free(pl->comb_u); free(pl->comb_w); free(pl->h_out);
+    free(pl);
+}
+
+/* the batch: unique device terms in flip-mask groups, the launches, and the sparse combination (host only) */
+static int expect_compile(ls_amd_expect *pl, ls_hs_operator const *const *ops, lsk_expect_term **h_terms) {
+    char const *who = "ls_amd_expect_create";
+    expect_entry *buf = NULL;
+    size_t len = 0, room = 0;
+    double *vmax = (double *)calloc((size_t)pl->n_ops, sizeof(double));
+    int rc = 0;
+    for (int k = 0; k < pl->n_ops && rc == 0; ++k) {
+        raw_term *t = NULL;
+        int const n = operator_raw_terms(ops[k], &t);
+        vmax[k] = raw_vmax(t, n);
+        rc = expect_conjugates(who, pl->basis, t, n, k, 1, &buf, &len, &room);
+        free(t);
+    }
+    if (rc != 0) { free(buf); free(vmax); return -1; }
+    len = expect_merge(buf, len, vmax);
+    free(vmax);
+    if (len >= (size_t)INT32_MAX) { free(buf); return set_error("%s: %zu conjugated terms in the batch, at most 2^31 - 1", who, len); }
+    /* the entries are sorted by key: one device term per key, one group per flip mask (split at LSK_EXPECT_CHUNK terms) */
+    size_t const cap = len > 0 ? len : 1;
+    *h_terms = (lsk_expect_term *)malloc(sizeof(lsk_expect_term) * cap);
+    pl->h_groups = (lsk_expect_group *)malloc(sizeof(lsk_expect_group) * cap);
+    pl->comb_k = (int *)malloc(sizeof(int) * cap); pl->comb_u = (int *)malloc(sizeof(int) * cap);
+    pl->comb_w = (double *)malloc(16 * cap);
+    if (!*h_terms || !pl->h_groups || !pl->comb_k || !pl->comb_u || !pl->comb_w) { free(buf); return set_error("%s: out of host memory", who); }
+    int nt = 0, ng = 0;
+    for (size_t i = 0; i < len; ++i) {
+        int const fresh = i == 0 || expect_key_cmp(&buf[i - 1], &buf[i]) != 0;
+        if (fresh) {
+            if (ng == 0 || pl->h_groups[ng - 1].x != buf[i].x || nt - pl->h_groups[ng - 1].begin >= LSK_EXPECT_CHUNK) {
+                lsk_expect_group g = {buf[i].x, buf[i].m, buf[i].r, nt, nt};
+                pl->h_groups[ng++] = g;
+            }
+            lsk_expect_group *g = &pl->h_groups[ng - 1];
+            /* the common projector: the mask bits every term of the group has, with one value */
+            g->cm &= buf[i].m & ~(g->cr ^ buf[i].r);
+            g->cr &= g->cm;
+            lsk_expect_term t = {buf[i].m, buf[i].r, buf[i].s};
+            (*h_terms)[nt++] = t;
+            g->end = nt;
+        }
+        pl->comb_k[i] = buf[i].k; pl->comb_u[i] = nt - 1;
+        pl->comb_w[2 * i] = buf[i].re; pl->comb_w[2 * i + 1] = buf[i].im;
+    }
+    free(buf);
+    pl->n_comb = len; pl->n_terms = nt; pl->n_groups = ng;
+    /* launches: consecutive groups of at most LSK_EXPECT_CHUNK terms together */
+    pl->chunk_first = (int *)malloc(sizeof(int) * ((size_t)ng + 2));
+    pl->n_chunks = 0;
+    for (int g = 0; g < ng;) {
+        pl->chunk_first[pl->n_chunks++] = g;
+        int const t0 = pl->h_groups[g].begin;
+        int h = g + 1;
+        while (h < ng && pl->h_groups[h].end - t0 <= LSK_EXPECT_CHUNK) ++h;
+        g = h;
+    }
+    pl->chunk_first[pl->n_chunks] = ng;
+    return 0;
+}
+
+static int expect_setup(ls_amd_expect *pl, lsk_expect_term const *h_terms, void *stream) {
+    struct ls_amd_basis_ext const *e = BEXT(pl->basis);
+    if (basis_device(pl->basis, &pl->bs) != 0) return -1;
+    pl->pm1 = cross_every_char_pm1(pl->basis);
+    pl->cons.weight = e->product ? -1 : e->hamming_weight;
+    if (e->product) { pl->cons.half = pl->basis->number_sites; pl->cons.n_up = e->prod_up; pl->cons.n_dn = e->prod_dn; }
+    void *p = NULL;
+    if (pl->n_terms > 0) {
+        if (upload(&p, h_terms, sizeof(lsk_expect_term) * (size_t)pl->n_terms) != 0) return -1;
+        pl->d_terms = (lsk_expect_term *)p;
+        if (upload(&p, pl->h_groups, sizeof(lsk_expect_group) * (size_t)pl->n_groups) != 0) return -1;
+        pl->d_groups = (lsk_expect_group *)p;
+    }
+    size_t const chunk = (size_t)(pl->n_terms < LSK_EXPECT_CHUNK ? (pl->n_terms > 0 ? pl->n_terms : 1) : LSK_EXPECT_CHUNK);
+    size_t const vals = 2 * (size_t)(pl->n_terms > 0 ? pl->n_terms : 1);
+    pl->h_out = (double *)malloc(8 * vals);
+    DEV(lsk_malloc(&p, 16 * chunk * (size_t)lsk_corr_blocks(pl->n)));
+    pl->d_partial = (double *)p;
+    DEV(lsk_malloc(&p, 8 * vals));
+    pl->d_out = (double *)p;
+    DEV(lsk_malloc(&p, 4 * sizeof(int)));
+    pl->d_err = (int *)p;
+    DEV(lsk_memset_async(pl->d_err, 0, 4 * sizeof(int), stream));
+    DEV(lsk_malloc(&p, 8 * (size_t)pl->n));
+    pl->d_norms = (double *)p;
+    /* the stabiliser norms and the look-up, as ls_amd_corr_create builds them */
+    DEV(lsk_norms(pl->bs, pl->n, pl->d_reps, pl->d_norms, stream));
+    DEV(lsk_sync(stream));
+    return sector_lookup("ls_amd_expect_create", pl->basis, &pl->bs, pl->d_reps, pl->n, pl->d_err, &pl->six, &pl->d_table, &pl->gtab, stream);
+}
+
+int ls_amd_expect_create(ls_amd_expect **out, ls_hs_basis const *basis, ls_hs_operator const *const *ops, int n_ops,
+                         uint64_t const *d_reps, int64_t n, void *stream) {
+    char const *who = "ls_amd_expect_create";
+    if (out) *out = NULL;
+    if (!out) return set_error("%s: NULL handle", who);
+    if (corr_preconditions(who, basis) != 0) return -1;
+    if (n_ops <= 0 || !ops) return set_error("%s: no operators (n_ops = %d%s)", who, n_ops, ops ? "" : ", NULL array");
+    for (int k = 0; k < n_ops; ++k)
+        if (expect_operator_check(who, basis, ops[k], k) != 0) return -1;
+    if (n <= 0 || !d_reps) return set_error("%s: NULL representatives or no rows (n = %lld)", who, (long long)n);
+    if (n >= 0xffffffffLL) return set_error("%s: bases with >= 2^32 - 1 states are not supported", who);
+    ls_amd_expect *pl = (ls_amd_expect *)calloc(1, sizeof(*pl));
+    pl->basis = basis;
+    pl->n_ops = n_ops;
+    pl->d_reps = d_reps; pl->n = n;
+    lsk_expect_term *h_terms = NULL;
+    int rc = expect_compile(pl, ops, &h_terms);
+    if (rc == 0) rc = expect_setup(pl, h_terms, stream);
+    free(h_terms);
+    if (rc != 0) { ls_amd_expect_destroy(pl); return -1; }
+    *out = pl;
+    return 0;
+}
+
+int ls_amd_expect_num_terms(ls_amd_expect const *pl) {
+    if (!pl) return set_error("ls_amd_expect_num_terms: NULL plan");
+    return pl->n_terms;
+}
+
+int ls_amd_expect_num_groups(ls_amd_expect const *pl) {
+    if (!pl) return set_error("ls_amd_expect_num_groups: NULL plan");
+    return pl->n_groups;
+}
+
+char const *ls_amd_expect_kernel_name(ls_amd_expect const *pl) {
+    if (!pl) { set_error("ls_amd_expect_kernel_name: NULL plan"); return NULL; }
+    return pl->bs.fermi ? lsk_expect_fermi_kernel_name() : lsk_expect_kernel_name();
+}
+
+int ls_amd_expect_values(ls_amd_expect *pl, ls_amd_dtype dtype, void const *d_psi, double *h_out, void *stream) {
+    char const *who = "ls_amd_expect_values";
+    if (!pl || !d_psi) return set_error("%s: NULL %s", who, !pl ? "plan" : "psi");
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
+    if (dtype == LS_AMD_F64 && !pl->pm1) return set_error("%s: f64 needs +-1 characters (complex characters: use c128)", who);
+    if (!h_out) return set_error("%s: NULL output", who);
+    int const cplx = dtype == LS_AMD_C128, nc = cplx ? 2 : 1;
+    for (int c = 0; c < pl->n_chunks; ++c) {
+        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
+        int const t0 = pl->h_groups[g0].begin, nt = pl->h_groups[g1 - 1].end - t0;
+        DEV(lsk_expect(pl->bs, pl->six, pl->gtab ? pl->gtab->tab : no_gtab(), pl->cons, g1 - g0, pl->d_groups + g0, pl->d_terms, t0, nt, cplx,
+                       pl->n, pl->d_reps, pl->d_norms, d_psi, pl->d_partial, pl->d_out + (size_t)t0 * nc, pl->d_err, stream));
+    }
+    int flag = 0, zero = 0;
+    DEV(lsk_sync(stream));
+    DEV(lsk_d2h(&flag, pl->d_err, sizeof(int)));
+    if (flag) {
+        DEV(lsk_h2d(pl->d_err, &zero, sizeof(int)));
+        return set_error("expectation values: the image of a representative under a term keeps the conserved numbers, has non-zero norm "
+                         "and is not in the basis (the array of representatives does not belong to this basis or is not the whole "
+                         "sector: another Hamming weight, a truncated array)");
+    }
+    if (pl->n_terms > 0) DEV(lsk_d2h(pl->h_out, pl->d_out, 8 * (size_t)pl->n_terms * nc));
+    for (int k = 0; k < 2 * pl->n_ops; ++k) h_out[k] = 0.0;
+    for (size_t i = 0; i < pl->n_comb; ++i) {
+        int const u = pl->comb_u[i];
+        double const rr = cplx ? pl->h_out[2 * u] : pl->h_out[u], ri = cplx ? pl->h_out[2 * u + 1] : 0.0;
+        double const wr = pl->comb_w[2 * i], wi = pl->comb_w[2 * i + 1];
+        h_out[2 * pl->comb_k[i]] += wr * rr - wi * ri;
+        h_out[2 * pl->comb_k[i] + 1] += wr * ri + wi * rr;
+    }
+    return 0;
+}

@@ -673,6 +673,34 @@ int lsk_corr_hop_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, int jw, int n_p
 /* out[q] = partial[q] + partial[m + q] + ... over `blocks` rows of m values, in that order */
 int lsk_corr_sum(int blocks, int m, double const *partial, double *out, void *stream);
 
+/* expectation values of arbitrary operators on a sector state (k_expect.hip, k_expect_fermi.hip): for every
+ * unique device term u = (m, r, s) of a flip-mask group x -- row-wise orientation, coefficient 1 --
+ *     out[u] = sum over the rows a with a & m == r of (-1)^popcount(a & s) conj(psi_a) / norms[a] * <a ^ x|psi>,
+ * <.|psi> the matrix element of lsk_corr_hop (x == 0: |psi_a|^2, no look-up).  The image a ^ x of a row is projected and looked up
+ * once per group; a row takes part in a group when a & cm == cr (the mask bits all terms of the group agree on) and the image keeps
+ * the conserved numbers `cons`; an image that leaves them contributes exactly zero, an image of non-zero norm inside them that is
+ * not among reps raises *d_err.  One call handles the groups [0, n_groups) of `groups`, whose terms (begin / end index `terms`) are
+ * terms[term0, term0 + n_terms), n_terms <= LSK_EXPECT_CHUNK: `partial` holds lsk_corr_blocks(n) * n_terms values, `out` n_terms
+ * (1 double for f64, 2 for c128).  No floating-point atomics: the reduction of lsk_corr_hop. */
+#define LSK_EXPECT_CHUNK 4096
+typedef struct lsk_expect_term { uint64_t m, r, s; } lsk_expect_term;
+typedef struct lsk_expect_group {
+    uint64_t x, cm, cr;
+    int32_t begin, end;
+} lsk_expect_group;
+typedef struct lsk_expect_cons {
+    int weight;           /* popcount of every state word, or -1 */
+    int half, n_up, n_dn; /* half > 0: the (N, N_up) basis -- popcounts of the bits below / from `half` */
+} lsk_expect_cons;
+char const *lsk_expect_kernel_name(void);
+char const *lsk_expect_fermi_kernel_name(void);
+int lsk_expect(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, int n_groups, lsk_expect_group const *groups,
+               lsk_expect_term const *terms, int term0, int n_terms, int cplx, int64_t n, uint64_t const *reps, double const *norms,
+               void const *psi, double *partial, double *out, int *d_err, void *stream);
+int lsk_expect_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, int n_groups, lsk_expect_group const *groups,
+                     lsk_expect_term const *terms, int term0, int n_terms, int cplx, int64_t n, uint64_t const *reps, double const *norms,
+                     void const *psi, double *partial, double *out, int *d_err, void *stream);
+
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */
 int lsk_norms(lsk_basis bs, int64_t n, uint64_t const *reps, double *norms, void *stream);

@@ -1,0 +1,203 @@
+"""Expectation values of arbitrary operators on a sector state in one pass (include/ls_amd.h: ls_amd_expect; csrc/k_expect.hip,
+k_expect_fermi.hip).
+
+The operators need not be invariant under the sector's group and may act on any number of sites: dimer-dimer correlations
+<(S_i.S_j)(S_k.S_l)>, scalar chirality S_i.(S_j x S_k), pair correlations <Delta+_i Delta_j>, four-point functions
+<c+_i c+_j c_k c_l>.  With R[A] = sum_r conj(psi_r) / n(r) (A psi^)(r) over the representatives alone (psi^ as in correlations.py),
+    <psi|O|psi> = |G|^-1 sum_g R[U_g O U_g^-1]
+for every O and every sector.  The host conjugates every term of every operator by every group element (on projected fermionic bases
+with the permutation signs of the Fock states), keeps the unique terms of the whole batch, and the device evaluates R of each of them in
+one pass: the image of a row under a flip mask is projected and looked up once and shared by all terms with that mask.  An image that
+leaves the conserved numbers of the basis (sigma^x on a fixed-weight basis, a lone c+) contributes exactly zero.  No floating-point
+atomics: two calls on the same input return the same bytes.  ONE partition, one state; nothing falls back to the CPU."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib, config
+from ._lib import LsAmdError
+from .correlations import _normalised
+from .entanglement import _complex_characters, _stream_ptr
+
+__all__ = ["ExpectationPlan", "expectation_values", "dimer_correlations", "pair_correlations", "expectation"]
+
+_PARTICLE_NAMES = {v: k for k, v in config.PARTICLES.items()}
+
+
+def _spec_of(basis):
+    """what config.parse_operator needs to know of a basis: its particle type and its number of sites"""
+    if getattr(basis, "spec", None) is not None:
+        return basis.spec
+    return config.BasisSpec(number_sites=basis.numberSites(), particle=_PARTICLE_NAMES[basis.particleType()])
+
+
+def _as_operator(basis, item, k):
+    from .api import Operator
+
+    if isinstance(item, Operator):
+        return item
+    if isinstance(item, config.OperatorSpec):
+        return Operator.fromSpec(basis, item)
+    if isinstance(item, dict) and "terms" in item:
+        return Operator.fromSpec(basis, config.parse_operator(item, _spec_of(basis)))
+    raise LsAmdError(f"ExpectationPlan: operator {k} is {type(item).__name__}: neither an Operator, an OperatorSpec nor an operator "
+                     "section {'terms': [{'expression': ..., 'sites': ...}]}")
+
+
+class ExpectationPlan:
+    """ls_amd_expect: the plan of the expectation values of `operators` -- Operators on `basis`, config.OperatorSpecs, or operator
+    sections {"terms": [{"expression": ..., "sites": ...}]} in the language of the basis's particle type -- in vectors on `reps` (the
+    ascending representatives of `basis`, a 1-D int64 device tensor, one partition).  psi is taken as it is."""
+
+    def __init__(self, basis, reps, operators):
+        import torch
+
+        if isinstance(reps, (list, tuple)):
+            if len(reps) != 1:
+                raise LsAmdError(f"ExpectationPlan: one partition (the whole sector on this device), got {len(reps)} blocks of representatives")
+            reps = reps[0]
+        if not isinstance(reps, torch.Tensor) or reps.dim() != 1 or reps.dtype != torch.int64 or not reps.is_contiguous():
+            raise LsAmdError("ExpectationPlan: reps must be a contiguous 1-D int64 device tensor (one partition)")
+        operators = list(operators) if not isinstance(operators, (dict, config.OperatorSpec)) and hasattr(operators, "__iter__") else [operators]
+        if not operators:
+            raise LsAmdError("ExpectationPlan: no operators")
+        ops = [_as_operator(basis, item, k) for k, item in enumerate(operators)]  # (only their term tables are read, at creation)
+        _lib.require_device()
+        if reps.device.type != "cuda":
+            raise LsAmdError("ExpectationPlan: reps must be a device tensor")
+        self.basis, self.reps = basis, reps  # borrowed by the plan: keep alive
+        self.complex_characters = _complex_characters(basis)
+        self.count = len(ops)
+        L = _lib.load()
+        arr = (type(ops[0].payload) * len(ops))(*[op.payload for op in ops])
+        h = C.c_void_p()
+        _lib.check(L.ls_amd_expect_create(C.byref(h), basis.payload, arr, len(ops), C.c_void_p(reps.data_ptr()), reps.numel(), _stream_ptr()))
+        self.h = h
+        self.num_terms = int(L.ls_amd_expect_num_terms(h))
+        self.num_groups = int(L.ls_amd_expect_num_groups(h))
+
+    def destroy(self):
+        if getattr(self, "h", None):
+            _lib.load().ls_amd_expect_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    def kernel(self):
+        name = _lib.load().ls_amd_expect_kernel_name(self.h)
+        if name is None:
+            _lib.check(-1)
+        return name.decode()
+
+    def _psi(self, who, psi):
+        import torch
+
+        n = int(self.reps.numel())
+        if self.h is None:
+            raise LsAmdError(f"ExpectationPlan.{who}: the plan was destroyed")
+        if not isinstance(psi, torch.Tensor) or psi.device.type != "cuda":
+            raise LsAmdError(f"ExpectationPlan.{who}: psi must be a device tensor (there is no CPU path)")
+        if psi.dim() != 1 or psi.numel() != n:
+            raise LsAmdError(f"ExpectationPlan.{who}: psi {tuple(psi.shape)} must be ONE vector of {n} elements")
+        if psi.dtype not in (torch.float64, torch.complex128):
+            raise LsAmdError(f"ExpectationPlan.{who}: psi is {psi.dtype}, neither float64 nor complex128")
+        if psi.dtype == torch.float64 and self.complex_characters:
+            psi = psi.to(torch.complex128)
+        psi = psi if psi.is_contiguous() else psi.contiguous()
+        return psi, (1 if psi.dtype == torch.complex128 else 0)
+
+    def values(self, psi):
+        """-> numpy complex128 (K,): <psi|O_k|psi> of every operator of the plan"""
+        psi, dt = self._psi("values", psi)
+        out = np.zeros(self.count, dtype=np.complex128)
+        _lib.check(_lib.load().ls_amd_expect_values(self.h, dt, C.c_void_p(psi.data_ptr()), out.view(np.float64).ctypes.data_as(_lib.c_f64p),
+                                                    _stream_ptr()))
+        return out
+
+
+def expectation_values(basis, reps, psi, operators):
+    """<O_k> of the normalised psi for every operator (what ExpectationPlan accepts), through one plan -> complex128 (K,)"""
+    pl = ExpectationPlan(basis, reps, operators)
+    try:
+        return pl.values(_normalised(psi))
+    finally:
+        pl.destroy()
+
+
+_SUB = "₀₁₂₃"
+_AXES = ("σˣ", "σʸ", "σᶻ")
+
+
+def dimer_section(bond_a, bond_b, scale: float = 1.0):
+    """the operator section of scale (S_i.S_j)(S_k.S_l) for the bonds (i, j) and (k, l): 9 monomials sigma^a_i sigma^a_j sigma^b_k
+    sigma^b_l / 16 on the distinct sites of the two bonds (a site both bonds hold carries the composed site operator)"""
+    sites = []
+    for q in (*bond_a, *bond_b):
+        if int(q) not in sites:
+            sites.append(int(q))
+    (i, j), (k, l) = [[sites.index(int(q)) for q in b] for b in (bond_a, bond_b)]
+    if i == j or k == l:
+        raise LsAmdError(f"dimer_correlations: a bond joins two different sites, got {tuple(bond_a)} and {tuple(bond_b)}")
+    terms = [{"expression": f"{0.0625 * float(scale)!r} × {a}{_SUB[i]} {a}{_SUB[j]} {b}{_SUB[k]} {b}{_SUB[l]}", "sites": [sites]}
+             for a in _AXES for b in _AXES]
+    return {"terms": terms}
+
+
+def dimer_correlations(basis, reps, psi, bonds):
+    """-> real (B, B): C[b][b'] = Re <(S_i.S_j)(S_k.S_l)> of the normalised psi on a spin-1/2 basis, bonds b = (i, j), b' = (k, l); the
+    diagonal is <(S_i.S_j)^2>.  (The real part is symmetric in the two bonds: the upper triangle is evaluated.)"""
+    if basis.particleType() != 0:
+        raise LsAmdError("dimer_correlations: S_i.S_j is an operator of spin-1/2 bases; a fermionic basis has pair_correlations")
+    bonds = [tuple(int(q) for q in b) for b in bonds]
+    B = len(bonds)
+    where = [(a, b) for a in range(B) for b in range(a, B)]
+    vals = expectation_values(basis, reps, psi, [dimer_section(bonds[a], bonds[b]) for a, b in where])
+    out = np.zeros((B, B))
+    for (a, b), v in zip(where, vals):
+        out[a, b] = out[b, a] = v.real
+    return out
+
+
+def pair_section(i, j):
+    """the operator section of Delta+_i Delta_j, Delta_i = c_{i down} c_{i up}; i == j: n_{i up} n_{i down}"""
+    if i == j:
+        return {"terms": [{"expression": "n₀↑ n₀↓", "sites": [[int(i)]]}]}
+    return {"terms": [{"expression": "c†₀↑ c†₀↓ c₁↓ c₁↑", "sites": [[int(i), int(j)]]}]}
+
+
+def pair_correlations(basis, reps, psi, sites=None):
+    """-> complex (L, L): P[i][j] = <Delta+_i Delta_j> of the normalised psi on a spinful-fermion basis, Delta_i = c_{i down} c_{i up}
+    (on-site singlet pairs), P[i][i] = <n_{i up} n_{i down}>; sites: a subset of the sites (default: all, in order)"""
+    if basis.particleType() == 0:
+        raise LsAmdError("pair_correlations: on-site pairs are operators of spinful-fermion bases; a spin-1/2 basis has dimer_correlations")
+    if basis.particleType() != config.PARTICLES["spinful-fermion"]:
+        raise LsAmdError("pair_correlations: on-site pairs Delta_i = c_{i down} c_{i up} need a spinful-fermion basis, not a spinless one "
+                         "(its four-point functions go through expectation_values)")
+    sites = list(range(basis.numberSites())) if sites is None else [int(q) for q in sites]
+    n = len(sites)
+    vals = expectation_values(basis, reps, psi, [pair_section(i, j) for i in sites for j in sites])
+    return np.asarray(vals).reshape(n, n)
+
+
+def expectation(config_, operators, state=None, dtype=None, eps: float = 1e-10):
+    """<O_k> of a config (dict or YAML path) for every operator (what ExpectationPlan accepts; sections are the simplest).  state None:
+    its ground state (thick-restart Lanczos to eps, as correlations.correlations(config)); else a vector on enumerateStates(basis, 1)."""
+    import torch
+
+    from . import api
+    from .diagonalize import LocalOperator, lanczos_smallest
+
+    load = api.loadConfigFromYaml if isinstance(config_, str) else api.loadConfigFromDict
+    basis, h = load(config_, hamiltonian=True)
+    reps, _ = api.enumerateStates(basis, 1)
+    if state is None:
+        if dtype is None:
+            dtype = torch.complex128 if _complex_characters(basis) or not h.isReal else torch.float64
+        state = lanczos_smallest(LocalOperator(h, reps, dtype), num_evals=1, eps=eps).eigenvectors[0]
+    return expectation_values(basis, reps[0], state, operators)

@@ -11,7 +11,9 @@ from . import entanglement as _entanglement  # noqa: E402
 from . import correlations  # noqa: E402  (the module keeps its name here too: its driver is correlations.correlations)
 from .correlations import (CorrelationPlan, FermionCorrelations, SpinCorrelations, fermion_correlations, spin_correlations,  # noqa: F401,E402
                            structure_factor)
+from . import expectation  # noqa: E402  (the module keeps its name here: its driver is expectation.expectation)
+from .expectation import ExpectationPlan, dimer_correlations, expectation_values, pair_correlations  # noqa: F401,E402
 from . import evolve  # noqa: E402  (the module keeps its name here: its driver is evolve.evolve)
 from .evolve import EvolveResult, autocorrelation, bessel_series, propagate, propagator_coefficients  # noqa: F401,E402
 
-__all__ = list(_api.__all__) + list(_entanglement.__all__) + [n for n in correlations.__all__ if n != "correlations"] + [n for n in evolve.__all__ if n != "evolve"]
+__all__ = list(_api.__all__) + list(_entanglement.__all__) + [n for n in correlations.__all__ if n != "correlations"] + [n for n in expectation.__all__ if n != "expectation"] + [n for n in evolve.__all__ if n != "evolve"]

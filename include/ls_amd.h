@@ -664,6 +664,40 @@ void ls_amd_corr_destroy(ls_amd_corr *plan);
  * kind 1: G[M][M] as (re, im) pairs. */
 int ls_amd_test_corr_symmetrize(ls_hs_basis const *basis, int kind, double const *raw, double *out);
 
+/* ------------------------------------------------------------------------------------------
+ * Expectation values of arbitrary operators on a sector state (csrc/k_expect.hip, k_expect_fermi.hip): the
+ * operators need not be invariant under the group of the sector and may act on any number of sites -- dimer-dimer correlations,
+ * scalar chirality, pair correlations, four-point functions.  With R[A] = sum_r conj(psi_r) / n(r) (A psi^)(r) over the
+ * representatives alone (psi^ as for ls_amd_corr; R is linear in A),
+ *     <psi|O|psi> = |G|^-1 sum_{g in G} R[U_g O U_g^-1]
+ * for every O and every sector.  The HOST conjugates every term (v, m, r, x, s) of every operator by every group element -- inside
+ * the term format: a permutation relabels the masks, on projected fermionic bases with the permutation signs U_g|a> = sign(g, a)|g.a>
+ * (the rule of ls_amd_operator_maps_sector_signed); an element with the global spin inversion sends a term to
+ * ((-1)^popcount(s) v, m, r ^ m, x, s) -- brings the results to one canonical row-wise form (the orientation of
+ * ls_amd_operator_adjoint; r inside m, the sign bits inside m folded into the coefficient) and keeps the UNIQUE terms of the whole
+ * batch with a sparse combination value[k] = sum_u w[k][u] R[u].  The DEVICE computes R[u] of every unique term in one pass over the
+ * representatives: the image r ^ x of a row is projected and looked up once per flip mask x and shared by all terms with that mask.
+ * No floating-point atomics; two calls on the same input return the same bytes.  psi is taken as it is (no normalisation is assumed).
+ * An image that leaves the conserved numbers of the basis (sigma^x on a fixed-weight basis, a lone c+) contributes exactly zero.
+ * Scope: ONE partition, one state.  ls_amd_expect_create refuses by name what ls_amd_corr_create refuses, n_ops <= 0, a NULL or
+ * unknown operator, an operator of another basis and, on projected fermionic bases, a term that flips modes outside its projector
+ * mask.  Only the term tables of the operators are read: they may be destroyed afterwards.  LS_AMD_F64 needs +-1 characters. */
+typedef struct ls_amd_expect ls_amd_expect;
+int ls_amd_expect_create(ls_amd_expect **out, ls_hs_basis const *basis, ls_hs_operator const *const *ops, int n_ops,
+                         uint64_t const *d_reps, int64_t n, void *stream);
+/* d_psi: n elements of `dtype` in HBM.  h_out: n_ops (re, im) pairs in HOST memory.  Synchronises `stream`; -1 with a message when
+ * an image inside the conserved numbers has non-zero norm and is not among the representatives (not the whole sector). */
+int ls_amd_expect_values(ls_amd_expect *plan, ls_amd_dtype dtype, void const *d_psi, double *h_out, void *stream);
+int ls_amd_expect_num_terms(ls_amd_expect const *plan);  /* unique device terms of the batch */
+int ls_amd_expect_num_groups(ls_amd_expect const *plan); /* flip-mask groups the device walks */
+char const *ls_amd_expect_kernel_name(ls_amd_expect const *plan); /* "k_expect", or "k_expect_fermi" on a projected fermionic basis */
+void ls_amd_expect_destroy(ls_amd_expect *plan);
+/* Host-only test hook (no device): the merged terms of |G|^-1 sum_g U_g O U_g^-1 in the operator's OWN orientation
+ * (A|a> = v [a & m == r] (-1)^popcount(a & s) |a ^ x>), r inside m and s outside m.  Returns their number, or -1; at most `cap` are
+ * written to v (re, im pairs), m, r, x, s. */
+int64_t ls_amd_test_expect_average(ls_hs_basis const *basis, ls_hs_operator const *op, int64_t cap, double *v, uint64_t *m, uint64_t *r,
+                                   uint64_t *x, uint64_t *s);
+
 /* test hooks: evaluate compiled host-side tables on the CPU (no device work) ------------------ */
 int ls_amd_basis_group_order(ls_hs_basis const *basis);
 /* 1 when the basis is a projected fermionic basis (spinless, or spinful with fixed number_up), i.e.
