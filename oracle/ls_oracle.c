@@ -319,12 +319,26 @@ static inline int64_t binary_search(const uint64_t *reps, int64_t count, uint64_
  * Identical results; it only keeps the CPU baseline of bench.py from being dominated by 25 cache-missing probes per
  * look-up.  The table belongs to the basis (built with it, outside any timed region: local_matvec builds it on first
  * use and the bench's warm-up call pays for that). */
-static struct { const uint64_t *reps; int64_t count; int shift; uint32_t *table; uint64_t nbuckets; } g_index;
-static void ensure_index(const uint64_t *reps, int64_t count) {
-    if (g_index.reps == reps && g_index.count == count && g_index.table) return;
+static struct { const uint64_t *reps; int64_t count; int shift; uint32_t *table; uint64_t nbuckets; uint64_t print; } g_index;
+/* The table is keyed by the ADDRESS of the array, and a caller's next array can lie where the last one lay (numpy reuses freed
+ * blocks): the table also remembers a fingerprint of the contents it was built from, checked on every use (one pass over the states,
+ * nothing next to a matvec), and whoever searches other arrays without building a table drops it (drop_index). */
+static uint64_t index_fingerprint(const uint64_t *reps, int64_t count) {
+    uint64_t h = 0x9e3779b97f4a7c15ULL ^ (uint64_t)count;
+    for (int64_t i = 0; i < count; ++i) h = (h ^ reps[i]) * 0xbf58476d1ce4e5b9ULL + (h >> 29);
+    return h;
+}
+static void drop_index(void) {
     free(g_index.table);
     g_index.table = NULL;
-    g_index.reps = reps; g_index.count = count;
+    g_index.reps = NULL; g_index.count = 0;
+}
+static void ensure_index(const uint64_t *reps, int64_t count) {
+    const uint64_t print = count >= (1 << 12) ? index_fingerprint(reps, count) : 0;
+    if (g_index.reps == reps && g_index.count == count && g_index.table && g_index.print == print) return;
+    free(g_index.table);
+    g_index.table = NULL;
+    g_index.reps = reps; g_index.count = count; g_index.print = print;
     if (count < (1 << 12) || count >= 0xffffffffLL) return; /* small arrays: plain search */
     int bits = 0;
     while ((1LL << (bits + 1)) <= count) ++bits;
@@ -342,7 +356,7 @@ static void ensure_index(const uint64_t *reps, int64_t count) {
     g_index.table[g_index.nbuckets + 1] = (uint32_t)count;
 }
 static inline int64_t indexed_search(const uint64_t *reps, int64_t count, uint64_t s) {
-    if (!g_index.table || g_index.reps != reps) return binary_search(reps, count, s);
+    if (!g_index.table || g_index.reps != reps || g_index.count != count) return binary_search(reps, count, s);
     uint64_t b = s >> g_index.shift;
     if (b >= g_index.nbuckets) return -1;
     int64_t lo = g_index.table[b], hi = g_index.table[b + 1];
@@ -648,6 +662,7 @@ static int partitioned_matvec(const lso_model *M, int P, const int64_t *counts,
      * set, which for numLocales > 1 would index a partition-local array with a global state; a
      * hashed partition needs the search, so the shortcut is only taken for P == 1. */
     const int ident = state_index_is_identity(M) && P == 1;
+    drop_index(); /* the partitions are searched without a table: one left behind by local_matvec must not answer for them */
     for (int p = 0; p < P; ++p) {
         const int64_t count = counts[p];
         if (count == 0) continue;

@@ -188,3 +188,35 @@ def test_extern_restatements_small():
     for i in range(200):
         s = int(CO.lib().lso_fixed_hamming_index_to_state(i, 5))
         assert bin(s).count("1") == 5 and int(CO.lib().lso_fixed_hamming_state_to_index(s)) == i
+
+
+def test_look_up_table_does_not_outlive_its_array():
+    """The oracle keeps one bucket table per representatives array, keyed by the array's ADDRESS; python hands the next array the
+    block the last one left.  Two ways a table went stale (test_reference_goldens failed by it, depending on where numpy put things):
+    another basis of the same length at the same address, and a partition of matvec_partitioned at the address of the array a
+    local_matvec had indexed."""
+    from oracle import model as M
+
+    def chain(weight):
+        cfg = M.heisenberg_chain_config(17)
+        cfg["basis"]["hamming_weight"] = weight
+        return CO.COracle(M.model_from_config(cfg))
+
+    o8, o9 = chain(8), chain(9)
+    r8, r9 = o8.enumerate(), o9.enumerate()
+    assert len(r8) == len(r9) == 24310 and not np.array_equal(r8, r9)  # C(17, 8) = C(17, 9): one length, other states
+    x = np.random.RandomState(3).rand(len(r8)) - 0.5
+    want8, want9 = o8.local_matvec(r8.copy(), x), o9.local_matvec(r9.copy(), x)
+    buf = np.empty(len(r8), dtype=np.uint64)
+    buf[:] = r8
+    same = lambda got, want: np.abs(got - want).max() <= 1e-13 * max(1.0, np.abs(want).max())  # noqa: E731 (threads: no fixed order)
+    assert same(o8.local_matvec(buf, x), want8)  # the table of `buf` is built here
+    buf[:] = r9
+    assert same(o9.local_matvec(buf, x), want9)  # same address, same length, other states
+    # a partition that lies where the indexed array lay
+    keys = CO.locale_idx_of(r9, 3)
+    rp, xp = CO.block_to_hashed(r9, keys, 3), CO.block_to_hashed(x, keys, 3)
+    part0 = buf[: len(rp[0])]
+    part0[:] = rp[0]
+    got = CO.hashed_to_block(o9.matvec_partitioned([part0, rp[1], rp[2]], xp), keys)
+    assert same(got, want9)
