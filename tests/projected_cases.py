@@ -49,7 +49,32 @@ def hop_terms(L):
     return [{"expression": monomial(1, "+-"), "sites": ring_tuples(L, 2)}, {"expression": monomial(1, "zz"), "sites": ring_tuples(L, 2)}]
 
 
-FAMILIES = {"tfim": tfim_terms, "dimer_xxz": dimer_terms, "chiral": chiral_terms, "jq": jq_terms, "hop": hop_terms}
+def xyz_terms(L):
+    """XYZ ring, Jx = 1, Jy = 0.6, Jz = 0.8: real, Hermitian, even under X, NO weight conservation -- the two-bit flip of a bond carries
+    Jx - Jy on an aligned pair and Jx + Jy on an anti-aligned one, i.e. a coefficient that depends on the partner's bits"""
+    return [{"expression": monomial(J, a + a), "sites": ring_tuples(L, 2)} for a, J in (("x", 1.0), ("y", 0.6), ("z", 0.8))]
+
+
+def twist_terms(L):
+    """tfim + 0.4i sigma^y_i sigma^z_{i+1}: a complex COEFFICIENT but a real matrix (i sigma^y is real), not Hermitian, even under X;
+    one-bit flip masks whose coefficient depends on the flipped bit and on its neighbour"""
+    return tfim_terms(L) + [{"expression": "(0.0+0.4j) " + monomial(1, "yz"), "sites": ring_tuples(L, 2)}]
+
+
+def phase_hop_terms(L):
+    """directed hopping of one complex amplitude: not Hermitian, conserves the weight, not even under X"""
+    return [{"expression": monomial(0.6 + 0.8j, "+-"), "sites": ring_tuples(L, 2)}, {"expression": monomial(1, "zz"), "sites": ring_tuples(L, 2)}]
+
+
+def two_domain_terms(L):
+    """Heisenberg ring, J = 1 on the bonds (i, i + 1) with i < L / 2 and 0.6 on the others (the closing bond too): two exchange runs
+    of different amplitude"""
+    bonds = ring_tuples(L, 2)
+    return heisenberg(bonds[: L // 2]) + heisenberg(bonds[L // 2 :], 0.6)
+
+
+FAMILIES = {"tfim": tfim_terms, "dimer_xxz": dimer_terms, "chiral": chiral_terms, "jq": jq_terms, "hop": hop_terms,
+            "xyz": xyz_terms, "twist": twist_terms, "phase_hop": phase_hop_terms, "two_domain": two_domain_terms}
 
 
 def make_config(family, L, weight=None, T=None, T2=None, R=None, X=None):
