@@ -188,6 +188,14 @@ def load():
         "ls_amd_fermi_expand_block": (C.c_int, [vp, C.c_int, c_intp, c_intp, c_i64p, c_i64p, c_i64p]),
         "ls_amd_test_fermi_expand_layout": (C.c_int, [bp, C.c_uint64, C.c_int, c_intp, c_intp, c_i64p, c_i64p, c_i64p, c_i64p]),
         "ls_amd_test_fermi_split_parity": (C.c_int, [C.c_uint64, C.c_int, C.c_uint64]),
+        "ls_amd_project_create": (C.c_int, [C.POINTER(vp), bp, vp, C.c_int64, vp]),
+        "ls_amd_project_full_size": (C.c_int64, [vp]),
+        "ls_amd_project_apply": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp]),
+        "ls_amd_project_check": (C.c_int, [vp, vp]),
+        "ls_amd_project_kernel_name": (C.c_char_p, [vp]),
+        "ls_amd_project_destroy": (None, [vp]),
+        "ls_amd_test_project_full_size": (C.c_int64, [bp]),
+        "ls_amd_test_project_state_index": (C.c_int64, [bp, C.c_uint64]),
         "ls_amd_corr_create": (C.c_int, [C.POINTER(vp), bp, vp, C.c_int64, vp]),
         "ls_amd_corr_modes": (C.c_int, [vp]),
         "ls_amd_corr_densities": (C.c_int, [vp, C.c_int, vp, c_f64p, c_f64p, C.c_int, vp]),

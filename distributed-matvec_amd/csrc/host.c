@@ -6042,6 +6042,179 @@ char const *ls_amd_expand_kernel_name(ls_amd_expand const *ex) {
 }
 
 /* ============================================================================================ */
+/* projection into a sector (include/ls_amd.h: ls_amd_project; csrc/k_project_t.hpp) */
+/* ============================================================================================ */
+/* the layout of the full-basis vector -- the one block of the expansion with A = every site / mode -- and F; host only: the refusals
+ * of ls_amd_project_create that need no device live here */
+static int project_layout_of(ls_hs_basis const *basis, lsk_project *pj) {
+    char const *who = "ls_amd_project";
+    if (!basis) return set_error("%s: NULL basis", who);
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    int const spin = basis->particle_type == LS_HS_SPIN;
+    if (!spin && basis->spin_inversion != 0) return set_error("%s: a fermionic basis has no spin inversion", who);
+    memset(pj, 0, sizeof(*pj));
+    if (!spin && e->product) {
+        int const L = basis->number_sites; /* L <= 32 */
+        long double const f = (long double)binom(L, e->prod_up) * (long double)binom(L, e->prod_dn);
+        if (f > 4.0e18L) return set_error("%s: the full basis has more than 2^62 states", who);
+        pj->kind = LSK_PROJECT_PRODUCT;
+        pj->half = L; pj->n_up = e->prod_up; pj->n_dn = e->prod_dn;
+        pj->n_low = (int64_t)binom(L, e->prod_up);
+        pj->full = pj->n_low * (int64_t)binom(L, e->prod_dn);
+        return 0;
+    }
+    expand_layout lay; /* every site in A: one block of one column, F rows */
+    uint64_t const all = e->nbits >= 64 ? ~0ULL : ((1ULL << e->nbits) - 1);
+    if (expand_layout_weight(&lay, who, spin ? "sites" : "modes", e->nbits, e->hamming_weight, all) != 0) return -1;
+    pj->kind = e->hamming_weight < 0 ? LSK_PROJECT_ALL : LSK_PROJECT_FIXED;
+    pj->full = lay.total;
+    return 0;
+}
+
+int64_t ls_amd_test_project_full_size(ls_hs_basis const *basis) {
+    lsk_project pj;
+    if (project_layout_of(basis, &pj) != 0) return -1;
+    return pj.full;
+}
+
+static int64_t project_host_rank(uint64_t s) { /* combinadic rank among the words of equal popcount (positions < 64, k < LSK_BINOM_K) */
+    int64_t idx = 0;
+    for (int k = 1; s; ++k, s &= s - 1) idx += (int64_t)binom(__builtin_ctzll(s), k);
+    return idx;
+}
+
+/* host only: index(state) of the kernels -- the position of `state` among the ascending states of the basis without symmetries --
+ * or -1 with a message that names why the word is no state of the basis */
+int64_t ls_amd_test_project_state_index(ls_hs_basis const *basis, uint64_t state) {
+    lsk_project pj;
+    if (project_layout_of(basis, &pj) != 0) return -1;
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    int const spin = basis->particle_type == LS_HS_SPIN;
+    uint64_t const all = e->nbits >= 64 ? ~0ULL : ((1ULL << e->nbits) - 1);
+    if (state & ~all) {
+        set_error("ls_amd_project: the state 0x%llx has bits above the %d %s of the basis", (unsigned long long)state, e->nbits, spin ? "sites" : "modes");
+        return -1;
+    }
+    if (pj.kind == LSK_PROJECT_PRODUCT) {
+        uint64_t const lo = state & ((1ULL << pj.half) - 1), hi = state >> pj.half;
+        int const nu = __builtin_popcountll(lo), nd = __builtin_popcountll(hi);
+        if (nu != pj.n_up || nd != pj.n_dn) {
+            set_error("ls_amd_project: the state 0x%llx has the particle numbers (%d up, %d down), the basis (%d up, %d down)",
+                      (unsigned long long)state, nu, nd, pj.n_up, pj.n_dn);
+            return -1;
+        }
+        return project_host_rank(hi) * pj.n_low + project_host_rank(lo);
+    }
+    if (pj.kind == LSK_PROJECT_FIXED) {
+        int const w = __builtin_popcountll(state);
+        if (w != e->hamming_weight) {
+            set_error("ls_amd_project: the state 0x%llx has %s %d, the basis %d", (unsigned long long)state,
+                      spin ? "Hamming weight" : "particle number", w, e->hamming_weight);
+            return -1;
+        }
+        return project_host_rank(state);
+    }
+    return (int64_t)state;
+}
+
+struct ls_amd_project {
+    lsk_basis bs;             /* device tables owned by the basis */
+    lsk_project pj;
+    int pm1;                  /* every character is +-1: f64 allowed */
+    int fermi;                /* a fermionic basis: k_project_pull_fermi */
+    int modes;
+    double *d_norms;          /* owned: n(r) of every row */
+    int *d_err;               /* owned */
+    uint64_t const *d_reps;   /* borrowed */
+    uint64_t const *d_binom;
+    int64_t n;
+};
+
+void ls_amd_project_destroy(ls_amd_project *p) {
+    if (!p) return;
+    if (p->d_norms) lsk_free(p->d_norms);
+    if (p->d_err) lsk_free(p->d_err);
+    free(p);
+}
+
+static int project_setup(ls_amd_project *p, ls_hs_basis const *basis, void *stream) {
+    if (basis_device(basis, &p->bs) != 0) return -1;
+    p->pm1 = cross_every_char_pm1(basis);
+    if (device_binom(&p->d_binom) != 0) return -1;
+    void *q = NULL;
+    DEV(lsk_malloc(&q, 4 * sizeof(int)));
+    p->d_err = (int *)q;
+    DEV(lsk_memset_async(p->d_err, 0, 4 * sizeof(int), stream));
+    DEV(lsk_malloc(&q, 8 * (size_t)(p->n > 0 ? p->n : 1)));
+    p->d_norms = (double *)q;
+    /* the stabiliser norms, by the routine the expansion and the cross-sector plans use */
+    DEV(lsk_norms(p->bs, p->n, p->d_reps, p->d_norms, stream));
+    DEV(lsk_sync(stream));
+    return 0;
+}
+
+int ls_amd_project_create(ls_amd_project **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, void *stream) {
+    if (out) *out = NULL;
+    if (!out || !basis) return set_error("ls_amd_project_create: NULL %s", !out ? "handle" : "basis");
+    if (n < 0 || (n > 0 && !d_reps)) return set_error("ls_amd_project_create: NULL representatives or a negative count");
+    lsk_project pj;
+    if (project_layout_of(basis, &pj) != 0) return -1;
+    ls_amd_project *p = (ls_amd_project *)calloc(1, sizeof(*p));
+    if (!p) return set_error("ls_amd_project_create: out of host memory");
+    p->pj = pj;
+    p->fermi = basis->particle_type != LS_HS_SPIN;
+    p->modes = BEXT(basis)->nbits;
+    p->d_reps = d_reps; p->n = n;
+    if (project_setup(p, basis, stream) != 0) { ls_amd_project_destroy(p); return -1; }
+    *out = p;
+    return 0;
+}
+
+int64_t ls_amd_project_full_size(ls_amd_project const *p) {
+    if (!p) { set_error("ls_amd_project_full_size: NULL plan"); return -1; }
+    return p->pj.full;
+}
+
+int ls_amd_project_apply(ls_amd_project *p, ls_amd_dtype dtype, int K, void const *d_phi, int64_t phi_s0, int64_t phi_s1, void *d_out,
+                         int64_t out_s0, int64_t out_s1, void *stream) {
+    if (!p || !d_phi || (!d_out && p && p->n > 0)) return set_error("ls_amd_project_apply: NULL %s", !p ? "plan" : (!d_phi ? "phi" : "out"));
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("ls_amd_project_apply: unknown dtype %d", (int)dtype);
+    if (dtype == LS_AMD_F64 && !p->pm1)
+        return set_error("ls_amd_project_apply: f64 needs +-1 characters (complex characters: use c128)");
+    if (K < 1 || K > LSK_PROJECT_MAX_K) return set_error("ls_amd_project_apply: K = %d columns, outside [1, %d]", K, LSK_PROJECT_MAX_K);
+    if (phi_s0 < 0 || phi_s1 < 0 || out_s0 < 0 || out_s1 < 0) return set_error("ls_amd_project_apply: negative strides");
+    if (p->n == 0) return 0;
+    lsk_project pj = p->pj;
+    pj.K = K;
+    pj.phi_s0 = phi_s0; pj.phi_s1 = phi_s1; pj.out_s0 = out_s0; pj.out_s1 = out_s1;
+    int const cplx = dtype == LS_AMD_C128;
+    if (p->fermi) DEV(lsk_project_pull_fermi(p->bs, pj, p->d_binom, cplx, p->n, p->d_reps, p->d_norms, d_phi, d_out, p->d_err, stream));
+    else DEV(lsk_project_pull(p->bs, pj, p->d_binom, cplx, p->n, p->d_reps, p->d_norms, d_phi, d_out, p->d_err, stream));
+    return 0;
+}
+
+int ls_amd_project_check(ls_amd_project *p, void *stream) {
+    if (!p) return set_error("ls_amd_project_check: NULL plan");
+    int flag = 0, zero = 0;
+    DEV(lsk_sync(stream));
+    DEV(lsk_d2h(&flag, p->d_err, sizeof(int)));
+    if (flag) {
+        DEV(lsk_h2d(p->d_err, &zero, sizeof(int)));
+        if (p->fermi)
+            return set_error("sector projection: a representative or one of its images is not in the basis (another particle number of the "
+                             "word or of a species, or bits above the %d modes): the array does not belong to this basis", p->modes);
+        return set_error("sector projection: a representative or one of its images is not in the basis (another Hamming weight, or bits "
+                         "above the %d sites): the array does not belong to this basis", p->modes);
+    }
+    return 0;
+}
+
+char const *ls_amd_project_kernel_name(ls_amd_project const *p) {
+    if (!p) { set_error("ls_amd_project_kernel_name: NULL plan"); return NULL; }
+    return p->fermi ? lsk_project_fermi_kernel_name() : lsk_project_kernel_name();
+}
+
+/* ============================================================================================ */
 /* two-point correlation matrices (include/ls_amd.h: ls_amd_corr; csrc/k_corr.hip) */
 /* ============================================================================================ */
 /* The device sums over the representatives alone (the RAW matrices); C[i][j] = |G|^-1 sum_g R[g(i)][g(j)] over the whole group is

@@ -648,6 +648,33 @@ int lsk_expand_fermi_push(lsk_basis bs, lsk_expand_fermi ex, uint64_t const *d_b
 /* parity of sigma(n) (host run of the device code) */
 int lsk_test_fermi_split_parity(uint64_t n, uint64_t mask_a, uint64_t mask_b);
 
+/* projection into a sector (k_project.hip, k_project_fermi.hip on k_project_t.hpp): the adjoint of the two
+ * expansions above with A = every site -- for the rows reps[0, n) and the K columns of phi,
+ *     out[i, c] = (|G| norms[i])^-1 sum_g chi(g) [sign(g, r_i)] phi[index(g r_i), c]        (norms[i] > 0; otherwise 0)
+ * summed over the permutation elements and, on a spin basis with the inversion, their flipped images with chi(g) inv.  index = the
+ * position among the ascending states of the basis without symmetries: the word (ALL), its combinadic rank (FIXED), or
+ * rank(high half) * n_low + rank(low half) (PRODUCT: the spinful (N_up, N_down) basis over 2 `half` modes) -- always < full.
+ * phi[j, c] = phi[j * phi_s0 + c * phi_s1], out[i, c] = out[i * out_s0 + c * out_s1] in ELEMENTS of the dtype.  Plain stores, one
+ * per (row, column); no atomics on the output.  *d_err is raised by a row or an image that is not a state of the basis; such an
+ * image is never ranked or loaded, such a row reads 0. */
+enum { LSK_PROJECT_ALL = 0, LSK_PROJECT_FIXED = 1, LSK_PROJECT_PRODUCT = 2 };
+#define LSK_PROJECT_MAX_K 64 /* the library's MAX_COLUMNS */
+#define LSK_PROJECT_COLS 8   /* columns per block of the K > 1 kernels */
+typedef struct lsk_project {
+    int kind;              /* LSK_PROJECT_* */
+    int half, n_up, n_dn;  /* PRODUCT: L and the particle numbers of the halves */
+    int64_t n_low;         /* PRODUCT: C(half, n_up) */
+    int64_t full;          /* F: the states of the basis without symmetries */
+    int K;                 /* columns, 1 .. LSK_PROJECT_MAX_K */
+    int64_t phi_s0, phi_s1, out_s0, out_s1;
+} lsk_project;
+char const *lsk_project_kernel_name(void);
+char const *lsk_project_fermi_kernel_name(void);
+int lsk_project_pull(lsk_basis bs, lsk_project pj, uint64_t const *d_binom, int cplx, int64_t n, uint64_t const *reps, double const *norms,
+                     void const *phi, void *out, int *d_err, void *stream);
+int lsk_project_pull_fermi(lsk_basis bs, lsk_project pj, uint64_t const *d_binom, int cplx, int64_t n, uint64_t const *reps,
+                           double const *norms, void const *phi, void *out, int *d_err, void *stream);
+
 /* two-point correlation matrices of a sector state (k_corr.hip, k_corr_fermi.hip): sums over the
  * representatives reps[0, n) alone -- the host averages them over the group afterwards.  A pair is the 16-bit word i | j << 8 of
  * two bits of the state word.  Both routines reduce in two steps without floating-point atomics: one partial per (block, pair) in

@@ -15,5 +15,7 @@ from . import expectation  # noqa: E402  (the module keeps its name here: its dr
 from .expectation import ExpectationPlan, dimer_correlations, expectation_values, pair_correlations  # noqa: F401,E402
 from . import evolve  # noqa: E402  (the module keeps its name here: its driver is evolve.evolve)
 from .evolve import EvolveResult, autocorrelation, bessel_series, propagate, propagator_coefficients  # noqa: F401,E402
+from . import projection  # noqa: E402
+from .projection import SectorProjection, product_state, project  # noqa: F401,E402
 
-__all__ = list(_api.__all__) + list(_entanglement.__all__) + [n for n in correlations.__all__ if n != "correlations"] + [n for n in expectation.__all__ if n != "expectation"] + [n for n in evolve.__all__ if n != "evolve"]
+__all__ = list(_api.__all__) + list(_entanglement.__all__) + list(projection.__all__) +[n for n in correlations.__all__ if n != "correlations"] + [n for n in expectation.__all__ if n != "expectation"] + [n for n in evolve.__all__ if n != "evolve"]

@@ -628,6 +628,45 @@ int ls_amd_test_fermi_expand_layout(ls_hs_basis const *basis, uint64_t mode_mask
                                     int64_t *cols, int64_t *offsets, int64_t *total);
 int ls_amd_test_fermi_split_parity(uint64_t mode_mask_a, int modes, uint64_t state);
 
+/* ---- projection of full-basis vectors into a sector (csrc/k_project.hip, k_project_fermi.hip) ------------
+ * The adjoint of the expansion above.  Let B be the matrix of the columns <s|r~> = conj(chi(g)) sign(g, r) n(r), s = g r (sign = 1
+ * on spin bases), so that the full-basis vector of a sector state is B psi (A = every site: unproject).  For a vector Phi over the
+ * ascending states of the same basis WITHOUT symmetries,
+ *     psi[r] = <r~|Phi> = (B+ Phi)[r] = (|G| n(r))^-1 sum_{g in G} chi(g) sign(g, r) Phi[index(g r)]      (n(r) > 0; otherwise 0)
+ * G includes the global spin inversion where the basis has one: every permutation element contributes its image t with chi(g) and
+ * t ^ mask with chi(g) inv, and |G| counts both.  index = the position in the layout of the expansion with A = every site / mode:
+ * the word itself without a fixed weight, the combinadic rank at fixed weight or particle number, rank_dn C(L, N_up) + rank_up on the
+ * spinful (N, N_up) product basis.  B+ B = 1, so projecting an expanded state returns it; B B+ is the projector on the sector.
+ * Pull form (k_project_pull; k_project_pull_fermi with the orbit sign): one representative per lane, the elements in a loop, the
+ * image ranked once per (row, element) for up to 8 columns, ONE plain store per (row, column) -- no atomics on the output, no
+ * floating-point atomics, and two calls return the same bytes.
+ *
+ * Scope: ONE partition (the whole sector and the whole full-basis vector on this device).  ONE create entry for both particle
+ * families (it dispatches on the basis): spin-1/2 bases and every fermionic basis the expansion takes, projected or not, the
+ * up <-> down flip included.  Refused by name: a NULL basis, more than 40 sites / modes without a fixed number, a weight beyond the
+ * binomial table (33), LS_AMD_F64 with characters other than +-1, K outside [1, 64]. */
+typedef struct ls_amd_project ls_amd_project;
+/* d_reps: the n ascending representatives of `basis` in HBM (borrowed until ls_amd_project_destroy).  Builds the norms n(r) -- by the
+ * routine of the expansion and the cross-sector plans; synchronises `stream`. */
+int ls_amd_project_create(ls_amd_project **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, void *stream);
+int64_t ls_amd_project_full_size(ls_amd_project const *plan); /* F: the states of the basis without symmetries */
+/* d_phi: K columns over the F full-basis states, element (j, c) at d_phi[j * phi_s0 + c * phi_s1]; d_out: K columns over the n
+ * representatives, element (i, c) at d_out[i * out_s0 + c * out_s1], every one ASSIGNED (rows of zero norm read 0) and nothing else
+ * written.  Strides in elements of `dtype`, not negative; (K, 1) -- the columns interleaved -- is the fast layout of d_phi (one gather
+ * fetches K neighbours).  1 <= K <= 64.  LS_AMD_F64 needs +-1 characters; anything else must be LS_AMD_C128.  Asynchronous on `stream`. */
+int ls_amd_project_apply(ls_amd_project *plan, ls_amd_dtype dtype, int K, void const *d_phi, int64_t phi_s0, int64_t phi_s1,
+                         void *d_out, int64_t out_s0, int64_t out_s1, void *stream);
+/* synchronises `stream` and reports the device error flag: -1 when a representative or one of its images is not in the basis
+ * (another Hamming weight or particle number, bits above the sites) -- such images are never ranked or loaded */
+int ls_amd_project_check(ls_amd_project *plan, void *stream);
+char const *ls_amd_project_kernel_name(ls_amd_project const *plan); /* "k_project_pull"; "k_project_pull_fermi" on a fermionic basis */
+void ls_amd_project_destroy(ls_amd_project *plan);
+/* Host-only test hook (no device): F of `basis`, or -1 with the message of the refusals above that need no device */
+int64_t ls_amd_test_project_full_size(ls_hs_basis const *basis);
+/* Host-only (no device): index(state), the position of `state` among the ascending states of the basis without symmetries, or -1 with
+ * a message that names why the word is no state of the basis (bits above the sites / modes, another weight or particle numbers) */
+int64_t ls_amd_test_project_state_index(ls_hs_basis const *basis, uint64_t state);
+
 /* ---- two-point correlation matrices of a sector state (csrc/k_corr.hip, k_corr_fermi.hip) ---------------
  * For a NORMALISED state psi on the n representatives of `basis` (projected or not), over the M bits of a state word (the sites
  * of a spin or spinless basis; the 2 L modes of a spinful one, mode (i, up) = bit i, mode (i, down) = bit i + L):
