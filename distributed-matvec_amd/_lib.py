@@ -275,6 +275,7 @@ def load():
         "ls_amd_test_window_find": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_uint64]),
         "ls_amd_test_nw_find": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_uint64]),
         "ls_amd_test_chain_near_table": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int16)]),
+        "ls_amd_test_chain_wave_tables": (C.c_int, [C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_int)]),
         "ls_amd_test_rep_trivial_dihedral": (C.c_uint64, [C.c_uint64, C.c_int, C.c_int, C.c_int]),
         "ls_amd_bench_k4": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, vp, vp, vp]),
         "ls_amd_test_free": (None, [vp]),

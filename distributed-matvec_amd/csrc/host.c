@@ -1755,6 +1755,8 @@ struct ls_amd_plan {
     void *d_chain_cache;   /* [chain_cached][count] u32, or u64 when chain_wide */
     int chain_wide;        /* 64-bit ranks (>= 2^32 - 1 states) */
     uint64_t *d_chain_rec; /* fused records (lsk_chain_pack) replacing reps + the first cached pair */
+    void *d_chain_wave;    /* 32-bit states and ranks: word table + one 8-byte header per 64 rows (setup_chain_headers); headed wave-rows do not read their records */
+    int chain_row_bytes;   /* plan bytes per row the kernel streams with the headers, rounded up */
     double chain_v[2];
     int64_t chain_row0; /* global rank of the first local row (replicated-x plans) */
     void *d_htab;        /* hash table {rep -> x * norm(rep)} of the tile-pull families */
@@ -2398,6 +2400,72 @@ static int chain_eligible(ls_amd_plan const *pl) {
     }
     return 1;
 }
+/* Word tables of the wave headers (k_chain_t, lsk_chain_headers), bits 0..11 of a state being its low word:
+ *   U[class_off[k] + r] = the r-th 12-bit word of weight k in ascending order (class_off[13] = 4096),
+ *   Rg[w] = rank of w ^ (1 << low_site) inside its own weight class (low_site < 0: 0).
+ * The 64 rows of a wave that share their bits >= 12 hold 64 consecutive entries of U, and the cached pair (low_site, a site >= 12)
+ * sends row `high | w` to row Rg[w] of ONE block of rows (the header holds its start). */
+static void chain_wave_tables(int low_site, uint16_t *U, uint16_t *Rg, int *class_off) {
+    int pos[13];
+    uint16_t rank_in[4096];
+    memset(class_off, 0, sizeof(int) * 14);
+    for (int w = 0; w < 4096; ++w) ++class_off[__builtin_popcount(w) + 1];
+    for (int k = 0; k < 13; ++k) { class_off[k + 1] += class_off[k]; pos[k] = class_off[k]; }
+    for (int w = 0; w < 4096; ++w) {
+        int const k = __builtin_popcount(w);
+        rank_in[w] = (uint16_t)(pos[k] - class_off[k]);
+        U[pos[k]++] = (uint16_t)w;
+    }
+    for (int w = 0; w < 4096; ++w) Rg[w] = low_site >= 0 ? rank_in[w ^ (1 << low_site)] : 0;
+}
+int ls_amd_test_chain_wave_tables(int low_site, uint16_t *U, uint16_t *Rg, int *class_off) {
+    if (low_site >= 12) return set_error("ls_amd_test_chain_wave_tables: the low site lies below bit 12");
+    chain_wave_tables(low_site, U, Rg, class_off);
+    return 0;
+}
+/* Wave headers of the plans with 32-bit states and ranks (k_chain_t: f64 on fused records, c128 on states + cache).  One partition, 13..32 sites, at most one cached pair, which has one site
+ * below bit 12 and one at or above it (the bond that closes a ring; an open chain has none): a wave-row whose 64 rows share their
+ * bits >= 12 reads an 8-byte header and 64 entries of a 16 KB table (U, Rg and the low site's bit interleaved: one 4-byte hit per
+ * lane) instead of 64 8-byte records; the other wave-rows keep the records.  Every other such plan, and every plan under
+ * LS_AMD_CHAIN_RECORDS=1 (A/B runs, tests), gets headers that say "records" everywhere -- the kernel reads them unconditionally.
+ * Returns 1 when there is no room for them. */
+static int setup_chain_headers(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t const *d_reps, int nc, uint64_t xmask, void *stream) {
+    int const L = NBITS(pl->op->basis);
+    char const *e = getenv("LS_AMD_CHAIN_RECORDS");
+    int headed = !(e && atoi(e) != 0) && L >= 13 && L <= 32 && pl->dbs.proj == LSK_PROJ_NONE && pl->chain_row0 == 0 &&
+                 pl->family == FAMILY_DIRECT_PULL && pl->dbs.hamming_weight >= 0 && nc <= 1;
+    int lo = -1, hi = -1;
+    if (headed && nc == 1) {
+        lo = __builtin_ctzll(xmask);
+        hi = 63 - __builtin_clzll(xmask);
+        if (lo >= 12 || hi < 12) { headed = 0; lo = hi = -1; }
+    }
+    int const words = lsk_chain_words();
+    int64_t const n_hdr = (n + 63) / 64;
+    uint16_t U[4096], Rg[4096];
+    int class_off[14];
+    uint32_t *tab = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)words);
+    if (!tab) return set_error("out of memory");
+    chain_wave_tables(headed ? lo : -1, U, Rg, class_off);
+    for (int t = 0; t < words; ++t) tab[t] = (uint32_t)U[t] | ((uint32_t)Rg[U[t]] << 16) | (lo >= 0 ? (((uint32_t)U[t] >> lo) & 1u) << 31 : 0u);
+    /* [word table][headers][counter of the wave-rows without a header] */
+    size_t const tab_bytes = sizeof(uint32_t) * (size_t)words, hdr_bytes = 8 * (size_t)n_hdr;
+    void *q;
+    if (lsk_malloc(&q, tab_bytes + hdr_bytes + 8) != 0) { free(tab); return 1; }
+    unsigned long long plain = 0;
+    unsigned long long *d_plain = (unsigned long long *)((char *)q + tab_bytes + hdr_bytes);
+    int const rc = lsk_h2d(q, tab, tab_bytes) || lsk_h2d(d_plain, &plain, 8) ||
+                   lsk_chain_headers(pl->dbs, index, n, d_reps, headed, hi, (char *)q + tab_bytes, d_plain, stream) || lsk_sync(stream) ||
+                   lsk_d2h(&plain, d_plain, 8);
+    free(tab);
+    if (rc) { lsk_free(q); return dev_error(); }
+    pl->d_chain_wave = q;
+    /* plan bytes per row: 8 per wave-row + 64 rows of records (f64: 8 bytes; c128: the 4-byte state + 4 per cached pair) per
+     * wave-row still on them, rounded up; all on records: theirs */
+    int const rec = pl->cplx ? 4 + 4 * nc : 8;
+    pl->chain_row_bytes = headed ? (int)((8 * (uint64_t)n_hdr + 64 * (uint64_t)rec * (uint64_t)plain + (uint64_t)n - 1) / (uint64_t)n) : rec;
+    return 0;
+}
 /* tile map with 1024-row tiles + the cache of partner ranks of the exchange pairs outside the runs (for a ring: the
  * bond that closes it) -- 4 bytes per row instead of a ranking loop of `weight` steps per row and matvec.
  * Leaves pl->has_chain == 0 (and no tile map) when a partner leaves the basis: k_direct reports that at run time,
@@ -2477,6 +2545,17 @@ static int setup_chain(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t con
         DEV(lsk_chain_pack(n, d_reps, pl->chain_cached ? pl->d_chain_cache : NULL, (uint64_t *)q, stream));
         DEV(lsk_sync(stream));
         if (pl->chain_cached <= 1 && pl->d_chain_cache) { lsk_free(pl->d_chain_cache); pl->d_chain_cache = NULL; }
+    }
+    if (NBITS(pl->op->basis) <= 32 && !pl->chain_wide && n > 0) { /* (f64 on the records, c128 on its two arrays) */
+        int const rc = setup_chain_headers(pl, index, n, d_reps, pl->chain_cached, pl->chain_cached > 0 ? cx[0] : 0, stream);
+        if (rc < 0) return -1;
+        if (rc > 0) { /* no room: the generic row kernel */
+            if (pl->d_chain_rec) { lsk_free(pl->d_chain_rec); pl->d_chain_rec = NULL; }
+            if (pl->d_chain_cache) { lsk_free(pl->d_chain_cache); pl->d_chain_cache = NULL; }
+            if (pl->d_tilemap) { lsk_free(pl->d_tilemap); pl->d_tilemap = NULL; memset(&pl->tilemap, 0, sizeof(pl->tilemap)); }
+            pl->chain_cached = 0;
+            return 0;
+        }
     }
     pl->has_chain = 1;
     return 0;
@@ -3435,6 +3514,7 @@ void ls_amd_plan_destroy(ls_amd_plan *pl) {
     if (pl->d_tilemap) lsk_free(pl->d_tilemap);
     if (pl->d_chain_cache) lsk_free(pl->d_chain_cache);
     if (pl->d_chain_rec) lsk_free(pl->d_chain_rec);
+    if (pl->d_chain_wave) lsk_free(pl->d_chain_wave);
     if (pl->d_pair_recs) lsk_free(pl->d_pair_recs);
     for (int k = 0; k < 6; ++k) if (pl->d_hub[k]) lsk_free(pl->d_hub[k]);
     if (pl->d_pair_rows) lsk_free(pl->d_pair_rows);
@@ -3618,7 +3698,7 @@ int ls_amd_matvec_replicated(ls_amd_plan *pl, void const *d_x_global, void *d_y_
         if (pl->has_chain)
             DEV(lsk_chain(pl->dop, pl->dbs, pl->gindex, pl->cplx, pl->chain_wide, pl->d_chain_rec != NULL, pl->tilemap, ps->count,
                           pl->d_chain_rec ? pl->d_chain_rec : ps->d_reps, pl->chain_row0, pl->gindex.count, d_x_global, d_y_local,
-                          pl->chain_cached, pl->d_chain_cache, pl->chain_v[0], pl->chain_v[1], stream));
+                          pl->chain_cached, pl->d_chain_cache, pl->chain_v[0], pl->chain_v[1], pl->d_chain_wave, stream));
         else
             DEV(lsk_direct_gx(pl->dop, pl->dbs, pl->gindex, pl->cplx, pl->tilemap, ps->d_reps, pl->d_row_gidx, d_x_global,
                           d_y_local, pl->d_err, stream));
@@ -3749,13 +3829,14 @@ char const *ls_amd_plan_kernel_name(ls_amd_plan const *pl) {
 int ls_amd_plan_packet_bytes(ls_amd_plan const *pl) { return pl->key_bytes + (pl->cplx ? 16 : 8); }
 /* bytes of per-row plan / basis data the plan's dominant kernel streams from HBM next to x and y (the roofline's
  * compulsory traffic is rows * (this + 2 w)): the staged row kernel reads the fused 8-byte record, or the low state word(s)
- * plus one cached partner rank per cached pair; the generic row kernels read the 8-byte state; the projected pull kernel
+ * plus one cached partner rank per cached pair -- with wave headers (setup_chain_headers) 8 bytes per wave-row and those records
+ * only for the wave-rows without one, rounded up; the generic row kernels read the 8-byte state; the projected pull kernel
  * the state and norm(alpha) */
 int ls_amd_plan_row_bytes(ls_amd_plan const *pl) {
     if (pl->has_hubbard) return 0; /* the species tables are O(sqrt N) and cache-resident: x and y are the whole stream */
     if (pl->has_pairs) return pl->pairs.wide ? 8 : 4; /* the plan's 4-byte copy of the states, or (33..64 sites) the 8-byte representatives */
     if (pl->has_chain) {
-        if (pl->d_chain_rec) return 8;
+        if (pl->d_chain_wave) return pl->chain_row_bytes; /* the records' bytes, or with wave headers what they and the remaining records come to */
         int const narrow = NBITS(pl->op->basis) <= 32 && !pl->chain_wide;
         return (narrow ? 4 : 8) + pl->chain_cached * (pl->chain_wide ? 8 : 4);
     }
@@ -4040,7 +4121,7 @@ int ls_amd_matvec(ls_amd_plan *pl, void const *const *d_x, void *const *d_y, voi
         if (pl->has_chain)
             DEV(lsk_chain(pl->dop, pl->dbs, ps->index, pl->cplx, pl->chain_wide, pl->d_chain_rec != NULL, pl->tilemap, ps->count,
                           pl->d_chain_rec ? pl->d_chain_rec : ps->d_reps, 0, ps->count, d_x[0], d_y[0], pl->chain_cached,
-                          pl->d_chain_cache, pl->chain_v[0], pl->chain_v[1], stream));
+                          pl->d_chain_cache, pl->chain_v[0], pl->chain_v[1], pl->d_chain_wave, stream));
         else if (pl->has_pairs)
             DEV(lsk_pairs(pl->pairs, pl->dbs.hamming_weight, pl->cplx, pl->tilemap, ps->count, d_x[0], d_y[0], stream));
         else if (pl->has_hubbard)

@@ -670,6 +670,7 @@ extern "C" int lsk_direct_gx(lsk_operator op, lsk_basis bs, lsk_index ix, int cp
 constexpr int kChainHalo = 512;    // >= C(11, 5)
 constexpr int kChainLdsPairs = 12; // pairs lo < 12 are served from the LDS window
 constexpr int kChainFar = 12;      // far-pair gathers in flight per row before the first wait (8 / 10 / 12: 7.67 / 7.66 / 7.63 ms)
+constexpr uint32_t kChainWords = 4096; // wave headers: the low word is bits 0..11, one table entry per 12-bit word
 
 // W = state word (u32 up to 32 sites, u64 up to 64), R = rank type (u32 while the basis has < 2^32 - 1 states, else u64),
 // CPLX = complex128 vectors (real operator; the window holds double2, gathers are 16 bytes per lane), TILE rows per
@@ -697,9 +698,9 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
                                                     int near_off,
                                                     uint64_t const *__restrict__ tilemap, int64_t slots_per_xcd, int64_t n,
                                                     uint64_t const *__restrict__ reps, void const *__restrict__ x_v,
-                                                    void *__restrict__ y_v, int hb, int n_cached,
+                                                    void *__restrict__ y_v, int n_cached,
                                                     R const *__restrict__ cache, double cv0, double cv1, int64_t row0,
-                                                    int64_t n_x) {
+                                                    int64_t n_x, uint32_t const *__restrict__ wave_plan) {
     typedef typename ChainX<CPLX>::type X;
     typedef WordTraits<W> WT;
     constexpr int NB = ChainTraits<W, R>::NB;
@@ -710,6 +711,7 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
     constexpr int WINDOW = TILE + 2 * HALO + 2;
     constexpr int FAR = CPLX ? kChainFarC : kChainFar;
     constexpr R kNone = ~(R)0;
+    constexpr int hb = kChainLdsPairs; // pairs from here up are priced once per wave where its rows agree on them
     X const *__restrict__ x = (X const *)x_v;
     X *__restrict__ y = (X *)y_v;
     // profiling builds only (make ablate, LS_AMD_ABLATE & 128): ONE MORE 8-byte stream per row, prefetched like the records -- what a
@@ -733,6 +735,16 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
     const int lane = threadIdx.x & 63;
     tilemap += (int64_t)xcd * slots_per_xcd;
     uint32_t const *__restrict__ reps32 = reinterpret_cast<uint32_t const *>(reps);
+    // Wave headers (HDR: 32-bit states and ranks; lsk_chain_headers): wave_plan = the word table, kChainWords x u32 in (weight,
+    // value) order: 12-bit word | its rank after the cached pair's low site is flipped << 16 | that site's bit << 31; then two
+    // u32 per 64 rows: [0] = common bits >= 12 | table index of the first row's low word (all ones in the low 12 bits: the rows
+    // do not share their high part -- that wave-row runs on its records as before), [1] = rank of the first row of the block
+    // the cached pair leads to | the pair's high bit << 31 (ranks of <= 32 sites stay below 2^30).  A lane is anti-aligned when
+    // the two top bits differ.  A headed wave-row reads 8 bytes + one 4-byte table hit per lane instead of an 8-byte record per
+    // row (c128: of a 4-byte state and a 4-byte cache entry).  Plans the headers do not serve (two cached pairs, a cached pair
+    // that does not cross bit 12, < 13 sites, row0 != 0) hold all ones in every header.
+    constexpr bool HDR = REC || (CPLX && sizeof(W) == 4 && sizeof(R) == 4);
+    constexpr int NSUB = TILE / kBlock;
     for (int64_t t = blockIdx.x >> 3; t < slots_per_xcd; t += blocks_per_xcd) {
         const uint64_t slot = tilemap[t];
         const int cnt = (int)(slot >> 48);
@@ -747,8 +759,7 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
             if (REC) {
                 const uint64_t rec = __builtin_nontemporal_load(reps + row);
                 a_out = (W)(uint32_t)rec;
-                t0_out = (R)(uint32_t)(rec >> 32);
-                if (n_cached == 0) t0_out = kNone;
+                t0_out = (R)(uint32_t)(rec >> 32); // (no cached pair: lsk_chain_pack wrote ~0)
             } else {
                 if (sizeof(W) == 4) a_out = (W)__builtin_nontemporal_load(reps32 + 2 * row); // low word only
                 else a_out = (W)__builtin_nontemporal_load(reps + row);
@@ -760,9 +771,24 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
         // Lanes past the end of a partial tile stay ACTIVE as ghosts of the tile's last row (they recompute it and
         // store nothing): the far pairs are priced lane-parallel, which needs every lane of a live wave.
         const int wave0 = (int)(threadIdx.x & ~63u);
+        // the headers of this wave's NSUB wave-rows (tiles start at multiples of TILE): lane s holds word [0] of iteration s's,
+        // lane NSUB + s its word [1] (the lanes from 2 NSUB on repeat them: no lane mask to keep)
+        uint32_t hq = ~0u;
+        if (HDR) {
+            const uint32_t hw = 2 * (uint32_t)(i0 >> 6) + 2 * ((threadIdx.x >> 6) + (uint32_t)(lane % NSUB) * (kBlock / 64)) + (lane / NSUB) % 2;
+            if (((int64_t)(hw >> 1) << 6) < n) hq = wave_plan[kChainWords + hw];
+        }
+        // the row of iteration s: table word of a headed wave-row (the lanes of a wave are consecutive words of one weight), else the record
+        auto fetch_row = [&](int s, int64_t row) {
+            if (HDR) {
+                const uint32_t ti = (uint32_t)__builtin_amdgcn_readlane((int)hq, s) & (kChainWords - 1u);
+                if (ti != kChainWords - 1u) { a_next = (W)wave_plan[ti + lane]; return; } // (profiling builds: no extra stream here)
+            }
+            load_row(row, a_next, t0_next, t1_next);
+        };
         if (wave0 < cnt) { // first row of this thread: requested before the window is staged
             const int64_t rr = i0 + ((int)threadIdx.x < cnt ? (int)threadIdx.x : cnt - 1);
-            load_row(rr, a_next, t0_next, t1_next);
+            fetch_row(0, rr);
         }
         __syncthreads(); // every wave is done with the previous window (and s_binom is loaded)
         if (CPLX) {
@@ -785,39 +811,54 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
         __syncthreads();
         const int own0 = (int)(row0 + i0 - w0);
         X y_pending = cx_zero<X>(); // stored one iteration late (see k_chain)
-        int64_t i_pending = -1;
+        int r_pending = -1;         // (row of the tile: one register, not two)
 #pragma unroll 1
         for (int sub = 0; sub < TILE / kBlock; ++sub) {
             const int r = sub * kBlock + threadIdx.x;
-            if (i_pending >= 0) cx_store_nt(y + i_pending, y_pending);
-            i_pending = -1;
-            const W a = a_next;
-            const R t0 = t0_next, t1 = t1_next;
+            if (r_pending >= 0) cx_store_nt(y + i0 + r_pending, y_pending);
+            r_pending = -1;
+            W a = a_next;
+            R t0 = t0_next;
+            const R t1 = t1_next;
             const uint64_t ex = ex_next;
             if (sub + 1 < TILE / kBlock && (sub + 1) * kBlock + wave0 < cnt) {
                 const int64_t in = i0 + (r + kBlock < cnt ? r + kBlock : cnt - 1);
-                load_row(in, a_next, t0_next, t1_next);
+                fetch_row(sub + 1, in);
             }
             if (sub * kBlock + wave0 >= cnt) continue; // wave-uniform: the whole wave is past the end
             const bool ghost = r >= cnt;
             const int64_t i = i0 + (ghost ? cnt - 1 : r);
             const R ig = (R)(row0 + i);
-            X g0 = cx_zero<X>(), g1 = cx_zero<X>();
-            if (n_cached > 0) g0 = x[t0 != kNone ? t0 : ig];
-            if (n_cached > 1) g1 = x[t1 != kNone ? t1 : ig];
-            const int jr = own0 + (int)(i - i0);
-            const X xr = s_x[jr];
-            double dr, di;
-            diag_coeff<W, true>(runs, n_diag, diag, a, dr, di);
-            X acc = cx_scale(dr, xr);
-            const W tdiff = a ^ (a >> 1);
             // The rows of a wave ascend, so every lane shares the common prefix of the first and the last state: pairs at or
             // above `ubit` (one past the highest bit on which those two differ) are wave-uniform.  92 % of the waves of
             // chain_32 have ubit <= 12; the others used to fall back to the per-lane loop for ALL their far pairs and now
             // only walk the pairs below ubit per lane.
-            const W a0 = readfirstlane_t<W>(a);
-            const W adiff = a0 ^ readlane_t<W>(a, 63);
-            const int ubit = adiff == 0 ? 0 : (int)(8 * sizeof(W)) - (sizeof(W) == 4 ? __clz((int)(uint32_t)adiff) : __clzll((long long)(uint64_t)adiff));
+            W a0;
+            int ubit;
+            const uint32_t h0 = HDR ? (uint32_t)__builtin_amdgcn_readlane((int)hq, sub) : ~0u;
+            if (HDR && (h0 & (kChainWords - 1u)) != kChainWords - 1u) { // headed wave-row: a_next held the table word
+                const uint32_t word = (uint32_t)a;
+                a0 = (W)(h0 & ~(kChainWords - 1u));
+                a = a0 | (W)(word & (kChainWords - 1u));
+                ubit = 0; // (<= 12 is all the split below asks)
+                // the cached pair: its anti-aligned lanes land in ONE block of rows, each at its table rank
+                const uint32_t h1 = (uint32_t)__builtin_amdgcn_readlane((int)hq, NSUB + sub);
+                t0 = (int32_t)(word ^ h1) < 0 ? (R)((h1 & 0x7fffffffu) + ((word >> 16) & 0x7fffu)) : kNone;
+            } else {
+                a0 = readfirstlane_t<W>(a);
+                const W adiff = a0 ^ readlane_t<W>(a, 63);
+                ubit = adiff == 0 ? 0 : (int)(8 * sizeof(W)) - (sizeof(W) == 4 ? __clz((int)(uint32_t)adiff) : __clzll((long long)(uint64_t)adiff));
+            }
+            const int jr = own0 + (int)(i - i0);
+            const X xr = s_x[jr];
+            // cached pairs: only the anti-aligned lanes gather (the aligned ones multiply their own x by zero, as ever)
+            X g0 = n_cached > 0 ? xr : cx_zero<X>(), g1 = n_cached > 1 ? xr : cx_zero<X>();
+            if (t0 != kNone) g0 = x[t0];
+            if (n_cached > 1 && t1 != kNone) g1 = x[t1];
+            double dr, di;
+            diag_coeff<W, true>(runs, n_diag, diag, a, dr, di);
+            X acc = cx_scale(dr, xr);
+            const W tdiff = a ^ (a >> 1);
             const R ig0 = readfirstlane_t<R>(ig);
             const uint32_t dl = (uint32_t)(ig - ig0); // 0..63: the far gathers address x as (uniform base) + dl
             for (int q = 0; q < runs.n_runs; ++q) {
@@ -939,9 +980,9 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
             cx_fma(t1 != kNone ? cv1 : 0.0, g1, acc);
             if (kAblate && extra_stream && ex == 0x0123456789abcdefULL) cx_fma(1.0, xr, acc); // (practically never: keeps the load alive)
             y_pending = acc;
-            i_pending = ghost ? -1 : i;
+            r_pending = ghost ? -1 : r;
         }
-        if (i_pending >= 0) cx_store_nt(y + i_pending, y_pending);
+        if (r_pending >= 0) cx_store_nt(y + i0 + r_pending, y_pending);
     }
 }
 
@@ -996,6 +1037,57 @@ extern "C" int lsk_chain_pack(int64_t n, uint64_t const *reps, void const *cache
     LSK_LAUNCH_CHECK();
     return 0;
 }
+
+// wave headers of k_chain_t (layout: see the kernel): one thread per 64 rows.  A wave-row is headed when its rows share every
+// bit >= 12 -- then their low words are 64 consecutive words of one weight kl, i.e. 64 consecutive entries of the word table from
+// index class_off[kl] + (in-class rank of the first low word).  The cached pair (one site below bit 12, `high_site` >= 12; < 0:
+// none) sends every anti-aligned row of such a wave-row into the block of high ^ high_site, low weight kl -+ 1, whose first row
+// is the rank of that high part over the lowest kl -+ 1 bits (bit 31 of the header's second word: the pair's high bit).  The last, partial wave-row of the basis is never headed (its
+// ghost lanes repeat a row).  *n_plain counts the wave-rows without a header.
+__global__ __launch_bounds__(kBlock) void k_chain_headers(int64_t n, uint64_t const *__restrict__ reps, int hamming_weight, int high_site,
+                                                          uint64_t const *__restrict__ g_binom, uint2 *__restrict__ out,
+                                                          unsigned long long *__restrict__ n_plain) {
+    const int64_t n_hdr = (n + 63) >> 6;
+    for (int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x; w < n_hdr; w += (int64_t)gridDim.x * kBlock) {
+        uint2 h = make_uint2(~0u, ~0u);
+        const uint32_t first = (uint32_t)reps[w << 6];
+        if ((w << 6) + 63 < n && ((first ^ (uint32_t)reps[(w << 6) + 63]) >> 12) == 0) {
+            const uint32_t high = first & ~(kChainWords - 1u), low = first & (kChainWords - 1u);
+            const int kl = __popc(low);
+            uint32_t ti = (uint32_t)rank_combinadic_w<uint32_t, uint64_t>(low, g_binom);
+            for (int k = 0; k < kl; ++k) ti += (uint32_t)g_binom[12 * LSK_BINOM_K + k];
+            uint32_t base = 0;
+            if (high_site >= 0) {
+                const uint32_t hbit = (high >> high_site) & 1u;
+                const int kp = hbit ? kl + 1 : kl - 1;
+                if (kp >= 0 && kp <= 12 && kp <= hamming_weight)
+                    base = (uint32_t)rank_combinadic_w<uint32_t, uint64_t>((high ^ (1u << high_site)) | ((1u << kp) - 1u), g_binom);
+                base |= hbit << 31;
+            }
+            h = make_uint2(high | ti, base);
+        } else
+            atomicAdd(n_plain, 1ULL);
+        out[w] = h;
+    }
+}
+// headed == 0: every header all ones (the plan keeps its records)
+extern "C" int lsk_chain_headers(lsk_basis bs, lsk_index ix, int64_t n, uint64_t const *reps, int headed, int high_site, void *out,
+                                 unsigned long long *d_n_plain, void *stream) {
+    if (n == 0) return 0;
+    if (!headed) {
+        if (hipMemsetAsync(out, 0xff, 8 * (size_t)((n + 63) >> 6), (hipStream_t)stream) != hipSuccess) { snprintf(g_err, sizeof(g_err), "lsk_chain_headers: memset failed"); return -1; }
+        return 0;
+    }
+    if (bs.number_sites > 32 || bs.number_sites < 13 || bs.hamming_weight < 0 || high_site >= bs.number_sites || (high_site >= 0 && high_site < 12)) {
+        snprintf(g_err, sizeof(g_err), "lsk_chain_headers: plan out of range");
+        return -1;
+    }
+    hipLaunchKernelGGL(k_chain_headers, dim3(grid_for((n + 63) >> 6)), dim3(kBlock), 0, (hipStream_t)stream, n, reps, bs.hamming_weight,
+                       high_site, ix.binom, (uint2 *)out, d_n_plain);
+    LSK_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int lsk_chain_words(void) { return (int)kChainWords; }
 
 // binomial table in the rank type of the staged kernel: the u64 table as it is, or a u32 copy made once per device table
 __global__ void k_binom_narrow(uint64_t const *__restrict__ in, uint32_t *__restrict__ out, int n) {
@@ -1085,7 +1177,7 @@ static int chain_lds_image(int rsize, int rows, int weight, int elem, int ldsp, 
 template <typename W, typename R, bool CPLX, int TILE, bool REC>
 static int launch_chain(lsk_operator op, lsk_basis bs, lsk_index ix, lsk_tilemap tm, int64_t n, uint64_t const *reps,
                         int64_t row0, int64_t n_x, void const *x, void *y, int n_cached, void const *cache, double cv0,
-                        double cv1, void *stream) {
+                        double cv1, void const *wave_plan, void *stream) {
     int64_t gb = tm.slots_per_xcd * 8;
     ChainImage img;
     if (chain_lds_image((int)sizeof(R), ChainTraits<W, R>::NB, bs.hamming_weight, CPLX ? 16 : 8, CPLX ? 11 : kChainLdsPairs, &img) != 0) return -1;
@@ -1095,8 +1187,9 @@ static int launch_chain(lsk_operator op, lsk_basis bs, lsk_index ix, lsk_tilemap
     // some overlap the LDS / ALU phases of others.
     hipLaunchKernelGGL((k_chain_t<W, R, CPLX, TILE, REC>), dim3((unsigned)gb), dim3(kBlock), (size_t)img.bytes, (hipStream_t)stream, op.runs,
                        op.n_diag, op.diag, bs.hamming_weight, img.dev, img.bytes / 16, img.kc, img.near_off, tm.entries, tm.slots_per_xcd, n, reps, x, y,
-                       kChainLdsPairs, n_cached | ((kAblate && (bs.debug_ablate & 128)) ? 0x100 : 0) | ((kAblate && (bs.debug_ablate & 4096)) ? 0x200 : 0) |
-                           ((kAblate && (bs.debug_ablate & 8192)) ? 0x400 : 0), (R const *)cache, cv0, cv1, row0, n_x);
+                       n_cached | ((kAblate && (bs.debug_ablate & 128)) ? 0x100 : 0) | ((kAblate && (bs.debug_ablate & 4096)) ? 0x200 : 0) |
+                           ((kAblate && (bs.debug_ablate & 8192)) ? 0x400 : 0), (R const *)cache, cv0, cv1, row0, n_x,
+                       (uint32_t const *)wave_plan);
     LSK_LAUNCH_CHECK();
     return 0;
 }
@@ -1107,10 +1200,11 @@ extern "C" int lsk_chain_tile_rows(int cplx) { return cplx ? 512 : 1024; }
 
 extern "C" int lsk_chain(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, int wide_ranks, int fused_records, lsk_tilemap tm,
                          int64_t n, uint64_t const *reps, int64_t row0, int64_t n_x, void const *x, void *y, int n_cached,
-                         void const *cache, double cv0, double cv1, void *stream) {
+                         void const *cache, double cv0, double cv1, void const *wave_plan, void *stream) {
     if (n == 0 || tm.slots_per_xcd == 0) return 0;
     const bool narrow = bs.number_sites <= 32 && !wide_ranks;
-#define LSK_CHAIN_ARGS op, bs, ix, tm, n, reps, row0, n_x, x, y, n_cached, cache, cv0, cv1, stream
+    if ((wave_plan != nullptr) != narrow) { snprintf(g_err, sizeof(g_err), "lsk_chain: 32-bit states and ranks come with wave headers, the other plans without"); return -1; }
+#define LSK_CHAIN_ARGS op, bs, ix, tm, n, reps, row0, n_x, x, y, n_cached, cache, cv0, cv1, wave_plan, stream
     if (fused_records) { // `reps` is the record array made by lsk_chain_pack (32-bit states and ranks only)
         if (!narrow || cplx) { snprintf(g_err, sizeof(g_err), "lsk_chain: fused records need 32-bit states and ranks and f64 vectors"); return -1; }
         return launch_chain<uint32_t, uint32_t, false, 1024, true>(LSK_CHAIN_ARGS);

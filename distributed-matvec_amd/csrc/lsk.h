@@ -267,11 +267,13 @@ int lsk_direct(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, int pull, 
 /* staged row kernel (k_chain_t): pull, real Hermitian operator, the full fixed-Hamming-weight basis without symmetries
  * (<= 64 sites; f64 or c128 vectors).  The tile map must have been built with lsk_chain_tile_rows(cplx)-row tiles.  The n
  * rows (reps, cache, y) are the global rows [row0, row0 + n) of the basis; x is the whole vector of n_x elements.
- * wide_ranks != 0: ranks (cache entries, indices into x) are 64-bit (bases with >= 2^32 states). */
+ * wide_ranks != 0: ranks (cache entries, indices into x) are 64-bit (bases with >= 2^32 states).
+ * wave_plan (<= 32 sites with 32-bit ranks, else NULL): the word table + wave headers of lsk_chain_headers; wave-rows with a header read
+ * it instead of their records. */
 int lsk_chain_tile_rows(int cplx);
 int lsk_chain(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, int wide_ranks, int fused_records, lsk_tilemap tm,
               int64_t n, uint64_t const *reps, int64_t row0, int64_t n_x, void const *x, void *y, int n_cached,
-              void const *cache, double cv0, double cv1, void *stream);
+              void const *cache, double cv0, double cv1, void const *wave_plan, void *stream);
 /* ---- staged row kernel for arbitrary exchange pairs (k_pairs_t, k_rows.hip): Heisenberg / XXZ on any lattice -------------
  * pairs are sorted by class: [0, n_near) both sites below bit 11, [n_near, n_near + n_str) i < 11 <= j, then both >= 11 */
 #define LSK_MAX_PAIRS 128
@@ -335,6 +337,14 @@ int lsk_narrow_states(int64_t n, uint64_t const *reps, uint32_t *out, void *stre
 /* fused_records != 0 (32-bit states and ranks): `reps` is out[] of lsk_chain_pack -- state | partner rank of the first
  * cached pair << 32 (cache == NULL: no cached pair) -- and `cache` only holds a second cached pair at cache + n */
 int lsk_chain_pack(int64_t n, uint64_t const *reps, void const *cache, uint64_t *out, void *stream);
+/* wave headers of the staged kernel (13..32 sites, 32-bit ranks): out[w] (8 bytes) describes rows 64 w .. 64 w + 63 when they
+ * share every bit >= 12, else it is all ones and *d_n_plain (a zeroed device word) counts it.  high_site: the site >= 12 of the
+ * cached pair, < 0 without one.  headed == 0 (any plan): all ones everywhere -- every wave-row on its records.  lsk_chain() expects the headers lsk_chain_words() 4-byte words past the start of wave_plan,
+ * behind the word table: entry t = the t-th 12-bit word in (weight, value) order | in-class rank of word ^ low site << 16 |
+ * the word's bit at the low site << 31. */
+int lsk_chain_headers(lsk_basis bs, lsk_index ix, int64_t n, uint64_t const *reps, int headed, int high_site, void *out,
+                      unsigned long long *d_n_plain, void *stream);
+int lsk_chain_words(void);
 /* partner ranks of a non-adjacent exchange pair for every row (u32, or u64 when wide_ranks); *d_flag is raised if a
  * partner leaves the basis */
 int lsk_chain_cache(lsk_basis bs, lsk_index ix, int64_t n, uint64_t const *reps, uint64_t xmask, void *out, int wide_ranks,

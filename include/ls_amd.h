@@ -770,6 +770,10 @@ int ls_amd_test_nw_find(uint64_t const *reps, int n, uint64_t key);
 /* Host-only test hook: the near-pair table of the staged row kernel (distributed-matvec_amd/csrc/k_rows.hip: chain_lds_image) for
  * vectors of `elem` bytes per entry and `ldsp` pairs served from the LDS window: 480 entries of four int16 into `out`. */
 int ls_amd_test_chain_near_table(int elem, int ldsp, int16_t *out);
+/* Host-only test hook: the word tables behind the wave headers of the staged row kernel (host.c: chain_wave_tables).  U[4096]: the
+ * 12-bit words grouped by weight, ascending inside each weight, class k starting at class_off[k] (14 entries, the last 4096);
+ * Rg[4096]: Rg[w] = rank of w ^ (1 << low_site) inside its own weight class (low_site < 12; < 0: all zero). */
+int ls_amd_test_chain_wave_tables(int low_site, uint16_t *U, uint16_t *Rg, int *class_off);
 /* Host-only test hook: the orbit minimum of `a` under the translations of a ring of L sites (and its reflections / the global
  * spin flip when asked), computed by the candidate-pruning routine the projected-basis kernels use (K4, trivial sector). */
 uint64_t ls_amd_test_rep_trivial_dihedral(uint64_t a, int L, int inv, int reflect);
