@@ -207,16 +207,24 @@ class Operator:
         out.basis.spec = self.basis.spec
         return out
 
-    def mapsSector(self, target_basis: Basis, explain: bool = False, signs: bool = False) -> bool:
+    def mapsSector(self, target_basis: Basis, explain: bool = False, signs: bool = False, subgroup: bool = False) -> bool:
         """whether this operator maps its own (source) sector into the sector of target_basis (ls_amd_operator_maps_sector: the
         exact covariance check U_g A U_g^-1 = chi2(g) conj(chi1(g)) A on the term tables; host only).  explain=True raises LsAmdError
         with the reason -- the offending generator, or why the two bases cannot be paired -- instead of returning False.
         signs=True runs the rule that CrossSectorPlan runs (ls_amd_operator_maps_sector_signed): the same answer for bases without
         permutation signs, and for projected fermionic bases -- which the plain rule refuses -- the covariance under
         U_g|a> = sign(g, a)|g.a>, with the Jordan-Wigner strings of the terms absorbed (c+_k, c_k, n_q, S^z_q, pair operators
-        between momentum, point-group and spin-flip sectors; particle numbers are not examined)."""
+        between momentum, point-group and spin-flip sectors; particle numbers are not examined).
+        subgroup=True runs the rule of CrossSectorPlan(groups="restrict") instead (ls_amd_operator_maps_subgroup_sector): the two
+        bases may have different generators as long as every generator of the target is an element of the source group (and a
+        spin inversion / spin_flip of the target is one of the source), and the covariance is asked of the TARGET's generators
+        only, with chi1 taken from the source's element -- signed where a basis is a projected fermionic one, whatever `signs`."""
         L = _lib.load()
-        rc = (L.ls_amd_operator_maps_sector_signed if signs else L.ls_amd_operator_maps_sector)(self.payload, target_basis.payload)
+        if subgroup:
+            rule = L.ls_amd_operator_maps_subgroup_sector
+        else:
+            rule = L.ls_amd_operator_maps_sector_signed if signs else L.ls_amd_operator_maps_sector
+        rc = rule(self.payload, target_basis.payload)
         if rc != 0 and explain:
             raise LsAmdError(L.ls_amd_last_error().decode("utf-8", "replace"))
         _lib.raise_pending_halt()
@@ -779,9 +787,23 @@ class CrossSectorPlan:
     offending generator otherwise; the check is Operator.mapsSector(target_basis, signs=True)); float64 needs a real operator and
     +-1 characters on both bases.  Spin bases, unprojected fermionic bases, and projected fermionic bases (spinless, spinful with
     spin_flip; up to 60 modes) whose generators are the same on both sides: there the kernel is "k_cross_pull_fermi", which
-    projects every image with the permutation signs (always +-1, so they never stand in the way of float64)."""
+    projects every image with the permutation signs (always +-1, so they never stand in the way of float64).
 
-    def __init__(self, operator: Operator, source_reps, target_basis: Basis, target_reps, dtype):
+    groups: what the two bases' symmetry groups may be (ls_amd_cross_create_groups).
+      "same" (default)  the same generator permutations in the same order; everything above.
+      "restrict"        the target group is a subgroup of the source group and A is covariant under the target's generators
+                        (Operator.mapsSector(target_basis, subgroup=True)): S^z_q from a ground state found with reflection and
+                        spin inversion into the translations-only sector k + q.  Host work only: the same kernels, to_csr works.
+                        A target without symmetries is always admitted (y = A B1 x on the plain basis).
+      "project"         any two bases of one particle type and number_sites and ANY operator, no covariance check: y is the
+                        component of A B1 x in the target sector, B2^+ A B1 x (sigma^z_0, c^+_0, a local quench; A = 1 moves a
+                        state between the sectors of two groups).  The kernel is "k_cross_project" ("k_cross_project_fermi"); the
+                        cost is |G2| times (2 |G2| with a target inversion) that of "restrict"; nnz counts the packets gathered
+                        per apply; to_csr is refused."""
+
+    GROUPS = {"same": 0, "restrict": 1, "project": 2}
+
+    def __init__(self, operator: Operator, source_reps, target_basis: Basis, target_reps, dtype, groups: str = "same"):
         torch = _torch()
         _lib.require_device()
         for name, t in (("source_reps", source_reps), ("target_reps", target_reps)):
@@ -793,10 +815,17 @@ class CrossSectorPlan:
         if not self.cplx and dtype not in (torch.float64, "f64"):
             raise LsAmdError(f"CrossSectorPlan: dtype {dtype} is neither float64 nor complex128")
         self.dtype = torch.complex128 if self.cplx else torch.float64
+        if groups not in self.GROUPS:
+            raise LsAmdError(f"CrossSectorPlan: groups = {groups!r} is none of 'same', 'restrict', 'project'")
+        self.groups = groups
         h = C.c_void_p()
-        _lib.check(_lib.load().ls_amd_cross_create(C.byref(h), operator.payload, target_basis.payload, 1 if self.cplx else 0,
-                                                   C.c_void_p(source_reps.data_ptr()), source_reps.numel(),
-                                                   C.c_void_p(target_reps.data_ptr()), target_reps.numel(), _stream_ptr()))
+        L = _lib.load()
+        tail = (C.c_void_p(source_reps.data_ptr()), source_reps.numel(), C.c_void_p(target_reps.data_ptr()), target_reps.numel(), _stream_ptr())
+        if groups == "same":
+            _lib.check(L.ls_amd_cross_create(C.byref(h), operator.payload, target_basis.payload, 1 if self.cplx else 0, *tail))
+        else:
+            _lib.check(L.ls_amd_cross_create_groups(C.byref(h), operator.payload, target_basis.payload, 1 if self.cplx else 0,
+                                                    self.GROUPS[groups], *tail))
         self.h = h
 
     def destroy(self):

@@ -5461,6 +5461,35 @@ static int not_fermionic(raw_term const *t) {
                      (unsigned long long)t->x, (unsigned long long)t->s, CANON_MAX_FREE, (unsigned long long)t->m);
 }
 
+/* the signed rule for one permutation p: *defect = the largest |U_p A U_p^-1 - f A| over the canonical entries (t: the n raw terms of
+ * A, c: their nc merged entries; tg: room for n terms; *both: scratch that grows, freed by the caller).  -1 when the image of a
+ * term is no fermionic operator (the message names the term as it was given). */
+static int signed_defect(raw_term const *t, int n, canon_term const *c, int64_t nc, int const *p, int L, double f_re, double f_im,
+                         raw_term *tg, canon_term **both, double *defect) {
+    uint64_t tab[64], nb[64];
+    perm_sign_table(p, L, tab, nb);
+    for (int k = 0; k < n; ++k) tg[k] = signed_conjugate(t[k], p, L, tab, nb);
+    canon_term *cg = NULL;
+    int64_t const ng = signed_expand(tg, n, &cg);
+    if (ng < 0) return not_fermionic(&t[-1 - ng]); /* (shown by the image only: the term as it was given) */
+    *both = (canon_term *)realloc(*both, sizeof(canon_term) * (size_t)(ng + nc > 0 ? ng + nc : 1));
+    memcpy(*both, cg, sizeof(canon_term) * (size_t)ng);
+    free(cg);
+    for (int64_t i = 0; i < nc; ++i) {
+        canon_term m = c[i];
+        m.re = -(f_re * c[i].re - f_im * c[i].im);
+        m.im = -(f_re * c[i].im + f_im * c[i].re);
+        (*both)[ng + i] = m;
+    }
+    int64_t const k = canon_merge(*both, ng + nc);
+    *defect = 0.0;
+    for (int64_t i = 0; i < k; ++i) {
+        double const d = fabs((*both)[i].re) > fabs((*both)[i].im) ? fabs((*both)[i].re) : fabs((*both)[i].im);
+        if (d > *defect) *defect = d;
+    }
+    return 0;
+}
+
 int ls_amd_operator_maps_sector_signed(ls_hs_operator const *op, ls_hs_basis const *target) {
     if (!op || !target) return set_error("ls_amd_operator_maps_sector_signed: NULL %s", !op ? "operator" : "target basis");
     if (!reg_get(op)) return set_error("ls_amd_operator_maps_sector_signed: unknown operator (ls_amd_adopt_operator first)");
@@ -5485,33 +5514,13 @@ int ls_amd_operator_maps_sector_signed(ls_hs_operator const *op, ls_hs_basis con
         for (int64_t i = 0; i < nc; ++i) { double const a = fabs(c[i].re) > fabs(c[i].im) ? fabs(c[i].re) : fabs(c[i].im); if (a > vmax) vmax = a; }
         double const tol = 1e-12 * vmax;
         tg = (raw_term *)malloc(sizeof(raw_term) * (size_t)(n > 0 ? n : 1));
-        uint64_t tab[64], nb[64];
         for (int g = 0; g < es->n_generators && rc == 0; ++g) {
             int const *p = es->gen_perms + (size_t)g * L;
             int const ord = perm_order(p, L);
-            perm_sign_table(p, L, tab, nb);
-            for (int k = 0; k < n; ++k) tg[k] = signed_conjugate(t[k], p, L, tab, nb);
-            canon_term *cg = NULL;
-            int64_t const ng = signed_expand(tg, n, &cg);
-            if (ng < 0) { rc = not_fermionic(&t[-1 - ng]); break; } /* (shown by the image only: the term as it was given) */
             /* g.A - f A, f = chi2(g) conj(chi1(g)) = exp(-2 pi i (sector2 - sector1) / order) */
             double const phi = -2.0 * M_PI * (double)(et->gen_sectors[g] - es->gen_sectors[g]) / (double)ord;
-            double const f_re = cos(phi), f_im = sin(phi);
-            both = (canon_term *)realloc(both, sizeof(canon_term) * (size_t)(ng + nc > 0 ? ng + nc : 1));
-            memcpy(both, cg, sizeof(canon_term) * (size_t)ng);
-            free(cg);
-            for (int64_t i = 0; i < nc; ++i) {
-                canon_term m = c[i];
-                m.re = -(f_re * c[i].re - f_im * c[i].im);
-                m.im = -(f_re * c[i].im + f_im * c[i].re);
-                both[ng + i] = m;
-            }
-            int64_t const k = canon_merge(both, ng + nc);
             double defect = 0.0;
-            for (int64_t i = 0; i < k; ++i) {
-                double const d = fabs(both[i].re) > fabs(both[i].im) ? fabs(both[i].re) : fabs(both[i].im);
-                if (d > defect) defect = d;
-            }
+            if (signed_defect(t, n, c, nc, p, L, cos(phi), sin(phi), tg, &both, &defect) != 0) { rc = -1; break; }
             if (defect > tol)
                 rc = set_error("the operator does not map the source sector into the target sector: under generator %d (sector %d -> %d of "
                                "order %d) it must pick up the factor exp(-2 pi i %d / %d), and misses that by %.3g",
@@ -5519,6 +5528,98 @@ int ls_amd_operator_maps_sector_signed(ls_hs_operator const *op, ls_hs_basis con
         }
     }
     free(t); free(tg); free(c); free(both);
+    return rc;
+}
+
+/* ---- bases with DIFFERENT groups (include/ls_amd.h: ls_amd_cross_create_groups) ---- */
+/* what both new modes need of a pair of bases: one particle type, one number of sites, one word */
+static int cross_groups_preconditions(ls_hs_basis const *a, ls_hs_basis const *b) {
+    struct ls_amd_basis_ext const *ea = (struct ls_amd_basis_ext const *)reg_get(a), *eb = (struct ls_amd_basis_ext const *)reg_get(b);
+    if (!ea || !eb) return set_error("cross-sector: unknown basis (ls_amd_adopt_basis first)");
+    if (a->particle_type != b->particle_type) return set_error("cross-sector: the bases have different particle types (%d and %d)", a->particle_type, b->particle_type);
+    if (a->number_sites != b->number_sites || ea->nbits != eb->nbits)
+        return set_error("cross-sector: the bases have different number_sites (%d and %d)", a->number_sites, b->number_sites);
+    if (ea->nbits > 64) return set_error("cross-sector: more than 64 sites are not supported (number_words == 1)");
+    return 0;
+}
+
+/* the element of the basis' group (the closure its extension holds; spinful bases: over the lifted permutations) that is the
+ * permutation p, or -1 */
+static int group_element_of(struct ls_amd_basis_ext const *e, int const *p, int L) {
+    for (int g = 0; g < e->order; ++g)
+        if (memcmp(e->perms + (size_t)g * L, p, sizeof(int) * (size_t)L) == 0) return g;
+    return -1;
+}
+
+int ls_amd_operator_maps_subgroup_sector(ls_hs_operator const *op, ls_hs_basis const *target) {
+    if (!op || !target) return set_error("ls_amd_operator_maps_subgroup_sector: NULL %s", !op ? "operator" : "target basis");
+    if (!reg_get(op)) return set_error("ls_amd_operator_maps_subgroup_sector: unknown operator (ls_amd_adopt_operator first)");
+    ls_hs_basis const *src = op->basis;
+    if (cross_groups_preconditions(src, target) != 0) return -1;
+    struct ls_amd_basis_ext const *es = BEXT(src), *et = BEXT(target);
+    int const L = es->nbits;
+    if (target->spin_inversion != 0 && src->spin_inversion == 0)
+        return set_error("cross-sector: the target basis has the spin inversion and the source basis has not: the target group is no "
+                         "subgroup of the source group (groups=\"project\" takes any two groups)");
+    if (et->spin_flip != 0 && es->spin_flip == 0)
+        return set_error("cross-sector: the target basis has spin_flip and the source basis has not: the target group is no subgroup "
+                         "of the source group (groups=\"project\" takes any two groups)");
+    /* every target generator h as an element of the source group: chi1(h) is that element's character */
+    int *at = (int *)malloc(sizeof(int) * (size_t)(et->n_generators > 0 ? et->n_generators : 1));
+    for (int g = 0; g < et->n_generators; ++g) {
+        at[g] = group_element_of(es, et->gen_perms + (size_t)g * L, L);
+        if (at[g] < 0) {
+            free(at);
+            return set_error("cross-sector: generator %d of the target basis is not an element of the source group (%d elements): the "
+                             "target group is no subgroup of the source group (groups=\"project\" takes any two groups)", g, es->order);
+        }
+    }
+    if (et->n_generators == 0 && target->spin_inversion == 0) { free(at); return 0; } /* no target group: always a subgroup, nothing to check */
+    int const fermi = es->fermi || et->fermi;
+    raw_term *t = NULL, *tg = NULL;
+    canon_term *c = NULL, *both = NULL;
+    int const n = operator_raw_terms(op, &t);
+    int64_t nc = 0;
+    int rc = 0;
+    if (fermi) {
+        for (int k = 0; k < n && rc == 0; ++k)
+            if (t[k].x & ~t[k].m)
+                rc = set_error("ls_amd_operator_maps_subgroup_sector: a term flips modes outside its projector mask (x = 0x%llx is not "
+                               "inside m = 0x%llx): not a product of creation and annihilation operators",
+                               (unsigned long long)t[k].x, (unsigned long long)t[k].m);
+        if (rc == 0 && (nc = signed_expand(t, n, &c)) < 0) rc = not_fermionic(&t[-1 - nc]);
+        tg = (raw_term *)malloc(sizeof(raw_term) * (size_t)(n > 0 ? n : 1));
+    } else if ((nc = canon_expand(op, &c)) < 0)
+        rc = set_error("ls_amd_operator_maps_subgroup_sector: a term's support exceeds its projector mask by more than %d sites", CANON_MAX_FREE);
+    if (rc == 0) {
+        nc = canon_merge(c, nc);
+        double vmax = 0.0;
+        for (int64_t i = 0; i < nc; ++i) { double const a = fabs(c[i].re) > fabs(c[i].im) ? fabs(c[i].re) : fabs(c[i].im); if (a > vmax) vmax = a; }
+        double const tol = 1e-12 * vmax;
+        for (int g = 0; g < et->n_generators && rc == 0; ++g) {
+            int const *p = et->gen_perms + (size_t)g * L;
+            int const ord = perm_order(p, L);
+            /* f = chi2(h) conj(chi1(h)): chi2 from the target's sector, chi1 from the source's element */
+            double const phi = -2.0 * M_PI * (double)et->gen_sectors[g] / (double)ord;
+            double const c1r = es->elems[at[g]].ch_re, c1i = es->elems[at[g]].ch_im;
+            double const f_re = cos(phi) * c1r + sin(phi) * c1i, f_im = sin(phi) * c1r - cos(phi) * c1i;
+            double defect = 0.0;
+            if (fermi) { if (signed_defect(t, n, c, nc, p, L, f_re, f_im, tg, &both, &defect) != 0) { rc = -1; break; } }
+            else defect = canon_defect(c, nc, p, L, f_re, f_im);
+            if (defect > tol)
+                rc = set_error("the operator does not map the source sector into the target sector: under generator %d of the target "
+                               "(sector %d of order %d there; element %d of the source group, character %.6g%+.6gi) it must pick up the "
+                               "factor %.6g%+.6gi, and misses that by %.3g", g, et->gen_sectors[g], ord, at[g], c1r, c1i, f_re, f_im, defect);
+        }
+        if (rc == 0 && target->spin_inversion != 0) {
+            double const f = (double)(src->spin_inversion * target->spin_inversion);
+            double const defect = canon_defect(c, nc, NULL, L, f, 0.0);
+            if (defect > tol)
+                rc = set_error("the operator does not map the source sector into the target sector: under the spin inversion (character %d -> "
+                               "%d) it must pick up the factor %d, and misses that by %.3g", src->spin_inversion, target->spin_inversion, (int)f, defect);
+        }
+    }
+    free(at); free(t); free(tg); free(c); free(both);
     return rc;
 }
 
@@ -5536,7 +5637,19 @@ struct ls_amd_cross {
     uint64_t const *d_src_reps, *d_dst_reps; /* borrowed */
     int64_t n_src, n_dst, nnz;
     int *d_err;               /* owned; d_err + 2: the packet counter of the counting pass (8 bytes) */
+    int mode;                 /* LS_AMD_CROSS_SAME | _RESTRICT (both: k_cross_pull) | _PROJECT (k_cross_project, which sums over dst's elements) */
+    lsk_basis dst;            /* device tables owned by the target basis */
 };
+
+/* one apply, or the counting pass (d_count != NULL), by the kernel of the plan's mode */
+static int cross_launch(ls_amd_cross *cx, void const *d_x, void *d_y, unsigned long long *d_count, void *stream) {
+    lsk_gtab const gt = cx->gtab ? cx->gtab->tab : no_gtab();
+    if (cx->mode == LS_AMD_CROSS_PROJECT)
+        return lsk_cross_project(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, gt, cx->dst, cx->cplx, cx->n_dst,
+                                 cx->d_dst_reps, cx->d_norms, d_x, d_y, cx->tiny, d_count, cx->d_err, stream);
+    return lsk_cross_pull(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, gt, cx->cplx, cx->n_dst, cx->d_dst_reps,
+                          cx->d_norms, d_x, d_y, cx->tiny, d_count, cx->d_err, stream);
+}
 
 void ls_amd_cross_destroy(ls_amd_cross *cx) {
     if (!cx) return;
@@ -5619,8 +5732,8 @@ static int sector_lookup(char const *who, ls_hs_basis const *basis, lsk_basis co
 
 static int cross_setup(ls_amd_cross *cx, ls_hs_operator const *op, ls_hs_basis const *target, void *stream) {
     ls_hs_basis const *src = op->basis;
-    lsk_basis dst;
-    if (basis_device(src, &cx->src) != 0 || basis_device(target, &dst) != 0) return -1;
+    if (basis_device(src, &cx->src) != 0 || basis_device(target, &cx->dst) != 0) return -1;
+    lsk_basis const dst = cx->dst;
     /* the adjoint's device groups: the diagonal terms are the group with flip mask 0 (row i of the target is not column i of the
      * source, so they take the projected path like every other group) */
     struct ls_amd_operator_ext const *ae = OEXT(cx->adj);
@@ -5664,8 +5777,7 @@ static int cross_setup(ls_amd_cross *cx, ls_hs_operator const *op, ls_hs_basis c
     unsigned long long count = 0;
     if (cx->n_groups > 0 && cx->n_dst > 0 && cx->n_src > 0) {
         int zero = 0;
-        DEV(lsk_cross_pull(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, cx->gtab ? cx->gtab->tab : no_gtab(), cx->cplx,
-                           cx->n_dst, cx->d_dst_reps, cx->d_norms, NULL, NULL, cx->tiny, (unsigned long long *)(cx->d_err + 2), cx->d_err, stream));
+        DEV(cross_launch(cx, NULL, NULL, (unsigned long long *)(cx->d_err + 2), stream));
         DEV(lsk_sync(stream));
         DEV(lsk_d2h(&count, cx->d_err + 2, sizeof(count)));
         DEV(lsk_h2d(cx->d_err, &zero, sizeof(int)));
@@ -5674,29 +5786,49 @@ static int cross_setup(ls_amd_cross *cx, ls_hs_operator const *op, ls_hs_basis c
     return 0;
 }
 
-int ls_amd_cross_create(ls_amd_cross **out, ls_hs_operator const *op, ls_hs_basis const *target, ls_amd_dtype dtype,
+/* the body of both constructors (who: the name in the messages).  mode decides the rule that admits the pair of bases -- SAME: the
+ * same generators, the operator covariant under them; RESTRICT: the target group inside the source group, covariant under the
+ * target's generators; PROJECT: no rule, the kernel projects -- and, for PROJECT, the kernel. */
+static int cross_create(char const *who, ls_amd_cross **out, ls_hs_operator const *op, ls_hs_basis const *target, ls_amd_dtype dtype, int mode,
                         uint64_t const *d_src_reps, int64_t n_src, uint64_t const *d_dst_reps, int64_t n_dst, void *stream) {
     if (out) *out = NULL;
-    if (!out || !op || !target) return set_error("ls_amd_cross_create: NULL %s", !out ? "handle" : (!op ? "operator" : "target basis"));
+    if (!out || !op || !target) return set_error("%s: NULL %s", who, !out ? "handle" : (!op ? "operator" : "target basis"));
     if (n_src < 0 || n_dst < 0 || (n_src > 0 && !d_src_reps) || (n_dst > 0 && !d_dst_reps))
-        return set_error("ls_amd_cross_create: NULL representatives or a negative count");
-    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("ls_amd_cross_create: unknown dtype %d", (int)dtype);
-    if (ls_amd_operator_maps_sector_signed(op, target) != 0) return -1; /* (the plain rule where no basis has permutation signs) */
+        return set_error("%s: NULL representatives or a negative count", who);
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
+    if (mode == LS_AMD_CROSS_SAME) {
+        if (ls_amd_operator_maps_sector_signed(op, target) != 0) return -1; /* (the plain rule where no basis has permutation signs) */
+    } else if (mode == LS_AMD_CROSS_RESTRICT) {
+        if (ls_amd_operator_maps_subgroup_sector(op, target) != 0) return -1;
+    } else if (mode == LS_AMD_CROSS_PROJECT) {
+        if (!reg_get(op)) return set_error("%s: unknown operator (ls_amd_adopt_operator first)", who);
+        if (cross_groups_preconditions(op->basis, target) != 0) return -1;
+    } else return set_error("%s: unknown mode %d (LS_AMD_CROSS_SAME, LS_AMD_CROSS_RESTRICT or LS_AMD_CROSS_PROJECT)", who, mode);
     ls_hs_operator *adj = ls_amd_operator_adjoint(op);
     if (!adj) return -1;
     if (dtype == LS_AMD_F64 && !(OEXT(adj)->is_real && cross_every_char_pm1(op->basis) && cross_every_char_pm1(target))) {
         ls_hs_destroy_operator(adj);
-        return set_error("ls_amd_cross_create: f64 needs a real operator and +-1 characters on both bases (complex characters or "
-                         "coefficients: use c128)");
+        return set_error("%s: f64 needs a real operator and +-1 characters on both bases (complex characters or "
+                         "coefficients: use c128)", who);
     }
     ls_amd_cross *cx = (ls_amd_cross *)calloc(1, sizeof(*cx));
     cx->adj = adj;
+    cx->mode = mode;
     cx->cplx = dtype == LS_AMD_C128;
     cx->d_src_reps = d_src_reps; cx->n_src = n_src;
     cx->d_dst_reps = d_dst_reps; cx->n_dst = n_dst;
     if (cross_setup(cx, op, target, stream) != 0) { ls_amd_cross_destroy(cx); return -1; }
     *out = cx;
     return 0;
+}
+
+int ls_amd_cross_create(ls_amd_cross **out, ls_hs_operator const *op, ls_hs_basis const *target, ls_amd_dtype dtype,
+                        uint64_t const *d_src_reps, int64_t n_src, uint64_t const *d_dst_reps, int64_t n_dst, void *stream) {
+    return cross_create("ls_amd_cross_create", out, op, target, dtype, LS_AMD_CROSS_SAME, d_src_reps, n_src, d_dst_reps, n_dst, stream);
+}
+int ls_amd_cross_create_groups(ls_amd_cross **out, ls_hs_operator const *op, ls_hs_basis const *target, ls_amd_dtype dtype, int mode,
+                               uint64_t const *d_src_reps, int64_t n_src, uint64_t const *d_dst_reps, int64_t n_dst, void *stream) {
+    return cross_create("ls_amd_cross_create_groups", out, op, target, dtype, mode, d_src_reps, n_src, d_dst_reps, n_dst, stream);
 }
 
 int ls_amd_cross_apply(ls_amd_cross *cx, void const *d_x, void *d_y, void *stream) {
@@ -5706,8 +5838,7 @@ int ls_amd_cross_apply(ls_amd_cross *cx, void const *d_x, void *d_y, void *strea
         DEV(lsk_memset_async(d_y, 0, (size_t)cx->n_dst * (cx->cplx ? 16 : 8), stream));
         return 0;
     }
-    DEV(lsk_cross_pull(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, cx->gtab ? cx->gtab->tab : no_gtab(), cx->cplx,
-                       cx->n_dst, cx->d_dst_reps, cx->d_norms, d_x, d_y, cx->tiny, NULL, cx->d_err, stream));
+    DEV(cross_launch(cx, d_x, d_y, NULL, stream));
     return 0;
 }
 
@@ -5726,6 +5857,7 @@ int ls_amd_cross_check(ls_amd_cross *cx, void *stream) {
 
 char const *ls_amd_cross_kernel_name(ls_amd_cross const *cx) {
     if (!cx) { set_error("ls_amd_cross_kernel_name: NULL plan"); return NULL; }
+    if (cx->mode == LS_AMD_CROSS_PROJECT) return cx->src.fermi || cx->dst.fermi ? lsk_cross_project_fermi_kernel_name() : lsk_cross_project_kernel_name();
     return cx->src.fermi ? lsk_cross_fermi_kernel_name() : lsk_cross_kernel_name();
 }
 int64_t ls_amd_cross_nnz(ls_amd_cross const *cx) {
@@ -5799,6 +5931,9 @@ static int cross_csr_run(ls_amd_cross *cx, ls_amd_csr *out, void **tmp, void *st
 int ls_amd_cross_csr(ls_amd_cross *cx, int64_t max_bytes, ls_amd_csr *out, void *stream) {
     if (out) memset(out, 0, sizeof(*out));
     if (!cx || !out) return set_error("ls_amd_cross_csr: NULL %s", !cx ? "plan" : "output");
+    if (cx->mode == LS_AMD_CROSS_PROJECT)
+        return set_error("ls_amd_cross_csr: a projecting plan (LS_AMD_CROSS_PROJECT, groups=\"project\") has no CSR export: the emitting "
+                         "mode numbers a row's packets per flip group, and this plan sums them over the target group's elements as well");
     int64_t const need = ls_amd_cross_csr_bytes(cx);
     if (need > max_bytes)
         return set_error("ls_amd_cross_csr: the export needs up to %lld bytes of device memory (%lld rows, %lld packets), max_bytes is %lld",

@@ -585,6 +585,19 @@ char const *lsk_cross_fermi_kernel_name(void);
 int lsk_cross_fermi_pull(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
                          lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, void const *x, void *y,
                          double tiny, unsigned long long *d_count, int *d_err, void *stream);
+/* the projecting form (k_cross_project.hip, k_cross_project: DESIGN.md section 6b, groups = "project"): the sum over the elements of
+ * the target group `dst` (chi2(g), the orbit sign of a projected fermionic target, the flipped images of a spin target with the
+ * inversion) outside the stages of k_cross_pull, so that y = B2+ A B1 x for any operator and any two groups.  The other arguments
+ * are those of lsk_cross_pull; f64 needs +-1 characters on dst as well.  lsk_cross_project hands a pair with a projected fermionic
+ * basis on either side to lsk_cross_project_fermi (k_cross_project_fermi.hip, k_cross_project_fermi). */
+char const *lsk_cross_project_kernel_name(void);
+int lsk_cross_project(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
+                      lsk_gtab gt, lsk_basis dst, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms,
+                      void const *x, void *y, double tiny, unsigned long long *d_count, int *d_err, void *stream);
+char const *lsk_cross_project_fermi_kernel_name(void);
+int lsk_cross_project_fermi(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
+                            lsk_gtab gt, lsk_basis dst, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms,
+                            void const *x, void *y, double tiny, unsigned long long *d_count, int *d_err, void *stream);
 
 /* the matrix of a cross-sector plan in CSR form (k_csr.hip).  lsk_cross_emit runs stages A, B1, B2 of
  * k_cross_pull (the arguments of lsk_cross_pull; either family) and, instead of gathering from x, hands every packet that reached a

@@ -266,7 +266,7 @@ def _target_basis(target):
     raise ValueError("target: a `basis:` section (dict), a whole config (dict or YAML path) or an api.Basis")
 
 
-def _spectral_function_cross(config, operator, target, state, num_moments, energies, bounds, dtype, eps):
+def _spectral_function_cross(config, operator, target, state, num_moments, energies, bounds, dtype, eps, groups="same"):
     """spectral_function for an operator that maps the config's sector into another one: psi lives in the config's own (source)
     sector, v0 = A psi goes through an api.CrossSectorPlan, and the config's Hamiltonian -- re-compiled on the target basis from
     its term tables -- supplies bounds and moments there."""
@@ -287,7 +287,10 @@ def _spectral_function_cross(config, operator, target, state, num_moments, energ
         raise ValueError("operator: an api.Operator (on the source basis) or the index of one of the config's observables")
     dtype = dtype or torch.float64
     tbasis = _target_basis(target)
-    A.mapsSector(tbasis, explain=True, signs=True)
+    if groups not in api.CrossSectorPlan.GROUPS:
+        raise ValueError(f"groups = {groups!r} is none of 'same', 'restrict', 'project'")
+    if groups != "project":  # (a projecting plan asks nothing of the operator)
+        A.mapsSector(tbasis, explain=True, signs=True, subgroup=groups == "restrict")
     h_t = api.Operator.fromSpec(tbasis, _config.OperatorSpec(_terms_of(h)))
     if not h_t.isHermitian:
         raise ValueError("kpm: the Hamiltonian is not Hermitian (Chebyshev moments need a real spectrum)")
@@ -303,7 +306,7 @@ def _spectral_function_cross(config, operator, target, state, num_moments, energ
         bounds = spectral_bounds(op)
     bounds = (float(bounds[0]), float(bounds[1]))
     v0 = torch.zeros(op.n_local, dtype=dtype, device=state.device)
-    cross = api.CrossSectorPlan(A, reps[0], tbasis, treps[0], dtype)
+    cross = api.CrossSectorPlan(A, reps[0], tbasis, treps[0], dtype, groups=groups)
     cross.apply(state, v0)
     cross.destroy()
     before = op.matvecs
@@ -323,7 +326,7 @@ def _spectral_function_cross(config, operator, target, state, num_moments, energ
 
 
 def spectral_function(config, operator, state=None, num_moments: int = 256, energies=None, bounds=None, dtype=None,
-                      eps: float = 1e-10, target=None):
+                      eps: float = 1e-10, target=None, groups: str = "same"):
     """S_A(w) = <psi|A^+ delta(w - H) A|psi> on the absolute energy scale of H.  operator: an api.Operator on the basis of the
     config, or the index of one of the config's `observables`; it must map the basis into itself.  state: a device vector in the
     order of the representatives; None: the ground state (thick-restart Lanczos to `eps`).  -> (energies, S, KpmResult).
@@ -334,11 +337,14 @@ def spectral_function(config, operator, state=None, num_moments: int = 256, ener
     `hamiltonian:` is re-compiled on the target basis, where the bounds and the moments are computed; KpmResult.target_state is
     v0.  Sectors with complex characters need dtype=torch.complex128.  Projected fermionic bases are sectors like any other here:
     c+_k / c_k from an N-particle ground state of momentum k0 into the N +- 1 sector of momentum k0 +- k is the photoemission
-    spectrum A(k, w), n_q and S^z_q give N(q, w) and S^z(q, w)."""
+    spectrum A(k, w), n_q and S^z_q give N(q, w) and S^z(q, w).
+    groups: passed to api.CrossSectorPlan -- "same" (the two bases have the same generators), "restrict" (the target group is a
+    subgroup of the config's: the ground state of the sector with every symmetry, S^z_q into translations only) or "project" (any
+    operator, e.g. the local sigma^z_0: v0 is the component of A psi in the target sector)."""
     import torch
 
     if target is not None:
-        return _spectral_function_cross(config, operator, target, state, num_moments, energies, bounds, dtype, eps)
+        return _spectral_function_cross(config, operator, target, state, num_moments, energies, bounds, dtype, eps, groups)
 
     from . import api
     from .diagonalize import LocalOperator, lanczos_smallest

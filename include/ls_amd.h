@@ -517,13 +517,43 @@ int ls_amd_operator_maps_sector_signed(ls_hs_operator const *op, ls_hs_basis con
  * searched index.  LS_AMD_F64 needs a real operator and +-1 characters on both bases; anything else must be LS_AMD_C128. */
 int ls_amd_cross_create(ls_amd_cross **out, ls_hs_operator const *op_on_source, ls_hs_basis const *target_basis, ls_amd_dtype dtype,
                         uint64_t const *d_src_reps, int64_t n_src, uint64_t const *d_dst_reps, int64_t n_dst, void *stream);
+/* Bases with DIFFERENT symmetry groups.  ls_amd_cross_create refuses them; here they are opt-in by `mode`:
+ *   LS_AMD_CROSS_SAME      exactly ls_amd_cross_create (its rule, its refusals, its kernel).
+ *   LS_AMD_CROSS_RESTRICT  the target group G2 is a SUBGROUP of the source group G1 and A is covariant under G2: A psi then lies in
+ *                          the target sector already and <r'|_2 A|psi> = (A psi^)(r') / n2(r'), which is what k_cross_pull evaluates
+ *                          from the source's orbits and the target's norms -- host work only, the existing kernels, the CSR export
+ *                          unchanged (its matrix is <r'|_2 A|r>_1).  Admitted by ls_amd_operator_maps_subgroup_sector.  A target
+ *                          without symmetries is always a subgroup: the result is A B1 x on the plain basis.  With the same
+ *                          generators on both sides the plan and its results are those of LS_AMD_CROSS_SAME, byte for byte.
+ *   LS_AMD_CROSS_PROJECT   any two bases of one particle type and number_sites, ANY operator, no covariance check:
+ *                              y[r'] = (|G2| n2(r'))^-1 sum_{g in G2} chi2(g) [sign(g, r')] (A B1 x)(g r')
+ *                          (a spin target with the inversion adds the images g r' ^ mask with chi2(g) inv) -- the component of
+ *                          A B1 x in the target sector, B2+ A B1 x, in the conventions and the normalisation of ls_amd_project; no
+ *                          full-basis vector exists at any time.  With A = 1 this moves a state between the sectors of two groups.
+ *                          The kernel is k_cross_project (k_cross_project_fermi when either basis is a projected fermionic one;
+ *                          csrc/k_cross_project_t.hpp): the loop over the target's elements outside the stages of k_cross_pull, so
+ *                          the cost is |G2| (2 |G2| with the inversion) times that of a restricted plan.  ls_amd_cross_nnz counts
+ *                          the packets gathered per apply, over all elements; ls_amd_cross_csr refuses such a plan by name.
+ * LS_AMD_F64 needs a real operator and +-1 characters on both bases in every mode.  One partition; projected fermionic sources up
+ * to 60 modes.  Everything else is as for ls_amd_cross_create. */
+enum { LS_AMD_CROSS_SAME = 0, LS_AMD_CROSS_RESTRICT = 1, LS_AMD_CROSS_PROJECT = 2 };
+int ls_amd_cross_create_groups(ls_amd_cross **out, ls_hs_operator const *op_on_source, ls_hs_basis const *target_basis, ls_amd_dtype dtype,
+                               int mode, uint64_t const *d_src_reps, int64_t n_src, uint64_t const *d_dst_reps, int64_t n_dst, void *stream);
+/* The rule of LS_AMD_CROSS_RESTRICT, exact and host only.  0 when (1) both bases have one particle type and number_sites, (2) every
+ * generator of the target is an ELEMENT of the source group -- looked up in the closure of the source's generators (for spinful
+ * bases: of the lifted permutations), which also yields chi1(h) -- (3) a spin inversion / spin_flip of the target is one of the
+ * source (the source may have one the target lacks), and (4) U_h A U_h^-1 = chi2(h) conj(chi1(h)) A for every generator h of the
+ * TARGET and for its inversion: the plain rule of ls_amd_operator_maps_sector, or the signed rule of
+ * ls_amd_operator_maps_sector_signed when either basis is a projected fermionic one.  -1 otherwise; the message names the target's
+ * generator ("generator g") or the inversion, and points to LS_AMD_CROSS_PROJECT when the target group is no subgroup. */
+int ls_amd_operator_maps_subgroup_sector(ls_hs_operator const *op, ls_hs_basis const *target_basis);
 /* y <- A x (d_x: n_src, d_y: n_dst elements of the plan's dtype); y is ASSIGNED.  Asynchronous on `stream`. */
 int ls_amd_cross_apply(ls_amd_cross *plan, void const *d_x, void *d_y, void *stream);
 /* synchronises `stream` and reports the device error flag: -1 ("... not in the source basis") when an image of A+ with non-zero
  * source norm was not found among the source's representatives -- A leaves the target's weight sector, say; y is then not A x.
  * The run-time counterpart of ls_amd_plan_check's "invalid index". */
 int ls_amd_cross_check(ls_amd_cross *plan, void *stream);
-char const *ls_amd_cross_kernel_name(ls_amd_cross const *plan); /* "k_cross_pull"; "k_cross_pull_fermi" for projected fermionic bases */
+char const *ls_amd_cross_kernel_name(ls_amd_cross const *plan); /* "k_cross_pull"; "k_cross_pull_fermi" for projected fermionic bases; "k_cross_project[_fermi]" for LS_AMD_CROSS_PROJECT */
 /* the (target row, flip mask) pairs that contribute: a coefficient of A+ above the rounding residue of cancelling terms
  * (1e-13 sum |v|) whose image has non-zero norm in the source sector */
 int64_t ls_amd_cross_nnz(ls_amd_cross const *plan);
