@@ -879,6 +879,34 @@ class CrossSectorPlan:
         if check:
             self.check()
 
+    def apply_block(self, x, y, check: bool = True):
+        """Y[:, k] <- A X[:, k] for the K columns of the (n_src, K) and (n_dst, K) device tensors x and y (ls_amd_cross_apply_block):
+        any strides -- (K, 1) interleaved is the fast layout, a transposed (K, n) tensor the column-major one -- and the plan's
+        dtype; 1 <= K <= 64; y is assigned; x and y must not overlap.  Stages A and B1 and the look-up of the images run once per
+        chunk of 8 columns instead of once per column; block_kernel(K) names the path."""
+        torch = _torch()
+        for name, t in (("x", x), ("y", y)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise LsAmdError(f"apply_block: {name} must be a 2-D (n, K) tensor")
+            if t.dtype != self.dtype:
+                raise LsAmdError(f"apply_block: {name} is {t.dtype}, the plan computes in {self.dtype}")
+            if t.device.type != "cuda":
+                raise LsAmdError(f"apply_block: {name} must be a device tensor")
+        if x.shape[0] != self.n_src or y.shape[0] != self.n_dst or x.shape[1] != y.shape[1]:
+            raise LsAmdError(f"apply_block: x {tuple(x.shape)} must be ({self.n_src}, K) and y {tuple(y.shape)} ({self.n_dst}, K)")
+        K = int(x.shape[1])
+        _lib.check(_lib.load().ls_amd_cross_apply_block(self.h, K, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
+                                                        C.c_void_p(y.data_ptr()), y.stride(0), y.stride(1), _stream_ptr()))
+        if check:
+            self.check()
+
+    def block_kernel(self, K: int) -> str:
+        """path a block of K columns takes on this plan: "k_cross_pull_blk", "k_cross_pull_blk_fermi" or "columns" (groups="project")"""
+        name = _lib.load().ls_amd_cross_block_kernel_name(self.h, int(K))
+        if name is None:
+            _lib.check(-1)
+        return name.decode()
+
     def check(self):
         _lib.check(_lib.load().ls_amd_cross_check(self.h, _stream_ptr()))
 

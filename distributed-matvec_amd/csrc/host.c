@@ -5639,6 +5639,7 @@ struct ls_amd_cross {
     int *d_err;               /* owned; d_err + 2: the packet counter of the counting pass (8 bytes) */
     int mode;                 /* LS_AMD_CROSS_SAME | _RESTRICT (both: k_cross_pull) | _PROJECT (k_cross_project, which sums over dst's elements) */
     lsk_basis dst;            /* device tables owned by the target basis */
+    void *d_blk_cols;         /* owned: two contiguous scratch columns (source, target) of the column loop of ls_amd_cross_apply_block */
 };
 
 /* one apply, or the counting pass (d_count != NULL), by the kernel of the plan's mode */
@@ -5658,6 +5659,7 @@ void ls_amd_cross_destroy(ls_amd_cross *cx) {
     if (cx->d_table) lsk_free(cx->d_table);
     if (cx->d_norms) lsk_free(cx->d_norms);
     if (cx->d_err) lsk_free(cx->d_err);
+    if (cx->d_blk_cols) lsk_free(cx->d_blk_cols);
     if (cx->gtab) ls_amd_internal_gtab_release(cx->gtab);
     if (cx->adj) ls_hs_destroy_operator(cx->adj);
     free(cx);
@@ -5839,6 +5841,65 @@ int ls_amd_cross_apply(ls_amd_cross *cx, void const *d_x, void *d_y, void *strea
         return 0;
     }
     DEV(cross_launch(cx, d_x, d_y, NULL, stream));
+    return 0;
+}
+
+/* ---- blocks of vectors (include/ls_amd.h: ls_amd_cross_apply_block; csrc/k_cross_blk.hip) ---- */
+/* SAME and RESTRICT plans have the block kernel; a projecting plan (k_cross_project has no block form) takes the column loop */
+static int cross_block_columns(ls_amd_cross const *cx) { return cx->mode == LS_AMD_CROSS_PROJECT; }
+
+char const *ls_amd_cross_block_kernel_name(ls_amd_cross const *cx, int K) {
+    if (!cx) { set_error("ls_amd_cross_block_kernel_name: NULL plan"); return NULL; }
+    if (K < 1 || K > 64) { set_error("ls_amd_cross_block_kernel_name: K = %d is outside [1, 64]", K); return NULL; }
+    if (cross_block_columns(cx)) return "columns";
+    return cx->src.fermi ? lsk_cross_blk_fermi_kernel_name() : lsk_cross_blk_kernel_name();
+}
+
+int ls_amd_cross_apply_block(ls_amd_cross *cx, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col,
+                             void *stream) {
+    char const *const who = "ls_amd_cross_apply_block";
+    if (!cx) return set_error("%s: NULL plan", who);
+    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
+    int64_t const ns = cx->n_src, nd = cx->n_dst;
+    if (nd == 0) return 0;
+    if (!d_y || (!d_x && ns > 0)) return set_error("%s: NULL %s", who, !d_y ? "Y" : "X");
+    if (K == 1) { x_col = 0; y_col = 0; }
+    if (axpby_strides(who, ns, K, x_row, x_col, "X") != 0 || axpby_strides(who, nd, K, y_row, y_col, "Y") != 0) return -1;
+    size_t const w = cx->cplx ? 16 : 8;
+    if (ns > 0) {
+        uintptr_t const x0 = (uintptr_t)d_x, x1 = x0 + w * (size_t)((ns - 1) * x_row + (int64_t)(K - 1) * x_col + 1);
+        uintptr_t const y0 = (uintptr_t)d_y, y1 = y0 + w * (size_t)((nd - 1) * y_row + (int64_t)(K - 1) * y_col + 1);
+        if (x0 < y1 && y0 < x1) return set_error("%s: X and Y overlap", who);
+    }
+    char *const y = (char *)d_y;
+    if (cx->n_groups == 0 || ns == 0) { /* A = 0, or nothing to read: Y = 0 */
+        if (y_col == 1 && y_row == K) { DEV(lsk_memset_async(y, 0, w * (size_t)nd * (size_t)K, stream)); return 0; }
+        if (!cx->d_blk_cols) DEV(lsk_malloc(&cx->d_blk_cols, w * (size_t)(ns + nd)));
+        char *const zero = (char *)cx->d_blk_cols + w * (size_t)ns; /* (the target scratch column, cleared, to copy from) */
+        DEV(lsk_memset_async(zero, 0, w * (size_t)nd, stream));
+        for (int k = 0; k < K; ++k) DEV(lsk_copy_strided(nd, (int)w, zero, 1, y + (size_t)k * (size_t)y_col * w, y_row, stream));
+        return 0;
+    }
+    if (!cross_block_columns(cx)) {
+        lsk_gtab const gt = cx->gtab ? cx->gtab->tab : no_gtab();
+        DEV(lsk_cross_pull_blk(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, gt, cx->cplx, nd, cx->d_dst_reps,
+                               cx->d_norms, K, d_x, x_row, x_col, d_y, y_row, y_col, cx->tiny, cx->d_err, stream));
+        return 0;
+    }
+    /* the column loop: ls_amd_cross_apply through contiguous scratch columns that the plan owns */
+    if ((x_row != 1 || y_row != 1) && !cx->d_blk_cols) DEV(lsk_malloc(&cx->d_blk_cols, w * (size_t)(ns + nd)));
+    char *const col_x = (char *)cx->d_blk_cols, *const col_y = col_x ? col_x + w * (size_t)ns : NULL;
+    for (int k = 0; k < K; ++k) {
+        void const *xin = (char const *)d_x + (size_t)k * (size_t)x_col * w;
+        void *const yk = y + (size_t)k * (size_t)y_col * w;
+        void *const yout = y_row == 1 ? yk : (void *)col_y;
+        if (x_row != 1) {
+            DEV(lsk_copy_strided(ns, (int)w, xin, x_row, col_x, 1, stream));
+            xin = col_x;
+        }
+        DEV(cross_launch(cx, xin, yout, NULL, stream));
+        if (y_row != 1) DEV(lsk_copy_strided(nd, (int)w, col_y, 1, yk, y_row, stream));
+    }
     return 0;
 }
 

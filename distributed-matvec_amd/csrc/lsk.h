@@ -585,6 +585,19 @@ char const *lsk_cross_fermi_kernel_name(void);
 int lsk_cross_fermi_pull(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
                          lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, void const *x, void *y,
                          double tiny, unsigned long long *d_count, int *d_err, void *stream);
+/* the block form (k_cross_blk.hip, k_cross_pull_blk): y[r', k] for the K columns (1 <= K <= 64) of the blocks x
+ * (source rows) and y (target rows), element strides (row, column) -- (K, 1) interleaved is the fast layout.  The other arguments
+ * are those of lsk_cross_pull, the stages and the error flag too; y is assigned, one plain store per (row, column).  No counting
+ * pass.  LS_AMD_CROSS_BLOCKS=<k>, read at every launch, caps the row blocks of the grid (a test hook).  lsk_cross_pull_blk hands
+ * src.fermi to lsk_cross_fermi_pull_blk (k_cross_blk_fermi.hip, k_cross_pull_blk_fermi). */
+char const *lsk_cross_blk_kernel_name(void);
+int lsk_cross_pull_blk(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
+                       lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, int K, void const *x,
+                       int64_t x_row, int64_t x_col, void *y, int64_t y_row, int64_t y_col, double tiny, int *d_err, void *stream);
+char const *lsk_cross_blk_fermi_kernel_name(void);
+int lsk_cross_fermi_pull_blk(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
+                             lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, int K, void const *x,
+                             int64_t x_row, int64_t x_col, void *y, int64_t y_row, int64_t y_col, double tiny, int *d_err, void *stream);
 /* the projecting form (k_cross_project.hip, k_cross_project: DESIGN.md section 6b, groups = "project"): the sum over the elements of
  * the target group `dst` (chi2(g), the orbit sign of a projected fermionic target, the flipped images of a spin target with the
  * inversion) outside the stages of k_cross_pull, so that y = B2+ A B1 x for any operator and any two groups.  The other arguments

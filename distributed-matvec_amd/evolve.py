@@ -22,7 +22,8 @@ import numpy as np
 from . import kpm
 from ._lib import LsAmdError
 
-__all__ = ["bessel_series", "propagator_coefficients", "propagate", "evolve", "autocorrelation", "EvolveResult"]
+__all__ = ["bessel_series", "propagator_coefficients", "propagate", "evolve", "autocorrelation", "EvolveResult",
+           "thermal_correlation", "combine_sectors", "ThermalCorrelationResult"]
 
 MAX_COLUMNS = 64
 _BIG = 1e250
@@ -322,3 +323,184 @@ def autocorrelation(moments, bounds, times, eps: float = 1e-12) -> np.ndarray:
             raise ValueError(f"autocorrelation: t = {float(t)!r} needs {len(c)} moments for eps = {eps!r}, {M} were given")
         out[..., j] = pref * (mu[..., :len(c)] @ c)
     return out
+
+
+# ---- finite temperature: C(t) = <A^+(t) A(0)>_beta by dynamical quantum typicality ----
+@dataclass
+class ThermalCorrelationResult:
+    times: np.ndarray         # [T] the output times
+    numerator: np.ndarray     # [T, K] complex128: N_k(t) = <A beta_k(t)|phi_k(t)>, |beta_k> = e^{-(beta/2)(H - E_ref)} R_k, |phi_k> = A|beta_k>
+    partition: np.ndarray     # [K] float64: Z_k = <beta_k|beta_k>
+    correlation: np.ndarray   # [T] complex128: sum_k N_k(t) / sum_k Z_k
+    dimension: int            # D_s, the dimension of the source sector (the weight of this sector in combine_sectors)
+    reference_energy: float   # E_ref of the cooling step
+    bounds: tuple             # (lo, hi) both spectra were rescaled with
+    orders: np.ndarray        # [T] int: the order N of the segment that ends at times[j] (the same in both sectors)
+    kernel: str               # CrossSectorPlan.block_kernel(K)
+    matvec_columns: int       # columns that went through H in the cooling and the propagation, both sectors
+    seconds: float = 0.0      # wall time of the driver
+
+
+def thermal_correlation(config, operator, beta, times, num_vectors: int = 8, seed: int = 0, vectors=None, target=None,
+                        groups: str = "same", bounds=None, reference_energy=None, eps: float = 1e-12):
+    """C(t) = <A^+(t) A(0)>_beta = Tr[e^{-beta H} e^{iHt} A^+ e^{-iHt} A] / Tr e^{-beta H} inside the symmetry sector of the config,
+    by dynamical quantum typicality: the trace is the average over K random vectors R_k cooled to |beta_k> = e^{-(beta/2)(H - E_ref)}
+    R_k (skipped at beta = 0), and with |phi_k> = A|beta_k>
+
+        N_k(t) = <A e^{-iHt} beta_k | e^{-iHt} phi_k>,    Z_k = <beta_k|beta_k>,    C(t) ~ sum_k N_k(t) / sum_k Z_k,
+
+    exactly C(t) of the sector when the R_k are a whole orthonormal basis of it.  config, operator, target and groups mean what they
+    mean for kpm.spectral_function: operator is an api.Operator on the config's basis (or the index of one of its `observables:`);
+    target is the sector A maps INTO (None: the config's own), where the config's `hamiltonian:` is re-compiled; the left vector
+    moves in the source sector, the right one in the target sector, segment by segment as evolve does, and every output time costs
+    one CrossSectorPlan.apply_block and K column dots.  Everything runs in complex128.
+    vectors: an (D_s, K) device block, K <= 64; None: kpm.random_phase_block(D_s, num_vectors, complex128, seed).
+    bounds: ONE (lo, hi) pair that encloses the spectrum in BOTH sectors; None: the union of kpm.spectral_bounds of the two.
+    reference_energy: E_ref, bounds[0] when None -- an argument so that several sectors share one (combine_sectors).
+    eps: the cut of every Chebyshev series, relative to the norm of the vector that comes OUT of it: the cooling step, which
+    shrinks its vector, is cut at eps times the smallest shrink factor of the block (and repeated when that was underestimated).
+    -> ThermalCorrelationResult."""
+    from . import api, config as _config
+
+    t0 = time.perf_counter()
+    # everything that can be refused without the device
+    try:
+        beta = float(beta)
+    except (TypeError, ValueError):
+        raise ValueError(f"beta = {beta!r}: need a finite number >= 0") from None
+    if not (math.isfinite(beta) and beta >= 0.0):
+        raise ValueError(f"beta = {beta!r}: need a finite number >= 0")
+    ts = np.atleast_1d(np.asarray(times, dtype=np.float64))
+    if ts.ndim != 1 or ts.size == 0 or not np.isfinite(ts).all() or (np.diff(ts) < 0.0).any():
+        raise ValueError("times: a non-empty ascending sequence of finite numbers")
+    if not float(eps) > 0.0:
+        raise ValueError(f"eps = {eps!r} must be positive")
+    if bounds is not None:
+        bounds = _check_bounds(bounds)
+    if reference_energy is not None and not math.isfinite(float(reference_energy)):
+        raise ValueError(f"reference_energy = {reference_energy!r} is not finite")
+    if groups not in api.CrossSectorPlan.GROUPS:
+        raise ValueError(f"groups = {groups!r} is none of 'same', 'restrict', 'project'")
+    if vectors is None:
+        if isinstance(num_vectors, bool) or not isinstance(num_vectors, (int, np.integer)) or not 1 <= int(num_vectors) <= MAX_COLUMNS:
+            raise ValueError(f"num_vectors = {num_vectors!r}: 1 <= num_vectors <= {MAX_COLUMNS}")
+    else:
+        if isinstance(vectors, (list, tuple)):
+            raise LsAmdError("thermal_correlation: one-partition blocks only (vectors is one (D_s, K) device tensor)")
+        if not hasattr(vectors, "dim") or vectors.dim() != 2 or not 1 <= int(vectors.shape[1]) <= MAX_COLUMNS:
+            raise LsAmdError(f"thermal_correlation: vectors must be an (D_s, K) block, 1 <= K <= {MAX_COLUMNS}")
+        if vectors.device.type != "cuda":
+            raise LsAmdError("thermal_correlation: vectors must be a device tensor")
+    basis, h, obs = kpm._load(config, observables=True)  # (refuses a Hamiltonian that is not Hermitian)
+    if isinstance(operator, (int, np.integer)) and not isinstance(operator, bool):
+        if obs is None or not 0 <= int(operator) < len(obs):
+            raise ValueError(f"operator = {operator}: the config has {0 if obs is None else len(obs)} observables")
+        A = obs[int(operator)]
+    elif isinstance(operator, api.Operator):
+        A = operator
+    else:
+        raise ValueError("operator: an api.Operator (on the source basis) or the index of one of the config's observables")
+    tbasis = basis if target is None else kpm._target_basis(target)
+    if groups != "project":  # (a projecting plan asks nothing of the operator)
+        A.mapsSector(tbasis, explain=True, signs=True, subgroup=groups == "restrict")
+    h_t = h if target is None else api.Operator.fromSpec(tbasis, _config.OperatorSpec(kpm._terms_of(h)))
+    if not h_t.isHermitian:
+        raise ValueError("thermal_correlation: the Hamiltonian is not Hermitian on the target basis")
+
+    import torch
+
+    from .diagonalize import LocalOperator
+
+    c128 = torch.complex128
+    reps, _ = api.enumerateStates(basis, 1)
+    treps = reps if target is None else api.enumerateStates(tbasis, 1)[0]
+    op_s = LocalOperator(h, reps, c128)
+    op_t = op_s if target is None else LocalOperator(h_t, treps, c128)
+    D_s = int(op_s.n_local)
+    if vectors is None:
+        R = kpm.random_phase_block(D_s, int(num_vectors), c128, seed, device=op_s.device)
+    else:
+        if vectors.shape[0] != D_s:
+            raise LsAmdError(f"thermal_correlation: vectors {tuple(vectors.shape)} must have {D_s} rows (the source sector)")
+        R = vectors.to(c128)
+    K = int(R.shape[1])
+    if bounds is None:
+        b_s = kpm.spectral_bounds(op_s)
+        b_t = b_s if op_t is op_s else kpm.spectral_bounds(op_t)
+        bounds = _check_bounds((min(b_s[0], b_t[0]), max(b_s[1], b_t[1])))
+    e_ref = float(bounds[0]) if reference_energy is None else float(reference_energy)
+    cross = api.CrossSectorPlan(A, reps[0], tbasis, treps[0], c128, groups=groups)
+    try:
+        before = op_s.matvecs + (0 if op_t is op_s else op_t.matvecs)
+        if beta > 0.0:
+            # propagate cuts its series at eps relative to the norm of R_k, and cooling shrinks the vector -- by e^{-(beta/2)(E_0 - lo)}
+            # at least, E_0 the sector's lowest level, lo the lower bound shared with the other sector -- so the cut is made at
+            # eps times the smallest shrink factor s = |beta_k| / |R_k|: eps holds relative to |beta_k>.  s is known only afterwards;
+            # the series falls faster than geometrically beyond order a beta / 2, so three digits in advance cost a few orders,
+            # and the pass is repeated only when s turns out smaller than that.
+            r_norm = torch.linalg.vector_norm(R, dim=0) * math.exp(-(bounds[0] - e_ref) * 0.5 * beta)  # (the exact prefactor is no shrinking)
+            eps_c = 1e-3 * float(eps)
+            for _ in range(3):
+                left = propagate(op_s, R, 0.5 * beta, bounds=bounds, eps=max(eps_c, 1e-300), imaginary=True, reference_energy=e_ref)
+                shrink = float((torch.linalg.vector_norm(left, dim=0) / r_norm).min())
+                if not shrink > 0.0 or eps_c <= float(eps) * shrink:
+                    break
+                eps_c = 0.1 * float(eps) * shrink
+        else:
+            left = R.contiguous().clone()
+        Z = (left.real ** 2 + left.imag ** 2).sum(dim=0).cpu().numpy()
+        right = torch.empty((op_t.n_local, K), dtype=c128, device=left.device)
+        cross.apply_block(left, right)
+        image = torch.empty_like(right)
+        T = len(ts)
+        numerator = np.zeros((T, K), dtype=np.complex128)
+        orders = np.zeros(T, dtype=np.int64)
+        prev = 0.0
+        for j, tj in enumerate(ts):
+            dt = float(tj) - prev
+            if dt != 0.0:
+                info = {}
+                left = propagate(op_s, left, dt, bounds=bounds, eps=eps, _info=info)
+                right = propagate(op_t, right, dt, bounds=bounds, eps=eps)
+                orders[j] = info["order"]
+                prev = float(tj)
+            cross.apply_block(left, image)
+            numerator[j] = (image.conj() * right).sum(dim=0).cpu().numpy()
+        columns = op_s.matvecs + (0 if op_t is op_s else op_t.matvecs) - before
+        kernel = cross.block_kernel(K)
+    finally:
+        cross.destroy()
+    res = ThermalCorrelationResult(ts, numerator, Z, numerator.sum(axis=1) / Z.sum(), D_s, e_ref, bounds, orders, kernel, int(columns))
+    res.seconds = time.perf_counter() - t0
+    return res
+
+
+def combine_sectors(results) -> np.ndarray:
+    """C(t) of the ensemble over several symmetry sectors from their thermal_correlation results (host only):
+
+        C(t) = sum_s (D_s / K_s) sum_k N_{s,k}(t)  /  sum_s (D_s / K_s) sum_k Z_{s,k}
+
+    -- every sector's stochastic trace estimates Tr_s with the weight D_s / K_s.  The results must share their `times` and their
+    `reference_energy` (the Boltzmann weights of two sectors are comparable only on one energy scale): ValueError otherwise.
+    -> complex128 [T]."""
+    results = list(results)
+    if not results:
+        raise ValueError("combine_sectors: no results")
+    first = results[0]
+    num = np.zeros(len(first.times), dtype=np.complex128)
+    den = 0.0
+    for s, r in enumerate(results):
+        if not np.array_equal(np.asarray(r.times), np.asarray(first.times)):
+            raise ValueError(f"combine_sectors: result {s} has other times than result 0")
+        if float(r.reference_energy) != float(first.reference_energy):
+            raise ValueError(f"combine_sectors: result {s} has reference_energy {r.reference_energy!r}, result 0 {first.reference_energy!r} "
+                             "(pass one reference_energy to every thermal_correlation)")
+        N = np.asarray(r.numerator)
+        Zk = np.asarray(r.partition)
+        K = Zk.shape[0]
+        if K < 1 or N.shape != (len(first.times), K) or not int(r.dimension) >= 1:
+            raise ValueError(f"combine_sectors: result {s} is malformed (numerator {N.shape}, partition {Zk.shape}, dimension {r.dimension!r})")
+        w = float(r.dimension) / K
+        num += w * N.sum(axis=1)
+        den += w * float(Zk.sum())
+    return num / den

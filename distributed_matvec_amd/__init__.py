@@ -14,7 +14,8 @@ from .correlations import (CorrelationPlan, FermionCorrelations, SpinCorrelation
 from . import expectation  # noqa: E402  (the module keeps its name here: its driver is expectation.expectation)
 from .expectation import ExpectationPlan, dimer_correlations, expectation_values, pair_correlations  # noqa: F401,E402
 from . import evolve  # noqa: E402  (the module keeps its name here: its driver is evolve.evolve)
-from .evolve import EvolveResult, autocorrelation, bessel_series, propagate, propagator_coefficients  # noqa: F401,E402
+from .evolve import (EvolveResult, ThermalCorrelationResult, autocorrelation, bessel_series, combine_sectors, propagate,  # noqa: F401,E402
+                     propagator_coefficients, thermal_correlation)
 from . import projection  # noqa: E402
 from .projection import SectorProjection, product_state, project  # noqa: F401,E402
 

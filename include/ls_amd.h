@@ -549,6 +549,22 @@ int ls_amd_cross_create_groups(ls_amd_cross **out, ls_hs_operator const *op_on_s
 int ls_amd_operator_maps_subgroup_sector(ls_hs_operator const *op, ls_hs_basis const *target_basis);
 /* y <- A x (d_x: n_src, d_y: n_dst elements of the plan's dtype); y is ASSIGNED.  Asynchronous on `stream`. */
 int ls_amd_cross_apply(ls_amd_cross *plan, void const *d_x, void *d_y, void *stream);
+/* Y[:, k] <- A X[:, k] for the K columns of the blocks X (n_src rows) and Y (n_dst rows) of the plan's dtype, 1 <= K <= 64; Y is
+ * ASSIGNED.  x_row / x_col, y_row / y_col: ELEMENT strides between rows and between columns, as in ls_amd_matvec_block -- any
+ * non-negative pair that puts no two (row, column) on one element; interleaved (K, 1) is the fast layout (one image's columns are
+ * consecutive memory), (1, n) the column-major one.  X and Y must not overlap.  Asynchronous on `stream`.  Plans of mode
+ * LS_AMD_CROSS_SAME and LS_AMD_CROSS_RESTRICT run the block kernel (csrc/k_cross_blk.hip): the term sums, the
+ * projection of every image and its look-up in the source basis are done once per chunk of 8 columns, not once per column.  Plans
+ * of mode LS_AMD_CROSS_PROJECT loop ls_amd_cross_apply over the columns, through contiguous scratch columns that the plan owns where
+ * a row stride is not 1.  A = 0 or an empty source clears Y.  The error flag is that of ls_amd_cross_apply: ls_amd_cross_check
+ * serves both.  -1 with a message: K outside 1...64, NULL X or Y, strides that make elements share storage, overlapping X and Y.
+ * Environment: LS_AMD_CROSS_BLOCKS=<k>, read at every launch, caps the row blocks of the block kernel's grid (a test hook: a
+ * workgroup then walks several tiles). */
+int ls_amd_cross_apply_block(ls_amd_cross *plan, int K, void const *d_x, int64_t x_row, int64_t x_col,
+                             void *d_y, int64_t y_row, int64_t y_col, void *stream);
+/* the path ls_amd_cross_apply_block takes for K columns: "k_cross_pull_blk", "k_cross_pull_blk_fermi" for a projected fermionic
+ * source, "columns" for LS_AMD_CROSS_PROJECT.  NULL with a message: NULL plan, K outside 1...64. */
+char const *ls_amd_cross_block_kernel_name(ls_amd_cross const *plan, int K);
 /* synchronises `stream` and reports the device error flag: -1 ("... not in the source basis") when an image of A+ with non-zero
  * source norm was not found among the source's representatives -- A leaves the target's weight sector, say; y is then not A x.
  * The run-time counterpart of ls_amd_plan_check's "invalid index". */
