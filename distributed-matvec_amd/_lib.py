@@ -209,6 +209,8 @@ def load():
         "ls_amd_test_corr_symmetrize": (C.c_int, [bp, C.c_int, c_f64p, c_f64p]),
         "ls_amd_expect_create": (C.c_int, [C.POINTER(vp), bp, C.POINTER(op), C.c_int, vp, C.c_int64, vp]),
         "ls_amd_expect_values": (C.c_int, [vp, C.c_int, vp, c_f64p, vp]),
+        "ls_amd_expect_values_block": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, c_f64p, vp]),
+        "ls_amd_expect_block_kernel_name": (C.c_char_p, [vp, C.c_int]),
         "ls_amd_expect_num_terms": (C.c_int, [vp]),
         "ls_amd_expect_num_groups": (C.c_int, [vp]),
         "ls_amd_expect_kernel_name": (C.c_char_p, [vp]),

@@ -6864,6 +6864,12 @@ struct ls_amd_expect {
     int *comb_k, *comb_u;
     double *comb_w;                        /* (re, im) */
     double *d_partial, *d_out, *h_out;     /* owned: the partial sums of the blocks of one chunk; R of every term, and its host copy */
+    /* ls_amd_expect_values_block, all owned and allocated at the first call that needs them (grown by later ones): */
+    double *d_blk_partial;                 /* the partial sums of the blocks of one block launch, blk_partial_vals x 16 bytes */
+    double *d_blk_out, *h_blk_out;         /* R of every (term, column), blk_out_vals x 16 bytes, and its host copy */
+    size_t blk_partial_vals, blk_out_vals;
+    void *d_blk_col;                       /* a contiguous scratch column of the column loop */
+    double *h_col;                         /* the values of one column of the column loop */
 };
 
 void ls_amd_expect_destroy(ls_amd_expect *pl) {
@@ -6875,8 +6881,12 @@ void ls_amd_expect_destroy(ls_amd_expect *pl) {
     if (pl->d_terms) lsk_free(pl->d_terms);
     if (pl->d_partial) lsk_free(pl->d_partial);
     if (pl->d_out) lsk_free(pl->d_out);
+    if (pl->d_blk_partial) lsk_free(pl->d_blk_partial);
+    if (pl->d_blk_out) lsk_free(pl->d_blk_out);
+    if (pl->d_blk_col) lsk_free(pl->d_blk_col);
     if (pl->gtab) ls_amd_internal_gtab_release(pl->gtab);
     free(pl->h_groups); free(pl->chunk_first); free(pl->comb_k); free(pl->comb_u); free(pl->comb_w); free(pl->h_out);
+    free(pl->h_blk_out); free(pl->h_col);
     free(pl);
 }
 
@@ -7040,6 +7050,134 @@ int ls_amd_expect_values(ls_amd_expect *pl, ls_amd_dtype dtype, void const *d_ps
         double const wr = pl->comb_w[2 * i], wi = pl->comb_w[2 * i + 1];
         h_out[2 * pl->comb_k[i]] += wr * rr - wi * ri;
         h_out[2 * pl->comb_k[i] + 1] += wr * ri + wi * rr;
+    }
+    return 0;
+}
+
+/* ---- blocks of states (include/ls_amd.h: ls_amd_expect_values_block; csrc/k_expect_blk.hip) ---- */
+/* LS_AMD_EXPECT_BLOCK, read at every call: `columns` loops ls_amd_expect_values over the columns; `kernel` and anything else
+ * (`auto`) take k_expect_blk for every K ("Block expectation values") */
+static int expect_block_columns(void) {
+    char const *e = getenv("LS_AMD_EXPECT_BLOCK");
+    return e && strcmp(e, "columns") == 0;
+}
+
+char const *ls_amd_expect_block_kernel_name(ls_amd_expect const *pl, int K) {
+    if (!pl) { set_error("ls_amd_expect_block_kernel_name: NULL plan"); return NULL; }
+    if (K < 1 || K > 64) { set_error("ls_amd_expect_block_kernel_name: K = %d is outside [1, 64]", K); return NULL; }
+    if (expect_block_columns()) return "columns";
+    return pl->bs.fermi ? lsk_expect_blk_fermi_kernel_name() : lsk_expect_blk_kernel_name();
+}
+
+/* columns of one block launch over a chunk of nt <= LSK_EXPECT_CHUNK terms: all K while nt * K stays within 8 LSK_EXPECT_CHUNK
+ * partial sums per block, else the most whole chunks of 8 columns that do (at least one) */
+static int expect_block_cols(int nt, int K) {
+    if ((int64_t)nt * K <= 8 * (int64_t)LSK_EXPECT_CHUNK) return K;
+    return 8 * LSK_EXPECT_CHUNK / nt / 8 * 8;
+}
+
+static int expect_block_kernel(ls_amd_expect *pl, int cplx, int K, char const *psi, int64_t p_row, int64_t p_col, double *h_out, void *stream) {
+    int const nc = cplx ? 2 : 1;
+    size_t const w = 8 * (size_t)nc;
+    /* the buffers of the block calls: allocated here, at the first call that needs them, and grown by a call with more columns */
+    size_t part = 1;
+    for (int c = 0; c < pl->n_chunks; ++c) {
+        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
+        size_t const nt = (size_t)(pl->h_groups[g1 - 1].end - pl->h_groups[g0].begin);
+        size_t const v = nt * (size_t)expect_block_cols((int)nt, K);
+        if (v > part) part = v;
+    }
+    part *= (size_t)lsk_corr_blocks(pl->n);
+    if (part > pl->blk_partial_vals) {
+        if (pl->d_blk_partial) { lsk_free(pl->d_blk_partial); pl->d_blk_partial = NULL; pl->blk_partial_vals = 0; }
+        void *p = NULL;
+        DEV(lsk_malloc(&p, 16 * part));
+        pl->d_blk_partial = (double *)p; pl->blk_partial_vals = part;
+    }
+    size_t const vals = (size_t)(pl->n_terms > 0 ? pl->n_terms : 1) * (size_t)K;
+    if (vals > pl->blk_out_vals) {
+        if (pl->d_blk_out) { lsk_free(pl->d_blk_out); pl->d_blk_out = NULL; }
+        free(pl->h_blk_out); pl->h_blk_out = NULL; pl->blk_out_vals = 0;
+        void *p = NULL;
+        DEV(lsk_malloc(&p, 16 * vals));
+        pl->d_blk_out = (double *)p;
+        pl->h_blk_out = (double *)malloc(16 * vals);
+        if (!pl->h_blk_out) return set_error("ls_amd_expect_values_block: out of host memory");
+        pl->blk_out_vals = vals;
+    }
+    /* the launches: per chunk of terms, per range of columns; a launch writes R[(u - t0) kl + (c - k0)] of its nt terms and kl
+     * columns at (t0 K + nt k0) of d_blk_out */
+    for (int c = 0; c < pl->n_chunks; ++c) {
+        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
+        int const t0 = pl->h_groups[g0].begin, nt = pl->h_groups[g1 - 1].end - t0;
+        int const cols = expect_block_cols(nt, K);
+        for (int k0 = 0; k0 < K; k0 += cols) {
+            int const kl = K - k0 < cols ? K - k0 : cols;
+            DEV(lsk_expect_blk(pl->bs, pl->six, pl->gtab ? pl->gtab->tab : no_gtab(), pl->cons, g1 - g0, pl->d_groups + g0, pl->d_terms, t0, nt,
+                               cplx, pl->n, pl->d_reps, pl->d_norms, kl, psi + (size_t)k0 * (size_t)p_col * w, p_row, p_col, pl->d_blk_partial,
+                               pl->d_blk_out + ((size_t)t0 * (size_t)K + (size_t)nt * (size_t)k0) * nc, pl->d_err, stream));
+        }
+    }
+    int flag = 0, zero = 0;
+    DEV(lsk_sync(stream));
+    DEV(lsk_d2h(&flag, pl->d_err, sizeof(int)));
+    if (flag) {
+        DEV(lsk_h2d(pl->d_err, &zero, sizeof(int)));
+        return set_error("expectation values: the image of a representative under a term keeps the conserved numbers, has non-zero norm "
+                         "and is not in the basis (the array of representatives does not belong to this basis or is not the whole "
+                         "sector: another Hamming weight, a truncated array)");
+    }
+    if (pl->n_terms > 0) DEV(lsk_d2h(pl->h_blk_out, pl->d_blk_out, w * (size_t)pl->n_terms * (size_t)K));
+    for (int k = 0; k < 2 * pl->n_ops * K; ++k) h_out[k] = 0.0;
+    /* value[k][c] = sum_u w[k][u] R[u][c]: the loop of ls_amd_expect_values per column (comb_u ascends: the chunk follows it) */
+    int ch = 0;
+    for (size_t i = 0; i < pl->n_comb; ++i) {
+        int const u = pl->comb_u[i];
+        while (u >= pl->h_groups[pl->chunk_first[ch + 1] - 1].end) ++ch;
+        int const t0 = pl->h_groups[pl->chunk_first[ch]].begin, nt = pl->h_groups[pl->chunk_first[ch + 1] - 1].end - t0;
+        int const cols = expect_block_cols(nt, K);
+        double const wr = pl->comb_w[2 * i], wi = pl->comb_w[2 * i + 1];
+        double *const o = h_out + 2 * (size_t)pl->comb_k[i] * (size_t)K;
+        for (int col = 0; col < K; ++col) {
+            int const k0 = col / cols * cols, kl = K - k0 < cols ? K - k0 : cols;
+            size_t const at = (size_t)t0 * (size_t)K + (size_t)nt * (size_t)k0 + (size_t)(u - t0) * (size_t)kl + (size_t)(col - k0);
+            double const rr = cplx ? pl->h_blk_out[2 * at] : pl->h_blk_out[at], ri = cplx ? pl->h_blk_out[2 * at + 1] : 0.0;
+            o[2 * col] += wr * rr - wi * ri;
+            o[2 * col + 1] += wr * ri + wi * rr;
+        }
+    }
+    return 0;
+}
+
+int ls_amd_expect_values_block(ls_amd_expect *pl, ls_amd_dtype dtype, int K, void const *d_psi, int64_t row_stride, int64_t col_stride,
+                               double *h_out, void *stream) {
+    char const *who = "ls_amd_expect_values_block";
+    if (!pl || !d_psi) return set_error("%s: NULL %s", who, !pl ? "plan" : "block");
+    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
+    if (dtype == LS_AMD_F64 && !pl->pm1) return set_error("%s: f64 needs +-1 characters (complex characters: use c128)", who);
+    if (!h_out) return set_error("%s: NULL output", who);
+    if (row_stride <= 0 || col_stride <= 0)
+        return set_error("%s: strides (row %lld, column %lld) of the block must be positive", who, (long long)row_stride, (long long)col_stride);
+    if (axpby_strides(who, pl->n, K, row_stride, col_stride, "the block") != 0) return -1;
+    int const cplx = dtype == LS_AMD_C128;
+    size_t const w = cplx ? 16 : 8;
+    char const *const psi = (char const *)d_psi;
+    if (!expect_block_columns()) return expect_block_kernel(pl, cplx, K, psi, row_stride, col_stride, h_out, stream);
+    /* the column loop: ls_amd_expect_values, through a contiguous scratch column that the plan owns where the rows are strided */
+    if (!pl->h_col && !(pl->h_col = (double *)malloc(16 * (size_t)pl->n_ops))) return set_error("%s: out of host memory", who);
+    if (row_stride != 1 && !pl->d_blk_col) DEV(lsk_malloc(&pl->d_blk_col, 16 * (size_t)pl->n));
+    for (int c = 0; c < K; ++c) {
+        void const *col = psi + (size_t)c * (size_t)col_stride * w;
+        if (row_stride != 1) {
+            DEV(lsk_copy_strided(pl->n, (int)w, col, row_stride, pl->d_blk_col, 1, stream));
+            col = pl->d_blk_col;
+        }
+        if (ls_amd_expect_values(pl, dtype, col, pl->h_col, stream) != 0) return -1;
+        for (int k = 0; k < pl->n_ops; ++k) {
+            h_out[2 * ((size_t)k * (size_t)K + (size_t)c)] = pl->h_col[2 * k];
+            h_out[2 * ((size_t)k * (size_t)K + (size_t)c) + 1] = pl->h_col[2 * k + 1];
+        }
     }
     return 0;
 }

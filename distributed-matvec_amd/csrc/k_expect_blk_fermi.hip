@@ -1,0 +1,26 @@
+// k_expect_blk_fermi.hip -- the block expectation-value kernel on projected FERMIONIC bases (spinless; spinful over their 2 L modes):
+// the k_expect_blk template of k_expect_blk_t.hpp with its FERMI switch on, so that stage B1 projects every image with the signed
+// characters chi(g) sign(g, a) of lsk_fermi.hpp, as k_expect_fermi does for one state.  The same 6 kinds as k_expect_blk.hip.
+// DESIGN.md section 6i.
+#include "k_expect_blk_t.hpp"
+
+// the name of the family in plans and reports: k_expect_blk<W, PM1, CPLX, FERMI = true>
+extern "C" char const *lsk_expect_blk_fermi_kernel_name(void) { return "k_expect_blk_fermi"; }
+
+// lsk_expect_blk for bs.fermi (same arguments; reached through it).  The basis is always projected, so always looked up in its static
+// index table: the sign table and the table's key width bound every shift and load of the kernel.
+extern "C" int lsk_expect_blk_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, int n_groups,
+                                    lsk_expect_group const *groups, lsk_expect_term const *terms, int term0, int n_terms, int cplx,
+                                    int64_t n, uint64_t const *reps, double const *norms, int K, void const *psi, int64_t p_row,
+                                    int64_t p_col, double *partial, double *out, int *d_err, void *stream) {
+    if (!bs.fermi || !bs.fsign || bs.spin_inversion != 0 || bs.k4_mode != 0 || bs.proj != LSK_PROJ_FULL) {
+        snprintf(g_err, sizeof(g_err), "%s: not a projected fermionic basis in K4 mode 0", __func__);
+        return -1;
+    }
+    if (n > 0 && n_groups > 0 && n_terms > 0 && (!gt.entries || gt.L != bs.number_sites)) {
+        snprintf(g_err, sizeof(g_err), "%s: a projected fermionic basis is looked up in its static index table", __func__);
+        return -1;
+    }
+    return expect_blk_launch<true>(__func__, bs, six, gt, cons, n_groups, groups, terms, term0, n_terms, cplx, n, reps, norms, K, psi, p_row,
+                                   p_col, partial, out, d_err, stream);
+}

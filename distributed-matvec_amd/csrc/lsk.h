@@ -763,6 +763,19 @@ int lsk_expect(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, i
 int lsk_expect_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, int n_groups, lsk_expect_group const *groups,
                      lsk_expect_term const *terms, int term0, int n_terms, int cplx, int64_t n, uint64_t const *reps, double const *norms,
                      void const *psi, double *partial, double *out, int *d_err, void *stream);
+/* the block form (k_expect_blk.hip, k_expect_blk_fermi.hip): lsk_expect for the K columns, 1 <= K <= 64, of
+ * the (n, K) block psi with element strides (p_row, p_col) -- out[(u K + c)] (1 double for f64, 2 for c128) is out[u] above of
+ * column c.  The packets, their projection and their look-up are shared by a chunk of 8 columns.  n_terms * K <= 8 LSK_EXPECT_CHUNK;
+ * `partial` holds lsk_corr_blocks(n) * n_terms * K values, `out` n_terms * K.  No floating-point atomics. */
+char const *lsk_expect_blk_kernel_name(void);
+char const *lsk_expect_blk_fermi_kernel_name(void);
+int lsk_expect_blk(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, int n_groups, lsk_expect_group const *groups,
+                   lsk_expect_term const *terms, int term0, int n_terms, int cplx, int64_t n, uint64_t const *reps, double const *norms,
+                   int K, void const *psi, int64_t p_row, int64_t p_col, double *partial, double *out, int *d_err, void *stream);
+int lsk_expect_blk_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, int n_groups, lsk_expect_group const *groups,
+                         lsk_expect_term const *terms, int term0, int n_terms, int cplx, int64_t n, uint64_t const *reps,
+                         double const *norms, int K, void const *psi, int64_t p_row, int64_t p_col, double *partial, double *out,
+                         int *d_err, void *stream);
 
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */

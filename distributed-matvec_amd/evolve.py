@@ -23,7 +23,8 @@ from . import kpm
 from ._lib import LsAmdError
 
 __all__ = ["bessel_series", "propagator_coefficients", "propagate", "evolve", "autocorrelation", "EvolveResult",
-           "thermal_correlation", "combine_sectors", "ThermalCorrelationResult"]
+           "thermal_correlation", "combine_sectors", "ThermalCorrelationResult", "thermal_expectation",
+           "combine_sector_expectations", "ThermalExpectationResult"]
 
 MAX_COLUMNS = 64
 _BIG = 1e250
@@ -504,3 +505,226 @@ def combine_sectors(results) -> np.ndarray:
         num += w * N.sum(axis=1)
         den += w * float(Zk.sum())
     return num / den
+
+
+# ---- finite temperature, static: <O>_beta, E(beta), C(beta), S(beta) by canonical typicality ----
+@dataclass
+class ThermalExpectationResult:
+    betas: np.ndarray              # [B] the inverse temperatures
+    numerator: np.ndarray          # [B, n_ops, K] complex128: <beta_k|O|beta_k>, |beta_k> = e^{-(beta/2)(H - E_ref)} R_k
+    partition: np.ndarray          # [B, K] float64: Z_k = <beta_k|beta_k>
+    energy_numerator: np.ndarray   # [B, K] float64: <beta_k|H|beta_k>
+    energy2_numerator: np.ndarray  # [B, K] float64: |H beta_k|^2
+    values: np.ndarray             # [B, n_ops] complex128: sum_k numerator / sum_k partition
+    energy: np.ndarray             # [B] <H>_beta
+    specific_heat: np.ndarray      # [B] beta^2 (<H^2> - <H>^2)
+    log_partition: np.ndarray      # [B] ln Tr e^{-beta H} = ln((D / K) sum_k Z_k) - beta E_ref
+    entropy: np.ndarray            # [B] log_partition + beta energy
+    dimension: int                 # D, the dimension of the sector (its weight in combine_sector_expectations)
+    reference_energy: float        # E_ref of the cooling
+    bounds: tuple                  # (lo, hi) the spectrum was rescaled with
+    orders: np.ndarray             # [B] int: the order N of the cooling segment that ends at betas[j]
+    kernel: str                    # ExpectationPlan.block_kernel(K)
+    matvec_columns: int            # columns that went through H, cooling and energies
+    seconds: float = 0.0           # wall time of the driver
+    expectation_seconds: float = 0.0  # of which inside ExpectationPlan.values_block
+
+
+def _thermal_derived(betas, num, Z, E1, E2, weight, e_ref):
+    """the ensemble quantities from the sums over the columns: num [B, n_ops], Z, E1, E2 [B]; weight = D / K of the trace estimate"""
+    values = num / Z[:, None]
+    energy = E1 / Z
+    heat = betas ** 2 * (E2 / Z - energy ** 2)
+    logz = np.log(weight * Z) - betas * e_ref
+    return values, energy, heat, logz, logz + betas * energy
+
+
+def _cool(op, block, tau, bounds, e_ref, eps):
+    """e^{-tau (H - E_ref)} block with the series cut at eps relative to the vector that comes OUT: the rule of thermal_correlation,
+    for one segment -> (block, order)"""
+    import torch
+
+    r_norm = torch.linalg.vector_norm(block, dim=0) * math.exp(-(bounds[0] - e_ref) * tau)  # (the exact prefactor is no shrinking)
+    eps_c = 1e-3 * float(eps)
+    info = {}
+    for _ in range(3):
+        out = propagate(op, block, tau, bounds=bounds, eps=max(eps_c, 1e-300), imaginary=True, reference_energy=e_ref, _info=info)
+        shrink = float((torch.linalg.vector_norm(out, dim=0) / r_norm).min())
+        if not shrink > 0.0 or eps_c <= float(eps) * shrink:
+            break
+        eps_c = 0.1 * float(eps) * shrink
+    return out, int(info["order"])
+
+
+def thermal_expectation(config, operators, betas, num_vectors: int = 8, seed: int = 0, vectors=None, bounds=None, reference_energy=None,
+                        eps: float = 1e-12, dtype=None):
+    """<O>_beta = Tr[e^{-beta H} O] / Tr e^{-beta H} of every operator, the energy, the specific heat, ln Z and the entropy inside the
+    symmetry sector of the config at every inverse temperature of `betas`, by canonical typicality: the trace is the average over K
+    random vectors R_k cooled to |beta_k> = e^{-(beta/2)(H - E_ref)} R_k,
+
+        <O>_beta ~ sum_k <beta_k|O|beta_k> / sum_k <beta_k|beta_k>,
+
+    exactly the sector's when the R_k are a whole orthonormal basis of it.  The block is cooled ONCE, from each beta to the next, so
+    the grid costs what its largest beta costs; at every beta one MatvecPlan.matvec_block_axpby gives <beta_k|beta_k> and
+    <beta_k|H|beta_k>, a column norm |H beta_k|^2, and ONE ExpectationPlan.values_block the K values of every operator.
+    operators: what ExpectationPlan accepts (Operators, OperatorSpecs, operator sections; the operators need not be invariant under
+    the sector's group), or integer indices into the config's `observables:`.  betas: a non-empty ascending sequence of finite numbers
+    >= 0.  vectors: an (D, K) device block, K <= 64; None: kpm.random_phase_block(D, num_vectors, dtype, seed) -- random signs in
+    float64, random phases in complex128.  dtype None: float64 when the Hamiltonian is real, the characters are +-1 and `vectors` is
+    real, else complex128; torch.float64 where that cannot be honoured is refused.  bounds, reference_energy, eps: as
+    thermal_correlation; the cut of every cooling segment is relative to the vector that comes out of it.
+    -> ThermalExpectationResult."""
+    from . import api, config as _config, expectation as _expectation
+    from .entanglement import _complex_characters
+
+    t0 = time.perf_counter()
+    # everything that can be refused without the device
+    try:
+        bs = np.atleast_1d(np.asarray(betas, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError("betas: a non-empty ascending sequence of finite numbers >= 0") from None
+    if bs.ndim != 1 or bs.size == 0 or not np.isfinite(bs).all() or (bs < 0.0).any() or (np.diff(bs) < 0.0).any():
+        raise ValueError("betas: a non-empty ascending sequence of finite numbers >= 0")
+    if not float(eps) > 0.0:
+        raise ValueError(f"eps = {eps!r} must be positive")
+    if bounds is not None:
+        bounds = _check_bounds(bounds)
+    if reference_energy is not None and not math.isfinite(float(reference_energy)):
+        raise ValueError(f"reference_energy = {reference_energy!r} is not finite")
+    if vectors is None:
+        if isinstance(num_vectors, bool) or not isinstance(num_vectors, (int, np.integer)) or not 1 <= int(num_vectors) <= MAX_COLUMNS:
+            raise ValueError(f"num_vectors = {num_vectors!r}: 1 <= num_vectors <= {MAX_COLUMNS}")
+    else:
+        if isinstance(vectors, (list, tuple)):
+            raise LsAmdError("thermal_expectation: one-partition blocks only (vectors is one (D, K) device tensor)")
+        if not hasattr(vectors, "dim") or vectors.dim() != 2 or not 1 <= int(vectors.shape[1]) <= MAX_COLUMNS:
+            raise LsAmdError(f"thermal_expectation: vectors must be an (D, K) block, 1 <= K <= {MAX_COLUMNS}")
+        if vectors.device.type != "cuda":
+            raise LsAmdError("thermal_expectation: vectors must be a device tensor")
+    basis, h, obs = kpm._load(config, observables=True)  # (refuses a Hamiltonian that is not Hermitian)
+    if isinstance(operators, (dict, _config.OperatorSpec, api.Operator)) or isinstance(operators, (int, np.integer)) or not hasattr(operators, "__iter__"):
+        operators = [operators]
+    operators = list(operators)
+    if not operators:
+        raise ValueError("thermal_expectation: no operators")
+    ops = []
+    for k, item in enumerate(operators):
+        if isinstance(item, (int, np.integer)) and not isinstance(item, bool):
+            if obs is None or not 0 <= int(item) < len(obs):
+                raise ValueError(f"operators[{k}] = {item}: the config has {0 if obs is None else len(obs)} observables")
+            item = obs[int(item)]
+        ops.append(_expectation._as_operator(basis, item, k))  # (refuses by name what ExpectationPlan refuses)
+
+    import torch
+
+    real = bool(h.isReal) and not _complex_characters(basis) and (vectors is None or not vectors.is_complex())
+    if dtype is None:
+        dtype = torch.float64 if real else torch.complex128
+    if dtype not in (torch.float64, torch.complex128):
+        raise ValueError(f"thermal_expectation: dtype = {dtype!r} is neither torch.float64 nor torch.complex128")
+    if dtype == torch.float64 and not real:
+        why = "the Hamiltonian is complex" if not h.isReal else ("the characters of the sector are complex" if _complex_characters(basis) else "vectors is complex")
+        raise LsAmdError(f"thermal_expectation: dtype = torch.float64 cannot be honoured: {why} (use torch.complex128)")
+
+    from .diagonalize import LocalOperator
+
+    reps, _ = api.enumerateStates(basis, 1)
+    if len(reps) != 1:
+        raise LsAmdError("thermal_expectation: one-partition plans only")
+    op = LocalOperator(h, reps, dtype)
+    _check_operator(op)
+    D = int(op.n_local)
+    if vectors is None:
+        R = kpm.random_phase_block(D, int(num_vectors), dtype, seed, device=op.device)
+    else:
+        if vectors.shape[0] != D:
+            raise LsAmdError(f"thermal_expectation: vectors {tuple(vectors.shape)} must have {D} rows (the sector)")
+        R = vectors.to(dtype)
+    K = int(R.shape[1])
+    if bounds is None:
+        bounds = _check_bounds(kpm.spectral_bounds(op))
+    e_ref = float(bounds[0]) if reference_energy is None else float(reference_energy)
+    plan = _expectation.ExpectationPlan(basis, reps[0], ops)
+    try:
+        B, n_ops = len(bs), plan.count
+        numerator = np.zeros((B, n_ops, K), dtype=np.complex128)
+        Z = np.zeros((B, K)); E1 = np.zeros((B, K)); E2 = np.zeros((B, K))
+        orders = np.zeros(B, dtype=np.int64)
+        before = op.matvecs
+        block = R.contiguous().clone()
+        Y = torch.empty_like(block)
+        dots = torch.zeros(2 * K, dtype=torch.float64, device=block.device)
+        t_exp = 0.0
+        prev = 0.0
+        for j, bj in enumerate(bs):
+            db = float(bj) - prev
+            if db != 0.0:
+                block, orders[j] = _cool(op, block, 0.5 * db, bounds, e_ref, eps)
+                prev = float(bj)
+            op.plan.matvec_block_axpby(block, Y, 1.0, 0.0, 0.0, dots)  # Y = H block; dots = (<X|X>, <X|Y>)
+            op.matvecs += K
+            d = dots.cpu().numpy()
+            Z[j], E1[j] = d[:K], d[K:]
+            E2[j] = (torch.linalg.vector_norm(Y, dim=0) ** 2).cpu().numpy()
+            t1 = time.perf_counter()
+            numerator[j] = plan.values_block(block)
+            t_exp += time.perf_counter() - t1
+        kernel = plan.block_kernel(K)
+        columns = op.matvecs - before
+    finally:
+        plan.destroy()
+    values, energy, heat, logz, entropy = _thermal_derived(bs, numerator.sum(axis=2), Z.sum(axis=1), E1.sum(axis=1), E2.sum(axis=1),
+                                                           D / K, e_ref)
+    res = ThermalExpectationResult(bs, numerator, Z, E1, E2, values, energy, heat, logz, entropy, D, e_ref, bounds, orders, kernel,
+                                   int(columns))
+    res.seconds = time.perf_counter() - t0
+    res.expectation_seconds = t_exp
+    return res
+
+
+def combine_sector_expectations(results) -> ThermalExpectationResult:
+    """the ensemble over several symmetry sectors from their thermal_expectation results (host only): every sector's stochastic trace
+    estimates Tr_s with the weight D_s / K_s, as in combine_sectors,
+
+        <O>_beta = sum_s (D_s / K_s) sum_k <beta_k|O|beta_k>_s  /  sum_s (D_s / K_s) sum_k Z_{s,k},
+
+    and likewise the energy, the specific heat, ln Z and the entropy.  The results must share their `betas`, their
+    `reference_energy` and their number of operators: ValueError otherwise.  -> a ThermalExpectationResult of one column per beta
+    that holds the weighted sums divided by the total dimension (so that its own fields obey the same relations)."""
+    results = list(results)
+    if not results:
+        raise ValueError("combine_sector_expectations: no results")
+    first = results[0]
+    betas = np.asarray(first.betas, dtype=np.float64)
+    B, n_ops = len(betas), np.asarray(first.numerator).shape[1]
+    num = np.zeros((B, n_ops), dtype=np.complex128)
+    Z = np.zeros(B); E1 = np.zeros(B); E2 = np.zeros(B)
+    dim, columns, seconds, t_exp = 0, 0, 0.0, 0.0
+    for s, r in enumerate(results):
+        if not np.array_equal(np.asarray(r.betas), betas):
+            raise ValueError(f"combine_sector_expectations: result {s} has other betas than result 0")
+        if float(r.reference_energy) != float(first.reference_energy):
+            raise ValueError(f"combine_sector_expectations: result {s} has reference_energy {r.reference_energy!r}, result 0 "
+                             f"{first.reference_energy!r} (pass one reference_energy to every thermal_expectation)")
+        N, Zk = np.asarray(r.numerator), np.asarray(r.partition)
+        if N.ndim != 3 or N.shape[1] != n_ops:
+            raise ValueError(f"combine_sector_expectations: result {s} has {N.shape[1] if N.ndim == 3 else '?'} operators, result 0 {n_ops}")
+        K = Zk.shape[1] if Zk.ndim == 2 else 0
+        if K < 1 or N.shape != (B, n_ops, K) or not int(r.dimension) >= 1:
+            raise ValueError(f"combine_sector_expectations: result {s} is malformed (numerator {N.shape}, partition {Zk.shape}, "
+                             f"dimension {r.dimension!r})")
+        w = float(r.dimension) / K
+        num += w * N.sum(axis=2)
+        Z += w * Zk.sum(axis=1)
+        E1 += w * np.asarray(r.energy_numerator).sum(axis=1)
+        E2 += w * np.asarray(r.energy2_numerator).sum(axis=1)
+        dim += int(r.dimension); columns += int(r.matvec_columns); seconds += float(r.seconds); t_exp += float(r.expectation_seconds)
+    e_ref = float(first.reference_energy)
+    num, Z, E1, E2 = num / dim, Z / dim, E1 / dim, E2 / dim
+    values, energy, heat, logz, entropy = _thermal_derived(betas, num, Z, E1, E2, float(dim), e_ref)
+    lo = min(float(r.bounds[0]) for r in results)
+    hi = max(float(r.bounds[1]) for r in results)
+    kernels = sorted({r.kernel for r in results})
+    return ThermalExpectationResult(betas, num[:, :, None], Z[:, None], E1[:, None], E2[:, None], values, energy, heat, logz, entropy, dim,
+                                    e_ref, (lo, hi), np.max([np.asarray(r.orders) for r in results], axis=0), "+".join(kernels), columns,
+                                    seconds, t_exp)

@@ -9,7 +9,9 @@ for every O and every sector.  The host conjugates every term of every operator 
 with the permutation signs of the Fock states), keeps the unique terms of the whole batch, and the device evaluates R of each of them in
 one pass: the image of a row under a flip mask is projected and looked up once and shared by all terms with that mask.  An image that
 leaves the conserved numbers of the basis (sigma^x on a fixed-weight basis, a lone c+) contributes exactly zero.  No floating-point
-atomics: two calls on the same input return the same bytes.  ONE partition, one state; nothing falls back to the CPU."""
+atomics: two calls on the same input return the same bytes.  ONE partition; one state per call of values, a block of up to 64 states
+per call of values_block (k_expect_blk: the images are projected and looked up once per chunk of 8 columns; DESIGN.md section 6i);
+nothing falls back to the CPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,7 +23,7 @@ from ._lib import LsAmdError
 from .correlations import _normalised
 from .entanglement import _complex_characters, _stream_ptr
 
-__all__ = ["ExpectationPlan", "expectation_values", "dimer_correlations", "pair_correlations", "expectation"]
+__all__ = ["ExpectationPlan", "expectation_values", "expectation_values_block", "dimer_correlations", "pair_correlations", "expectation"]
 
 _PARTICLE_NAMES = {v: k for k, v in config.PARTICLES.items()}
 
@@ -119,6 +121,66 @@ class ExpectationPlan:
         _lib.check(_lib.load().ls_amd_expect_values(self.h, dt, C.c_void_p(psi.data_ptr()), out.view(np.float64).ctypes.data_as(_lib.c_f64p),
                                                     _stream_ptr()))
         return out
+
+    def block_kernel(self, K):
+        """the path values_block takes for a block of K columns: "k_expect_blk", "k_expect_blk_fermi", or "columns" (the loop over
+        values, LS_AMD_EXPECT_BLOCK=columns)"""
+        if self.h is None:
+            raise LsAmdError("ExpectationPlan.block_kernel: the plan was destroyed")
+        name = _lib.load().ls_amd_expect_block_kernel_name(self.h, int(K))
+        if name is None:
+            _lib.check(-1)
+        return name.decode()
+
+    def values_block(self, psi):
+        """-> numpy complex128 (n_ops, K): <psi_c|O_k|psi_c> of every operator of the plan for the K columns, 1 <= K <= 64, of the
+        (n, K) device tensor psi (any strides, float64 or complex128) in one pass: the images, their projection and their look-up
+        are shared by a chunk of 8 columns.  The columns are taken as they are."""
+        import torch
+
+        who, n = "values_block", int(self.reps.numel())
+        if self.h is None:
+            raise LsAmdError(f"ExpectationPlan.{who}: the plan was destroyed")
+        if not isinstance(psi, torch.Tensor) or psi.device.type != "cuda":
+            raise LsAmdError(f"ExpectationPlan.{who}: psi must be a device tensor (there is no CPU path)")
+        if psi.dim() != 2:
+            raise LsAmdError(f"ExpectationPlan.{who}: psi {tuple(psi.shape)} must be a 2-D block (n, K); one vector goes through values")
+        if psi.shape[0] != n:
+            raise LsAmdError(f"ExpectationPlan.{who}: psi {tuple(psi.shape)} must have {n} rows")
+        K = int(psi.shape[1])
+        if K < 1 or K > 64:
+            raise LsAmdError(f"ExpectationPlan.{who}: K = {K} columns, outside [1, 64]")
+        if psi.dtype not in (torch.float64, torch.complex128):
+            raise LsAmdError(f"ExpectationPlan.{who}: psi is {psi.dtype}, neither float64 nor complex128")
+        if psi.dtype == torch.float64 and self.complex_characters:
+            psi = psi.to(torch.complex128)
+        rs, cs = (int(s) for s in psi.stride())
+        if K == 1:
+            cs = 1
+        if n == 1:
+            rs = max(rs, K * cs)
+        if rs <= 0 or cs <= 0 or not (rs >= K * cs or cs >= n * rs):  # (expanded or overlapping views)
+            psi = psi.contiguous()
+            rs, cs = K, 1
+        out = np.zeros((self.count, K), dtype=np.complex128)
+        _lib.check(_lib.load().ls_amd_expect_values_block(self.h, 1 if psi.dtype == torch.complex128 else 0, K, C.c_void_p(psi.data_ptr()), rs, cs,
+                                                          out.view(np.float64).ctypes.data_as(_lib.c_f64p), _stream_ptr()))
+        return out
+
+
+def expectation_values_block(basis, reps, psi, operators):
+    """<O_k> of every normalised column of the (n, K) block psi for every operator (what ExpectationPlan accepts), through one plan
+    and one pass -> complex128 (n_ops, K)"""
+    import torch
+
+    pl = ExpectationPlan(basis, reps, operators)
+    try:
+        if isinstance(psi, torch.Tensor) and psi.dim() == 2 and psi.numel():
+            nrm = torch.linalg.vector_norm(psi, dim=0)
+            psi = psi / torch.where(nrm > 0, nrm, torch.ones_like(nrm))
+        return pl.values_block(psi)
+    finally:
+        pl.destroy()
 
 
 def expectation_values(basis, reps, psi, operators):

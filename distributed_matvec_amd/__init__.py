@@ -12,10 +12,12 @@ from . import correlations  # noqa: E402  (the module keeps its name here too: i
 from .correlations import (CorrelationPlan, FermionCorrelations, SpinCorrelations, fermion_correlations, spin_correlations,  # noqa: F401,E402
                            structure_factor)
 from . import expectation  # noqa: E402  (the module keeps its name here: its driver is expectation.expectation)
-from .expectation import ExpectationPlan, dimer_correlations, expectation_values, pair_correlations  # noqa: F401,E402
+from .expectation import (ExpectationPlan, dimer_correlations, expectation_values, expectation_values_block,  # noqa: F401,E402
+                          pair_correlations)
 from . import evolve  # noqa: E402  (the module keeps its name here: its driver is evolve.evolve)
-from .evolve import (EvolveResult, ThermalCorrelationResult, autocorrelation, bessel_series, combine_sectors, propagate,  # noqa: F401,E402
-                     propagator_coefficients, thermal_correlation)
+from .evolve import (EvolveResult, ThermalCorrelationResult, ThermalExpectationResult, autocorrelation, bessel_series,  # noqa: F401,E402
+                     combine_sector_expectations, combine_sectors, propagate, propagator_coefficients, thermal_correlation,
+                     thermal_expectation)
 from . import projection  # noqa: E402
 from .projection import SectorProjection, product_state, project  # noqa: F401,E402
 

@@ -764,7 +764,8 @@ int ls_amd_test_corr_symmetrize(ls_hs_basis const *basis, int kind, double const
  * representatives: the image r ^ x of a row is projected and looked up once per flip mask x and shared by all terms with that mask.
  * No floating-point atomics; two calls on the same input return the same bytes.  psi is taken as it is (no normalisation is assumed).
  * An image that leaves the conserved numbers of the basis (sigma^x on a fixed-weight basis, a lone c+) contributes exactly zero.
- * Scope: ONE partition, one state.  ls_amd_expect_create refuses by name what ls_amd_corr_create refuses, n_ops <= 0, a NULL or
+ * Scope: ONE partition; one state per call of ls_amd_expect_values, a block of up to 64 states per call of
+ * ls_amd_expect_values_block (below).  ls_amd_expect_create refuses by name what ls_amd_corr_create refuses, n_ops <= 0, a NULL or
  * unknown operator, an operator of another basis and, on projected fermionic bases, a term that flips modes outside its projector
  * mask.  Only the term tables of the operators are read: they may be destroyed afterwards.  LS_AMD_F64 needs +-1 characters. */
 typedef struct ls_amd_expect ls_amd_expect;
@@ -777,6 +778,20 @@ int ls_amd_expect_num_terms(ls_amd_expect const *plan);  /* unique device terms 
 int ls_amd_expect_num_groups(ls_amd_expect const *plan); /* flip-mask groups the device walks */
 char const *ls_amd_expect_kernel_name(ls_amd_expect const *plan); /* "k_expect", or "k_expect_fermi" on a projected fermionic basis */
 void ls_amd_expect_destroy(ls_amd_expect *plan);
+/* Blocks of states (csrc/k_expect_blk.hip, k_expect_blk_fermi.hip): <psi_c|O_k|psi_c> of every operator of the
+ * plan for the K columns of a block in ONE pass -- the packets of a flip mask, their projection and their look-up are shared by a
+ * chunk of 8 columns; a resolved image gathers the chunk (interleaved columns: 64 / 128 consecutive bytes).  The same guarantees as
+ * ls_amd_expect_values: no floating-point atomics, equal bytes from equal inputs, the same error.
+ * d_psi: an (n, K) block of `dtype` in HBM with element strides (row, col), 1 <= K <= 64.  h_out: n_ops x K (re, im) pairs in HOST
+ * memory, operator-major (h_out[2 (k K + c)]).  Synchronises `stream`.  Refused by name: K outside [1, 64], a NULL plan, block or
+ * output, an unknown dtype, LS_AMD_F64 with complex characters, strides <= 0 and strides that make two elements share storage.
+ * The first block call allocates the plan's block buffers (16 bytes per (block of rows, term, column) of a launch, at most
+ * 8 * 4096 (term, column) pairs per launch: a batch with more splits its launches by terms and by columns).
+ * LS_AMD_EXPECT_BLOCK=auto|kernel|columns, read at every call: `columns` loops ls_amd_expect_values over the columns (through a
+ * contiguous scratch column of the plan where row != 1); `auto` is `kernel`. */
+int ls_amd_expect_values_block(ls_amd_expect *plan, ls_amd_dtype dtype, int K, void const *d_psi, int64_t row_stride, int64_t col_stride,
+                               double *h_out, void *stream);
+char const *ls_amd_expect_block_kernel_name(ls_amd_expect const *plan, int K); /* "k_expect_blk", "k_expect_blk_fermi", or "columns" */
 /* Host-only test hook (no device): the merged terms of |G|^-1 sum_g U_g O U_g^-1 in the operator's OWN orientation
  * (A|a> = v [a & m == r] (-1)^popcount(a & s) |a ^ x>), r inside m and s outside m.  Returns their number, or -1; at most `cap` are
  * written to v (re, im pairs), m, r, x, s. */
