@@ -211,6 +211,8 @@ def load():
         "ls_amd_expect_values": (C.c_int, [vp, C.c_int, vp, c_f64p, vp]),
         "ls_amd_expect_values_block": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, c_f64p, vp]),
         "ls_amd_expect_block_kernel_name": (C.c_char_p, [vp, C.c_int]),
+        "ls_amd_expect_matrix_elements": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, c_f64p, vp]),
+        "ls_amd_expect_matrix_kernel_name": (C.c_char_p, [vp, C.c_int, C.c_int]),
         "ls_amd_expect_num_terms": (C.c_int, [vp]),
         "ls_amd_expect_num_groups": (C.c_int, [vp]),
         "ls_amd_expect_kernel_name": (C.c_char_p, [vp]),

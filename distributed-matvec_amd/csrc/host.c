@@ -6870,6 +6870,10 @@ struct ls_amd_expect {
     size_t blk_partial_vals, blk_out_vals;
     void *d_blk_col;                       /* a contiguous scratch column of the column loop */
     double *h_col;                         /* the values of one column of the column loop */
+    /* ls_amd_expect_matrix_elements, owned and allocated at the first call (grown by later ones): */
+    double *d_mat_partial;                 /* the partial sums of the blocks of one matrix launch, mat_partial_vals x 16 bytes */
+    double *d_mat_out, *h_mat_out;         /* R of every (term, bra, ket), mat_out_vals x 16 bytes, and its host copy */
+    size_t mat_partial_vals, mat_out_vals;
 };
 
 void ls_amd_expect_destroy(ls_amd_expect *pl) {
@@ -6884,9 +6888,11 @@ void ls_amd_expect_destroy(ls_amd_expect *pl) {
     if (pl->d_blk_partial) lsk_free(pl->d_blk_partial);
     if (pl->d_blk_out) lsk_free(pl->d_blk_out);
     if (pl->d_blk_col) lsk_free(pl->d_blk_col);
+    if (pl->d_mat_partial) lsk_free(pl->d_mat_partial);
+    if (pl->d_mat_out) lsk_free(pl->d_mat_out);
     if (pl->gtab) ls_amd_internal_gtab_release(pl->gtab);
     free(pl->h_groups); free(pl->chunk_first); free(pl->comb_k); free(pl->comb_u); free(pl->comb_w); free(pl->h_out);
-    free(pl->h_blk_out); free(pl->h_col);
+    free(pl->h_blk_out); free(pl->h_col); free(pl->h_mat_out);
     free(pl);
 }
 
@@ -7177,6 +7183,138 @@ int ls_amd_expect_values_block(ls_amd_expect *pl, ls_amd_dtype dtype, int K, voi
         for (int k = 0; k < pl->n_ops; ++k) {
             h_out[2 * ((size_t)k * (size_t)K + (size_t)c)] = pl->h_col[2 * k];
             h_out[2 * ((size_t)k * (size_t)K + (size_t)c) + 1] = pl->h_col[2 * k + 1];
+        }
+    }
+    return 0;
+}
+
+/* ---- matrix elements between two blocks (include/ls_amd.h: ls_amd_expect_matrix_elements; csrc/k_expect_mat.hip) ---- */
+char const *ls_amd_expect_matrix_kernel_name(ls_amd_expect const *pl, int Ka, int Kb) {
+    if (!pl) { set_error("ls_amd_expect_matrix_kernel_name: NULL plan"); return NULL; }
+    if (Ka < 1 || Ka > 64 || Kb < 1 || Kb > 64) {
+        set_error("ls_amd_expect_matrix_kernel_name: Ka = %d, Kb = %d: each must be within [1, 64]", Ka, Kb);
+        return NULL;
+    }
+    return pl->bs.fermi ? lsk_expect_mat_fermi_kernel_name() : lsk_expect_mat_kernel_name();
+}
+
+/* (bra, ket) columns of one matrix launch over a chunk of nt <= LSK_EXPECT_CHUNK terms: all of them while nt * Ka * Kb stays within
+ * 8 LSK_EXPECT_CHUNK partial sums per block; else the ket columns are cut first, to the most whole chunks of 8 that fit (at least
+ * one, as nt <= LSK_EXPECT_CHUNK), and then the bra columns, to the most that fit beside them (whole chunks of 8 where 8 fit) */
+static void expect_matrix_cols(int nt, int Ka, int Kb, int *kal, int *kbl) {
+    int64_t const cap = 8 * (int64_t)LSK_EXPECT_CHUNK / nt; /* >= 8 */
+    if ((int64_t)Ka * Kb <= cap) { *kal = Ka; *kbl = Kb; return; }
+    int64_t b = cap / 8 * 8;
+    if (b > Kb) b = Kb;
+    int64_t a = cap / b;
+    if (a >= 8) a = a / 8 * 8;
+    if (a > Ka) a = Ka;
+    *kal = (int)a; *kbl = (int)b;
+}
+
+/* where launch (chunk of terms [t0, t0 + nt); bra columns from a0, kla of them; ket columns from b0) writes in d_mat_out: the chunks
+ * of terms follow each other, within one the ranges of bra columns, within those the ranges of ket columns */
+static size_t expect_matrix_at(int t0, int nt, int Ka, int Kb, int a0, int kla, int b0) {
+    return (size_t)t0 * (size_t)Ka * (size_t)Kb + (size_t)nt * ((size_t)a0 * (size_t)Kb + (size_t)kla * (size_t)b0);
+}
+
+int ls_amd_expect_matrix_elements(ls_amd_expect *pl, ls_amd_dtype dtype, int Ka, void const *d_bra, int64_t bra_row, int64_t bra_col, int Kb,
+                                  void const *d_ket, int64_t ket_row, int64_t ket_col, double *h_out, void *stream) {
+    char const *who = "ls_amd_expect_matrix_elements";
+    if (!pl || !d_bra || !d_ket) return set_error("%s: NULL %s", who, !pl ? "plan" : !d_bra ? "bra block" : "ket block");
+    if (Ka < 1 || Ka > 64) return set_error("%s: Ka = %d is outside [1, 64]", who, Ka);
+    if (Kb < 1 || Kb > 64) return set_error("%s: Kb = %d is outside [1, 64]", who, Kb);
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
+    if (dtype == LS_AMD_F64 && !pl->pm1) return set_error("%s: f64 needs +-1 characters (complex characters: use c128)", who);
+    if (!h_out) return set_error("%s: NULL output", who);
+    if (bra_row <= 0 || bra_col <= 0)
+        return set_error("%s: strides (row %lld, column %lld) of the bra block must be positive", who, (long long)bra_row, (long long)bra_col);
+    if (ket_row <= 0 || ket_col <= 0)
+        return set_error("%s: strides (row %lld, column %lld) of the ket block must be positive", who, (long long)ket_row, (long long)ket_col);
+    if (axpby_strides(who, pl->n, Ka, bra_row, bra_col, "the bra block") != 0) return -1;
+    if (axpby_strides(who, pl->n, Kb, ket_row, ket_col, "the ket block") != 0) return -1;
+    int const cplx = dtype == LS_AMD_C128, nc = cplx ? 2 : 1;
+    size_t const w = 8 * (size_t)nc;
+    char const *const bra = (char const *)d_bra, *const ket = (char const *)d_ket;
+    /* the buffers of the matrix calls: allocated here, at the first call, and grown by a call with more pairs of columns */
+    size_t part = 1;
+    for (int c = 0; c < pl->n_chunks; ++c) {
+        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
+        int const nt = pl->h_groups[g1 - 1].end - pl->h_groups[g0].begin;
+        int kal, kbl;
+        expect_matrix_cols(nt, Ka, Kb, &kal, &kbl);
+        size_t const v = (size_t)nt * (size_t)kal * (size_t)kbl;
+        if (v > part) part = v;
+    }
+    part *= (size_t)lsk_corr_blocks(pl->n);
+    if (part > pl->mat_partial_vals) {
+        if (pl->d_mat_partial) { lsk_free(pl->d_mat_partial); pl->d_mat_partial = NULL; pl->mat_partial_vals = 0; }
+        void *p = NULL;
+        DEV(lsk_malloc(&p, 16 * part));
+        pl->d_mat_partial = (double *)p; pl->mat_partial_vals = part;
+    }
+    size_t const pairs = (size_t)Ka * (size_t)Kb;
+    size_t const vals = (size_t)(pl->n_terms > 0 ? pl->n_terms : 1) * pairs;
+    if (vals > pl->mat_out_vals) {
+        if (pl->d_mat_out) { lsk_free(pl->d_mat_out); pl->d_mat_out = NULL; }
+        free(pl->h_mat_out); pl->h_mat_out = NULL; pl->mat_out_vals = 0;
+        void *p = NULL;
+        DEV(lsk_malloc(&p, 16 * vals));
+        pl->d_mat_out = (double *)p;
+        pl->h_mat_out = (double *)malloc(16 * vals);
+        if (!pl->h_mat_out) return set_error("%s: out of host memory", who);
+        pl->mat_out_vals = vals;
+    }
+    /* the launches: per chunk of terms, per range of bra columns, per range of ket columns; a launch writes
+     * R[((u - t0) kla + (a - a0)) klb + (b - b0)] of its nt terms at expect_matrix_at() of d_mat_out */
+    for (int c = 0; c < pl->n_chunks; ++c) {
+        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
+        int const t0 = pl->h_groups[g0].begin, nt = pl->h_groups[g1 - 1].end - t0;
+        int kal, kbl;
+        expect_matrix_cols(nt, Ka, Kb, &kal, &kbl);
+        for (int a0 = 0; a0 < Ka; a0 += kal) {
+            int const kla = Ka - a0 < kal ? Ka - a0 : kal;
+            for (int b0 = 0; b0 < Kb; b0 += kbl) {
+                int const klb = Kb - b0 < kbl ? Kb - b0 : kbl;
+                DEV(lsk_expect_mat(pl->bs, pl->six, pl->gtab ? pl->gtab->tab : no_gtab(), pl->cons, g1 - g0, pl->d_groups + g0, pl->d_terms, t0,
+                                   nt, cplx, pl->n, pl->d_reps, pl->d_norms, kla, bra + (size_t)a0 * (size_t)bra_col * w, bra_row, bra_col, klb,
+                                   ket + (size_t)b0 * (size_t)ket_col * w, ket_row, ket_col, pl->d_mat_partial,
+                                   pl->d_mat_out + expect_matrix_at(t0, nt, Ka, Kb, a0, kla, b0) * nc, pl->d_err, stream));
+            }
+        }
+    }
+    int flag = 0, zero = 0;
+    DEV(lsk_sync(stream));
+    DEV(lsk_d2h(&flag, pl->d_err, sizeof(int)));
+    if (flag) {
+        DEV(lsk_h2d(pl->d_err, &zero, sizeof(int)));
+        return set_error("expectation values: the image of a representative under a term keeps the conserved numbers, has non-zero norm "
+                         "and is not in the basis (the array of representatives does not belong to this basis or is not the whole "
+                         "sector: another Hamming weight, a truncated array)");
+    }
+    if (pl->n_terms > 0) DEV(lsk_d2h(pl->h_mat_out, pl->d_mat_out, w * (size_t)pl->n_terms * pairs));
+    for (size_t k = 0; k < 2 * (size_t)pl->n_ops * pairs; ++k) h_out[k] = 0.0;
+    /* value[k][a][b] = sum_u w[k][u] R[u][a][b]: the loop of ls_amd_expect_values per pair (comb_u ascends: the chunk follows it) */
+    int ch = 0;
+    for (size_t i = 0; i < pl->n_comb; ++i) {
+        int const u = pl->comb_u[i];
+        while (u >= pl->h_groups[pl->chunk_first[ch + 1] - 1].end) ++ch;
+        int const t0 = pl->h_groups[pl->chunk_first[ch]].begin, nt = pl->h_groups[pl->chunk_first[ch + 1] - 1].end - t0;
+        int kal, kbl;
+        expect_matrix_cols(nt, Ka, Kb, &kal, &kbl);
+        double const wr = pl->comb_w[2 * i], wi = pl->comb_w[2 * i + 1];
+        double *const o = h_out + 2 * (size_t)pl->comb_k[i] * pairs;
+        for (int a = 0; a < Ka; ++a) {
+            int const a0 = a / kal * kal, kla = Ka - a0 < kal ? Ka - a0 : kal;
+            for (int b = 0; b < Kb; ++b) {
+                int const b0 = b / kbl * kbl, klb = Kb - b0 < kbl ? Kb - b0 : kbl;
+                size_t const at = expect_matrix_at(t0, nt, Ka, Kb, a0, kla, b0) + ((size_t)(u - t0) * (size_t)kla + (size_t)(a - a0)) * (size_t)klb
+                                  + (size_t)(b - b0);
+                double const rr = cplx ? pl->h_mat_out[2 * at] : pl->h_mat_out[at], ri = cplx ? pl->h_mat_out[2 * at + 1] : 0.0;
+                double *const v = o + 2 * ((size_t)a * (size_t)Kb + (size_t)b);
+                v[0] += wr * rr - wi * ri;
+                v[1] += wr * ri + wi * rr;
+            }
         }
     }
     return 0;

@@ -776,6 +776,22 @@ int lsk_expect_blk_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_co
                          lsk_expect_term const *terms, int term0, int n_terms, int cplx, int64_t n, uint64_t const *reps,
                          double const *norms, int K, void const *psi, int64_t p_row, int64_t p_col, double *partial, double *out,
                          int *d_err, void *stream);
+/* matrix elements between two blocks (k_expect_mat.hip, k_expect_mat_fermi.hip): lsk_expect_blk with a bra
+ * block phi (n, Ka; strides a_row, a_col) and a ket block psi (n, Kb; strides k_row, k_col), 1 <= Ka, Kb <= 64 --
+ *     out[(u Ka + a) Kb + b] = sum over the rows r with r & m == r_u of (-1)^popcount(r & s) conj(phi[r, a]) / norms[r] * <r ^ x|psi[:, b]>
+ * (1 double for f64, 2 for c128).  The packets, their projection and their look-up are shared by a chunk of 8 bra x 8 ket columns.
+ * n_terms * Ka * Kb <= 8 LSK_EXPECT_CHUNK; `partial` holds lsk_corr_blocks(n) * n_terms * Ka * Kb values, `out` n_terms * Ka * Kb.  Both
+ * blocks are only read and may be the same memory.  No floating-point atomics. */
+char const *lsk_expect_mat_kernel_name(void);
+char const *lsk_expect_mat_fermi_kernel_name(void);
+int lsk_expect_mat(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, int n_groups, lsk_expect_group const *groups,
+                   lsk_expect_term const *terms, int term0, int n_terms, int cplx, int64_t n, uint64_t const *reps, double const *norms,
+                   int Ka, void const *phi, int64_t a_row, int64_t a_col, int Kb, void const *psi, int64_t k_row, int64_t k_col,
+                   double *partial, double *out, int *d_err, void *stream);
+int lsk_expect_mat_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_expect_cons cons, int n_groups, lsk_expect_group const *groups,
+                         lsk_expect_term const *terms, int term0, int n_terms, int cplx, int64_t n, uint64_t const *reps,
+                         double const *norms, int Ka, void const *phi, int64_t a_row, int64_t a_col, int Kb, void const *psi,
+                         int64_t k_row, int64_t k_col, double *partial, double *out, int *d_err, void *stream);
 
 /* plan-time helpers -------------------------------------------------------------------------- */
 /* norms[i] = sqrt(stab(reps[i]) / |G|) */

@@ -12,8 +12,8 @@ from . import correlations  # noqa: E402  (the module keeps its name here too: i
 from .correlations import (CorrelationPlan, FermionCorrelations, SpinCorrelations, fermion_correlations, spin_correlations,  # noqa: F401,E402
                            structure_factor)
 from . import expectation  # noqa: E402  (the module keeps its name here: its driver is expectation.expectation)
-from .expectation import (ExpectationPlan, dimer_correlations, expectation_values, expectation_values_block,  # noqa: F401,E402
-                          pair_correlations)
+from .expectation import (ExpectationPlan, dimer_correlations, eigenstate_matrix_elements, expectation_values,  # noqa: F401,E402
+                          expectation_values_block, matrix_elements, pair_correlations)
 from . import evolve  # noqa: E402  (the module keeps its name here: its driver is evolve.evolve)
 from .evolve import (EvolveResult, ThermalCorrelationResult, ThermalExpectationResult, autocorrelation, bessel_series,  # noqa: F401,E402
                      combine_sector_expectations, combine_sectors, propagate, propagator_coefficients, thermal_correlation,

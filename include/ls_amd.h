@@ -792,6 +792,24 @@ void ls_amd_expect_destroy(ls_amd_expect *plan);
 int ls_amd_expect_values_block(ls_amd_expect *plan, ls_amd_dtype dtype, int K, void const *d_psi, int64_t row_stride, int64_t col_stride,
                                double *h_out, void *stream);
 char const *ls_amd_expect_block_kernel_name(ls_amd_expect const *plan, int K); /* "k_expect_blk", "k_expect_blk_fermi", or "columns" */
+/* Matrix elements between two blocks of states of the sector (csrc/k_expect_mat.hip, k_expect_mat_fermi.hip):
+ * <phi_a|O_k|psi_b> of every operator of the plan for every column a of a bra block and every column b of a ket block in ONE pass.
+ * Two states of one sector transform with the same character, so the group average of O maps the sector into itself and
+ *     <phi|O|psi> = |G|^-1 sum_{g in G} R[U_g O U_g^-1](phi, psi),    R[A](phi, psi) = sum_r conj(phi_r) / n(r) (A psi^)(r)
+ * over the representatives alone: the sesquilinear form of R above, ANTILINEAR in the bra (its columns are conjugated) and linear in
+ * the ket (the block the operator acts on).  The plan, its term tables and its combination are those of ls_amd_expect_create; the
+ * packets of a flip mask, their projection and their look-up are shared by a chunk of 8 bra x 8 ket columns.  The same guarantees as
+ * ls_amd_expect_values: no floating-point atomics, equal bytes from equal inputs, the same error.  The columns are taken as they are.
+ * d_bra: an (n, Ka) block, d_ket: an (n, Kb) block, both of `dtype` in HBM, each with its own element strides (row, col),
+ * 1 <= Ka, Kb <= 64; both are only read and may be the same memory or overlap.  h_out: n_ops x Ka x Kb (re, im) pairs in HOST memory,
+ * operator-major, then bra, then ket (h_out[2 ((k Ka + a) Kb + b)] = Re <phi_a|O_k|psi_b>).  Synchronises `stream`.  Refused by name:
+ * a NULL plan, block or output, Ka or Kb outside [1, 64], an unknown dtype, LS_AMD_F64 with complex characters, strides <= 0 and
+ * strides that make two elements of one block share storage.
+ * The first call allocates the plan's matrix buffers (16 bytes per (block of rows, term, bra, ket) of a launch, at most 8 * 4096
+ * (term, bra, ket) triples per launch: a larger batch splits its launches by terms, then by ket columns, then by bra columns). */
+int ls_amd_expect_matrix_elements(ls_amd_expect *plan, ls_amd_dtype dtype, int Ka, void const *d_bra, int64_t bra_row, int64_t bra_col,
+                                  int Kb, void const *d_ket, int64_t ket_row, int64_t ket_col, double *h_out, void *stream);
+char const *ls_amd_expect_matrix_kernel_name(ls_amd_expect const *plan, int Ka, int Kb); /* "k_expect_mat" or "k_expect_mat_fermi" */
 /* Host-only test hook (no device): the merged terms of |G|^-1 sum_g U_g O U_g^-1 in the operator's OWN orientation
  * (A|a> = v [a & m == r] (-1)^popcount(a & s) |a ^ x>), r inside m and s outside m.  Returns their number, or -1; at most `cap` are
  * written to v (re, im pairs), m, r, x, s. */
