@@ -157,6 +157,9 @@ def load():
         "ls_amd_block_axpby_acc": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp,
                                              C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                              C.c_double, vp, vp]),
+        "ls_amd_matvec_block_series": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_double, C.c_double, vp, C.c_int64, C.c_int64, vp, C.c_int64,
+                                                 C.c_int64, C.c_int, vp, vp]),
+        "ls_amd_plan_series_kernel_name": (C.c_char_p, [vp, C.c_int]),
         "ls_amd_plan_check": (C.c_int, [vp, vp]),
         "ls_amd_plan_enable_timing": (C.c_int, [vp, C.c_int]),
         "ls_amd_plan_kernel_times": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int, c_intp]),

@@ -729,6 +729,54 @@ class MatvecPlan:
             _lib.check(-1)
         return name.decode()
 
+    def matvec_block_series(self, x, z, coefficients, bounds, check: bool = True, work=None):
+        """Z <- sum_n c_n T_n((H - b) / a) X for the K columns of the (N, K) device tensors x and z (vectors are blocks of one
+        column), a = (hi - lo) / 2, b = (hi + lo) / 2 of bounds = (lo, hi) (ls_amd_matvec_block_series): one accumulate step per
+        order, the loop and the growth guard in C.  x: the plan's dtype, any nested strides, left as it was.  z: the plan's dtype or
+        complex128 (float64 only with real coefficients), strides of its own, assigned; it must not overlap x.  coefficients: N + 1
+        numbers, real or complex.  work: None (the plan allocates two blocks and keeps them), or a contiguous device tensor of
+        2 N K elements of the plan's dtype.  Bounds that do not enclose the spectrum raise LsAmdError naming them.
+        series_kernel(K) names the path."""
+        torch = _torch()
+        import numpy as np
+
+        who = "matvec_block_series"
+        if self.P != 1 or self.me >= 0:
+            raise _lib.LsAmdError(f"{who}: one-partition plans only (this plan has P = {self.P}, my_partition = {self.me})")
+        want = torch.complex128 if self.cplx else torch.float64
+        (x,), z, _ = _acc_args(who, [("x", x)], z, 0.0, want=want)
+        n = self.reps[0].numel()
+        if x.shape[0] != n:
+            raise _lib.LsAmdError(f"{who}: x {tuple(x.shape)} and z must both be ({n}, K)")
+        K = int(x.shape[1])
+        c = np.ascontiguousarray(np.asarray(coefficients, dtype=np.complex128).reshape(-1))
+        if c.size < 1:
+            raise _lib.LsAmdError(f"{who}: no coefficients")
+        if z.dtype == torch.float64 and np.any(c.imag != 0.0):
+            raise _lib.LsAmdError(f"{who}: z is float64 and the coefficients are not real: the accumulator must be complex128")
+        try:
+            lo, hi = float(bounds[0]), float(bounds[1])
+        except (TypeError, ValueError, IndexError):
+            raise _lib.LsAmdError(f"{who}: bounds = {bounds!r}: need finite lo < hi") from None
+        wp = None
+        if work is not None:
+            if not isinstance(work, torch.Tensor) or work.device.type != "cuda" or work.dtype != want or not work.is_contiguous() \
+                    or work.numel() < 2 * n * K:
+                raise _lib.LsAmdError(f"{who}: work must be a contiguous device tensor of at least {2 * n * K} elements of {want}")
+            wp = C.c_void_p(work.data_ptr())
+        _lib.check(_lib.load().ls_amd_matvec_block_series(self.h, K, int(c.size) - 1, c.ctypes.data_as(C.c_void_p), lo, hi,
+                                                          C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), C.c_void_p(z.data_ptr()),
+                                                          z.stride(0), z.stride(1), int(z.dtype == torch.complex128), wp, _stream_ptr()))
+        if check:
+            self.check()
+
+    def series_kernel(self, K: int) -> str:
+        """row path of every order of matvec_block_series for K columns: what axpby_kernel(K) returns"""
+        name = _lib.load().ls_amd_plan_series_kernel_name(self.h, int(K))
+        if name is None:
+            _lib.check(-1)
+        return name.decode()
+
     def check(self):
         _lib.check(_lib.load().ls_amd_plan_check(self.h, _stream_ptr()))
 

@@ -1790,6 +1790,9 @@ struct ls_amd_plan {
     lsk_tilemap blk_tilemap;
     void *d_blk_tilemap;
     void *d_blk_cols; /* [2][count] elements */
+    void *d_series_work;      /* ls_amd_matvec_block_series without caller's work: two blocks of count x series_cols elements */
+    int series_cols;
+    double *d_series_dots;    /* [64][2 * 64]: the dots of 64 orders */
     void const *y_checked[2]; /* y pointers whose memory kind was looked at (push plans: ls_amd_internal_check_y) */
     int leaves_basis;         /* pull plan over a non-Hermitian operator whose row expansion leaves the basis (found at plan time) */
     /* kernel timing ring */
@@ -2098,6 +2101,11 @@ static void block_free(ls_amd_plan *pl) {
     memset(&pl->blk_tilemap, 0, sizeof(pl->blk_tilemap));
     if (pl->d_blk_cols) lsk_free(pl->d_blk_cols);
     pl->d_blk_cols = NULL;
+    if (pl->d_series_work) lsk_free(pl->d_series_work);
+    pl->d_series_work = NULL;
+    pl->series_cols = 0;
+    if (pl->d_series_dots) lsk_free(pl->d_series_dots);
+    pl->d_series_dots = NULL;
 }
 /* room for the packet streams of as many of the plan's rows as `max_bytes` allow (all of them if it can); returns the number
  * of rows covered (0: none -- the plan keeps the fused kernel) */
@@ -4730,6 +4738,120 @@ int ls_amd_matvec_block_axpby_acc(ls_amd_plan *pl, int K, void const *d_x, int64
         stage_end(pl, st, stream);
     }
     timing_end(pl, slot, stream);
+    return 0;
+}
+
+/* ============================================================================================ */
+/* a whole Chebyshev series on a block (ls_amd_matvec_block_series): the accumulate step above,  */
+/* once per order, between two work blocks; no kernel of its own                                 */
+/* ============================================================================================ */
+#define SERIES_GUARD_EVERY 64   /* orders between two read-backs of the dots (kpm.GUARD_EVERY) */
+#define SERIES_GUARD_SLACK 1e-6 /* kpm.GUARD_SLACK */
+char const *ls_amd_plan_series_kernel_name(ls_amd_plan const *pl, int K) {
+    if (!pl) { set_error("ls_amd_plan_series_kernel_name: plan is NULL"); return NULL; }
+    if (K < 1 || K > 64) { set_error("ls_amd_plan_series_kernel_name: K = %d is outside [1, 64]", K); return NULL; }
+    return g_axpby_names[block_path(pl, K)];
+}
+
+/* Z <- 0 for any strides axpby_strides lets through: one memset where the block is dense, else column by column (in slabs of rows)
+ * out of `zeros`, zero_bytes of cleared device memory */
+static int series_clear(char *z, size_t wz, int64_t n, int K, int64_t zr, int64_t zc, void const *zeros, size_t zero_bytes, void *stream) {
+    if ((n - 1) * zr + (int64_t)(K - 1) * zc + 1 == n * (int64_t)K) {
+        DEV(lsk_memset_async(z, 0, wz * (size_t)n * (size_t)K, stream));
+        return 0;
+    }
+    int64_t const slab = (int64_t)(zero_bytes / wz);
+    if (slab < 1) return set_error("ls_amd_matvec_block_series: no room to clear Z from");
+    for (int k = 0; k < K; ++k)
+        for (int64_t r0 = 0; r0 < n; r0 += slab) {
+            int64_t const rows = r0 + slab < n ? slab : n - r0;
+            DEV(lsk_copy_strided(rows, (int)wz, zeros, 1, z + ((size_t)k * (size_t)zc + (size_t)r0 * (size_t)zr) * wz, zr, stream));
+        }
+    return 0;
+}
+
+int ls_amd_matvec_block_series(ls_amd_plan *pl, int K, int N, double const *coeffs, double lo, double hi, void const *d_x, int64_t x_row,
+                               int64_t x_col, void *d_z, int64_t z_row, int64_t z_col, int z_cplx, void *d_work, void *stream) {
+    char const *const who = "ls_amd_matvec_block_series";
+    if (!pl) return set_error("%s: plan is NULL", who);
+    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
+    if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1)
+        return set_error("%s: one-partition plans only (this plan has P = %d, my_partition = %d)", who, pl->P, pl->me);
+    if (N < 0) return set_error("%s: N = %d is negative", who, N);
+    if (!coeffs) return set_error("%s: coeffs is NULL", who);
+    if (!(isfinite(lo) && isfinite(hi) && lo < hi)) return set_error("%s: bounds (%.17g, %.17g): need finite lo < hi", who, lo, hi);
+    z_cplx = z_cplx != 0;
+    for (int i = 0; i <= N; ++i) {
+        if (!(isfinite(coeffs[2 * i]) && isfinite(coeffs[2 * i + 1])))
+            return set_error("%s: coeffs[%d] = (%g, %g) is not finite", who, i, coeffs[2 * i], coeffs[2 * i + 1]);
+        if (!z_cplx && coeffs[2 * i + 1] != 0.0)
+            return set_error("%s: z_cplx = 0 with Im coeffs[%d] = %g: an f64 Z needs real coefficients", who, i, coeffs[2 * i + 1]);
+    }
+    int64_t const n = pl->parts[0].count;
+    if (n <= 0) return 0;
+    if (!d_x) return set_error("%s: X is NULL", who);
+    if (K == 1) { x_col = 0; z_col = 0; }
+    if (acc_check_z(who, pl->cplx, z_cplx, n, K, d_z, z_row, z_col, 0.0) != 0) return -1;
+    if (axpby_strides(who, n, K, x_row, x_col, "X") != 0) return -1;
+    size_t const w = pl->cplx ? 16 : 8, wz = z_cplx ? 16 : 8;
+    size_t const block = w * (size_t)n * (size_t)K;
+    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_x, x_row, x_col)) return set_error("%s: Z and X overlap", who);
+    char *work = (char *)d_work;
+    if (!work) {
+        if (pl->d_series_work && pl->series_cols < K) {
+            DEV(lsk_sync(stream));
+            lsk_free(pl->d_series_work);
+            pl->d_series_work = NULL;
+            pl->series_cols = 0;
+        }
+        if (!pl->d_series_work) {
+            if (lsk_malloc(&pl->d_series_work, 2 * block) != 0) return dev_error();
+            pl->series_cols = K;
+        }
+        work = (char *)pl->d_series_work;
+    }
+    {
+        uintptr_t const a0 = (uintptr_t)work, a1 = a0 + 2 * block;
+        uintptr_t const x0 = (uintptr_t)d_x, x1 = x0 + w * (size_t)((n - 1) * x_row + (int64_t)(K - 1) * x_col + 1);
+        uintptr_t const z0 = (uintptr_t)d_z, z1 = z0 + wz * (size_t)((n - 1) * z_row + (int64_t)(K - 1) * z_col + 1);
+        if (a0 < x1 && x0 < a1) return set_error("%s: work and X overlap", who);
+        if (a0 < z1 && z0 < a1) return set_error("%s: work and Z overlap", who);
+    }
+    if (!pl->d_series_dots && lsk_malloc((void **)&pl->d_series_dots, sizeof(double) * SERIES_GUARD_EVERY * 128) != 0) return dev_error();
+    double const a = 0.5 * (hi - lo), b = 0.5 * (hi + lo);
+    /* the two work blocks in the interleaved layout (row stride K, column stride 1): cur = v_n, oth = v_{n-1}, overwritten by v_{n+1} */
+    char *cur = work, *oth = work + block;
+    /* Z <- c_0 X: Z cleared (oth, cleared, is where a padded Z copies its zeros from), then the accumulate alone over X */
+    DEV(lsk_memset_async(oth, 0, block, stream));
+    if (series_clear((char *)d_z, wz, n, K, z_row, z_col, oth, block, stream) != 0) return -1;
+    DEV(lsk_axpby_acc(pl->cplx, n, K, NULL, 0, 0, NULL, 0, 0, (void *)(uintptr_t)d_x, x_row, x_col, 0.0, 0.0, 1.0, d_z, z_row, z_col, z_cplx,
+                      coeffs[0], coeffs[1], NULL, NULL, stream));
+    if (N == 0) return 0;
+    for (int k = 0; k < K; ++k)
+        DEV(lsk_copy_strided(n, (int)w, (char const *)d_x + (size_t)k * (size_t)x_col * w, x_row, cur + (size_t)k * w, K, stream));
+    double mu0[64], host[SERIES_GUARD_EVERY * 128];
+    for (int s = 0, checked = 0; s < N; ++s) {
+        double *const dots = pl->d_series_dots + (size_t)(s - checked) * 2 * (size_t)K;
+        double const al = (s == 0 ? 1.0 : 2.0) / a, be = (s == 0 ? -1.0 : -2.0) * b / a, ga = s == 0 ? 0.0 : -1.0;
+        if (ls_amd_matvec_block_axpby_acc(pl, K, cur, K, 1, oth, K, 1, al, be, ga, d_z, z_row, z_col, z_cplx, coeffs[2 * (s + 1)],
+                                          coeffs[2 * (s + 1) + 1], dots, stream) != 0)
+            return -1;
+        char *const t = cur; cur = oth; oth = t;
+        if (s + 1 - checked == SERIES_GUARD_EVERY || s + 1 == N) {
+            int const rows = s + 1 - checked;
+            DEV(lsk_sync(stream));
+            DEV(lsk_d2h(host, pl->d_series_dots, sizeof(double) * (size_t)rows * 2 * (size_t)K));
+            if (checked == 0) memcpy(mu0, host, sizeof(double) * (size_t)K);
+            for (int r = 0; r < rows; ++r)
+                for (int k = 0; k < K; ++k) {
+                    double const vv = host[(size_t)r * 2 * (size_t)K + k];
+                    if (!(vv <= (1.0 + SERIES_GUARD_SLACK) * mu0[k]))
+                        return set_error("%s: the Chebyshev recurrence grows at order %d (<v_n|v_n> / <v_0|v_0> = %.6g in column %d): the "
+                                         "spectrum is not inside the bounds (%.17g, %.17g)", who, checked + r, vv / mu0[k], k, lo, hi);
+                }
+            checked = s + 1;
+        }
+    }
     return 0;
 }
 

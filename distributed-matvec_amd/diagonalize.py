@@ -541,15 +541,245 @@ def lanczos_block_smallest(op, num_evals: int = 1, block_size: int = 4, eps: flo
             prof["restart"] += tick() - t_a
 
 
+class FilteredOperator:
+    """-p(H) = -sum_n c_n T_n((H - b) / a) through the operator interface lanczos_block_smallest uses (matvec_block, matvec,
+    random_vector, new_vector, matvecs, check, dtype, n_local, sizes, device, block_kernel): with the coefficients of
+    kpm.delta_filter the levels of H nearest sigma are its SMALLEST.  op: a LocalOperator on one partition; every application is
+    one MatvecPlan.matvec_block_series.  matvecs counts columns x orders of H (they are added to op.matvecs as well),
+    applications the filter calls."""
+
+    def __init__(self, op, coefficients, bounds):
+        import numpy as np
+
+        if len(op.sizes) != 1:
+            raise ValueError("FilteredOperator: one-partition plans only")
+        c = np.asarray(coefficients, dtype=np.float64).reshape(-1)
+        if c.size < 1 or not np.isfinite(c).all():
+            raise ValueError("FilteredOperator: coefficients: a non-empty sequence of finite real numbers")
+        lo, hi = float(bounds[0]), float(bounds[1])
+        if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+            raise ValueError(f"FilteredOperator: bounds = ({bounds[0]!r}, {bounds[1]!r}): need finite lo < hi")
+        self.op = op
+        self.coefficients = c
+        self._negated = -c
+        self.bounds = (lo, hi)
+        self.order = int(c.size) - 1
+        self.dtype = op.dtype
+        self.n_local = op.n_local
+        self.sizes = list(op.sizes)
+        self.device = op.device
+        self.matvecs = 0
+        self.applications = 0
+        self.seconds = 0.0  # wall time inside the filter calls
+
+    def matvec_block(self, x, y):
+        """Y <- -p(H) X for the K <= 64 columns of the (n, K) views x and y (any nested strides; x is left as it was)"""
+        K = int(x.shape[1])
+        t0 = time.perf_counter()
+        self.op.plan.matvec_block_series(x, y, self._negated, self.bounds, check=False)  # (returns after its last guard read-back)
+        self.seconds += time.perf_counter() - t0
+        self.matvecs += K * self.order
+        self.op.matvecs += K * self.order
+        self.applications += 1
+
+    def matvec(self, x, y):
+        self.matvec_block(x.reshape(-1, 1), y.reshape(-1, 1))
+
+    def check(self):
+        self.op.check()
+
+    def dot(self, a, b):
+        return self.op.dot(a, b)
+
+    def new_vector(self):
+        return self.op.new_vector()
+
+    def random_vector(self, seed):
+        return self.op.random_vector(seed)
+
+    def block_kernel(self, K):
+        return self.op.plan.series_kernel(K)
+
+
+@dataclass
+class InteriorResult:
+    eigenvalues: list         # the num_evals levels nearest sigma, ascending
+    eigenvectors: list        # device vectors, one per level
+    residual_norms: list      # ||H y - theta y||, computed from H y itself
+    sigma: float
+    order: int                # of the filter polynomial
+    bounds: tuple             # (lo, hi) the spectrum was rescaled with
+    applications: int         # filter calls (each one `order` block steps)
+    matvecs: int              # columns that went through H: the filter's columns x orders, and the Rayleigh-Ritz steps
+    polish_rounds: int
+    converged: bool           # every residual <= eps max(|lo|, |hi|)
+    seconds: float
+    filter_seconds: float = 0.0   # ... of which inside the filter calls (Lanczos run and polish rounds)
+    orth_seconds: float = 0.0     # ... of which in the Lanczos run outside the filter: orthogonalisation, restarts, the small problems
+    ritz_seconds: float = 0.0     # ... of which inside the Rayleigh-Ritz steps (orthonormalisation, H Q, rotation, residuals)
+    lanczos_restarts: int = 0
+    kernel: str = ""          # MatvecPlan.series_kernel(block_size)
+
+
+INTERIOR_MAX_RESTARTS = 30    # of the Lanczos run on p(H); what is left is the polish rounds' to finish
+
+
+def _interior_window(num_evals, guard, block_size, max_basis):
+    """the basis window lanczos_block_smallest opens for num_evals + guard pairs, and the rows its fused orthogonalisation holds"""
+    return max(max_basis if max_basis is not None else 0, 2 * (num_evals + guard) + 3 * block_size), 128
+
+
+def interior_eigenpairs(config_or_op, sigma, num_evals: int = 8, eps: float = 1e-6, block_size: int = 8, order=None, guard=None,
+                        bounds=None, max_basis=None, max_polish: int = 3, seed: int = 1234, dtype=None, cut=None,
+                        verbose: bool = False) -> InteriorResult:
+    """The `num_evals` eigenpairs of a Hermitian operator nearest the energy `sigma`, at any basis size the matvec reaches on one
+    partition: polynomially filtered block Lanczos (POLFED: Sierant, Lewenstein, Zakrzewski, PRL 125, 156601).
+    config_or_op: a config (dict or YAML path) with a `hamiltonian:`, or a LocalOperator.
+    1. bounds (kpm.spectral_bounds when None) and the order of the filter (kpm.filter_order for num_evals + guard levels, guard =
+       max(block_size, num_evals // 4), from a density of states of 64 moments when None); p = kpm.delta_filter(sigma, bounds, order).
+    2. lanczos_block_smallest on FilteredOperator(-p(H)) for num_evals + guard pairs, to eps / 4 of p's scale.
+    3. Rayleigh-Ritz against H itself on the vectors it returns: p is flat at its peak, so p's own Ritz vectors do not separate
+       neighbouring levels of H -- only the space they span is accurate.  The block is orthonormalised (Cholesky-QR twice), H Q is
+       formed in blocks of <= 64 columns, the small problem solved on the host, and ||H y - theta y|| computed from H y.
+    4. The num_evals pairs nearest sigma are kept; converged when each residual <= eps max(|lo|, |hi|).
+    5. Otherwise up to max_polish rounds of subspace iteration: one more filter application on the whole Ritz block, then 3 and 4.
+       What is still not converged after them is returned with converged=False.
+    Refused before any device work: an operator that is not Hermitian, more than one partition, num_evals + guard beyond the basis
+    window of lanczos_block_smallest, a sigma outside given bounds, order < 2.  -> InteriorResult."""
+    import numpy as np
+    import torch
+
+    from . import api, kpm
+
+    t0 = time.perf_counter()
+    who = "interior_eigenpairs"
+    for name, v, least in (("num_evals", num_evals, 1), ("block_size", block_size, 1), ("max_polish", max_polish, 0)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+            raise ValueError(f"{who}: {name} = {v!r}: an integer >= {least}")
+    if block_size > 16:
+        raise ValueError(f"{who}: block_size = {block_size}: the block solver takes 1 <= block_size <= 16")
+    if guard is None:
+        guard = max(int(block_size), int(num_evals) // 4)
+    if isinstance(guard, bool) or not isinstance(guard, (int, np.integer)) or guard < 0:
+        raise ValueError(f"{who}: guard = {guard!r}: an integer >= 0")
+    if order is not None and (isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order < 2):
+        raise ValueError(f"{who}: order = {order!r}: the filter needs an order >= 2")
+    if not float(eps) > 0.0:
+        raise ValueError(f"{who}: eps = {eps!r} must be positive")
+    cut = kpm.FILTER_CUT if cut is None else float(cut)
+    want = int(num_evals) + int(guard)
+    window, rows = _interior_window(int(num_evals), int(guard), int(block_size), max_basis)
+    if window > rows:
+        raise ValueError(f"{who}: num_evals + guard = {want} with block_size = {block_size} needs a basis of {window} vectors; "
+                         f"lanczos_block_smallest holds {rows} (2 (num_evals + guard) + 3 block_size <= {rows}, and max_basis <= {rows})")
+    if bounds is not None:
+        bounds = kpm._bounds(bounds, who)
+        kpm._scaled_sigma(sigma, bounds[0], bounds[1], who)
+    elif not math.isfinite(float(sigma)):
+        raise ValueError(f"{who}: sigma = {sigma!r} is not finite")
+    if isinstance(config_or_op, LocalOperator) or hasattr(config_or_op, "plan"):
+        op = config_or_op
+        if not op.plan.matrix.isHermitian:
+            raise ValueError(f"{who}: the operator is not Hermitian (the filter needs a real spectrum)")
+        if len(op.sizes) != 1:
+            raise api.LsAmdError(f"{who}: one-partition plans only (this operator has {len(op.sizes)} partitions)")
+    else:
+        load = api.loadConfigFromYaml if isinstance(config_or_op, str) else api.loadConfigFromDict
+        basis, h = load(config_or_op, hamiltonian=True)
+        if not h.isHermitian:
+            raise ValueError(f"{who}: the Hamiltonian is not Hermitian (the filter needs a real spectrum)")
+        if dtype is None:
+            dtype = torch.float64 if h.isReal and not api._complex_characters(basis) else torch.complex128
+        reps, _ = api.enumerateStates(basis, 1)
+        op = LocalOperator(h, reps, dtype)
+    n = int(op.n_local)
+    if want > n:
+        raise ValueError(f"{who}: num_evals + guard = {want} exceeds the dimension {n} of the basis")
+    if bounds is None:
+        bounds = kpm._bounds(kpm.spectral_bounds(op), who)
+        kpm._scaled_sigma(sigma, bounds[0], bounds[1], who)
+    lo, hi = bounds
+    sigma = float(sigma)
+    before = op.matvecs
+    if order is None:
+        order = kpm.filter_order(want, n, None, bounds, cut=cut, sigma=sigma, op=op)
+    order = int(order)
+    fop = FilteredOperator(op, kpm.delta_filter(sigma, bounds, order), bounds)
+    h_norm = max(abs(lo), abs(hi))
+    t_ritz = 0.0
+
+    def clock():
+        if op.device.type == "cuda":
+            torch.cuda.synchronize()
+        return time.perf_counter()
+
+    t1 = clock()
+    inner = lanczos_block_smallest(fop, num_evals=want, block_size=int(block_size), eps=0.25 * float(eps), max_basis=max_basis,
+                                   max_restarts=INTERIOR_MAX_RESTARTS, seed=seed, verbose=verbose)
+    t_orth = clock() - t1 - fop.seconds
+    m = len(inner.eigenvectors)
+    Q = torch.stack(inner.eigenvectors)  # [m, n]: rows are vectors, as the solvers keep them
+    del inner.eigenvectors[:]
+    W = torch.empty_like(Q)
+    cplx = Q.is_complex()
+
+    def orthonormalise():
+        for _ in range(2):
+            G = (Q.conj() @ Q.t() if cplx else Q @ Q.t()).cpu().numpy()  # G[i, j] = <q_i|q_j>
+            R = np.linalg.cholesky(0.5 * (G + G.conj().T)).conj().T      # G = R^H R
+            Q.copy_(torch.as_tensor(np.linalg.inv(R).T, dtype=Q.dtype, device=Q.device) @ Q)
+
+    def rayleigh_ritz():
+        """Q <- the Ritz vectors of H in span Q (orthonormal rows), W <- H Q; -> (theta ascending, explicit residual norms)"""
+        for s in range(0, m, 64):
+            e = min(m, s + 64)
+            op.matvec_block(Q[s:e].t(), W[s:e].t())
+        Hs = (Q.conj() @ W.t() if cplx else Q @ W.t()).cpu().numpy()   # Hs[i, j] = <q_i|H q_j>
+        theta, S = np.linalg.eigh(0.5 * (Hs + Hs.conj().T))
+        St = torch.as_tensor(S.T, dtype=Q.dtype, device=Q.device)      # y_i = sum_j S[j, i] q_j
+        Q.copy_(St @ Q)
+        W.copy_(St @ W)
+        res = torch.empty(m, dtype=torch.float64, device=Q.device)
+        for i in range(m):
+            res[i] = torch.linalg.vector_norm(W[i] - float(theta[i]) * Q[i])
+        return theta, res.cpu().numpy()
+
+    polish = 0
+    while True:
+        t1 = clock()
+        orthonormalise()
+        theta, res = rayleigh_ritz()
+        op.check()
+        t_ritz += clock() - t1
+        near = np.sort(np.argsort(np.abs(theta - sigma), kind="stable")[:int(num_evals)])
+        done = bool(np.all(res[near] <= float(eps) * h_norm))
+        if verbose:
+            print(f"[interior] order {order}, polish {polish}: theta = {theta[near]}, residuals = {res[near]}", flush=True)
+        if done or polish >= int(max_polish):
+            break
+        for s in range(0, m, 64):
+            e = min(m, s + 64)
+            fop.matvec_block(Q[s:e].t(), W[s:e].t())
+        Q, W = W, Q
+        polish += 1
+    vecs = [Q[int(i)].clone() for i in near]
+    return InteriorResult([float(theta[i]) for i in near], vecs, [float(res[i]) for i in near], sigma, order, (lo, hi), fop.applications,
+                          int(op.matvecs - before), polish, done, time.perf_counter() - t0, fop.seconds, t_orth, t_ritz,
+                          int(inner.restarts),
+                          fop.block_kernel(int(block_size)))
+
+
 def diagonalize(config, num_evals: int = 1, eps: float = 1e-6, num_partitions: int = 1, dtype=None, output: str | None = None,
-                max_basis: int = 24, verbose: bool = False, block_size: int = 1):
+                max_basis: int = 24, verbose: bool = False, block_size: int = 1, sigma=None):
     """`Diagonalize.main` (Diagonalize.chpl:258-332) on one device: config (dict or YAML path) ->
     representatives (enumerated on the GPU; an existing HDF5 `output` that already holds basis/representatives is
     reused and extended, like makeBasisStates :227-246) ->
     eigenpairs; `output` (.npz) receives what the reference writes to its HDF5 groups:
     basis/representatives, hamiltonian/eigenvalues, hamiltonian/eigenvectors, hamiltonian/residuals.
     block_size (the reference's kMaxBlockSize, Diagonalize.chpl:172,192): 1 = lanczos_smallest; 2..16 = lanczos_block_smallest,
-    which finds degenerate levels with their multiplicity (up to block_size)."""
+    which finds degenerate levels with their multiplicity (up to block_size).
+    sigma: None, or a target energy: the num_evals levels NEAREST sigma (interior_eigenpairs with this block_size; one partition;
+    -> InteriorResult), written to the same datasets."""
     import os
 
     import numpy as np
@@ -559,10 +789,15 @@ def diagonalize(config, num_evals: int = 1, eps: float = 1e-6, num_partitions: i
 
     if isinstance(block_size, bool) or not isinstance(block_size, int) or not 1 <= block_size <= 16:
         raise ValueError(f"block_size = {block_size!r}: 1 <= block_size <= 16")
+    if sigma is not None and num_partitions != 1:
+        raise ValueError(f"diagonalize: sigma = {sigma!r} with num_partitions = {num_partitions}: interior eigenpairs "
+                         "(interior_eigenpairs) run on one partition")
     if isinstance(config, str):
         basis, h = api.loadConfigFromYaml(config, hamiltonian=True)
     else:
         basis, h = api.loadConfigFromDict(config, hamiltonian=True)
+    if sigma is not None and not h.isHermitian:
+        raise ValueError("diagonalize: the Hamiltonian is not Hermitian (sigma: the interior solver needs a real spectrum)")
     dtype = dtype or torch.float64
     reps = None
     if output and output.endswith((".h5", ".hdf5")) and num_partitions == 1:
@@ -594,7 +829,9 @@ def diagonalize(config, num_evals: int = 1, eps: float = 1e-6, num_partitions: i
         raise ValueError(f"block_size = {block_size} exceeds the dimension {n_total} of the basis")
     cache_bytes = 0
     # (LS_AMD_SLOT_CACHE has one meaning everywhere: bytes; 0 = off; set = the C plan applies it at creation, nothing to add here)
-    if num_partitions == 1 and os.environ.get("LS_AMD_SLOT_CACHE") is None:
+    if sigma is not None:
+        pass  # (the interior solver keeps three blocks of num_evals + guard vectors next to the Lanczos basis: it stays matrix-free)
+    elif num_partitions == 1 and os.environ.get("LS_AMD_SLOT_CACHE") is None:
         n_states = int(reps[0].numel())
         free, _total = torch.cuda.mem_get_info()
         if block_size == 1:
@@ -610,7 +847,9 @@ def diagonalize(config, num_evals: int = 1, eps: float = 1e-6, num_partitions: i
     op = LocalOperator(h, reps, dtype, slot_cache_bytes=cache_bytes)
     if verbose and op.cached_rows:
         print(f"[diagonalize] slot cache: {op.cached_rows} rows, {op.plan.slot_cache[1] / 1e9:.2f} GB", flush=True)
-    if block_size == 1:
+    if sigma is not None:
+        r = interior_eigenpairs(op, sigma, num_evals=num_evals, eps=eps, block_size=block_size, max_basis=max_basis, verbose=verbose)
+    elif block_size == 1:
         r = lanczos_smallest(op, num_evals=num_evals, eps=eps, max_basis=max_basis, verbose=verbose)
     else:
         r = lanczos_block_smallest(op, num_evals=num_evals, block_size=block_size, eps=eps, max_basis=max_basis, verbose=verbose)

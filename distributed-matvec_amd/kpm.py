@@ -146,6 +146,143 @@ def chebyshev_moments(op, start, num_moments: int, bounds) -> np.ndarray:
     return moments_from_dots(host, K, M)
 
 
+FILTER_CUT = 0.17    # filter_order: the levels wanted see p(E) >= cut p(sigma) (POLFED, PRL 125, 156601)
+
+
+def _bounds(bounds, who):
+    try:
+        lo, hi = float(bounds[0]), float(bounds[1])
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"{who}: bounds = {bounds!r}: need finite lo < hi") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+        raise ValueError(f"{who}: bounds = ({bounds[0]!r}, {bounds[1]!r}): need finite lo < hi")
+    return lo, hi
+
+
+def _scaled_sigma(sigma, lo, hi, who):
+    try:
+        sigma = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: sigma = {sigma!r} is not a number") from None
+    if not (math.isfinite(sigma) and lo < sigma < hi):
+        raise ValueError(f"{who}: sigma = {sigma!r} is not inside the bounds ({lo!r}, {hi!r}); the levels at the edges of the spectrum: "
+                         "diagonalize()")
+    return (sigma - 0.5 * (hi + lo)) / (0.5 * (hi - lo))
+
+
+def delta_filter(sigma: float, bounds, order: int) -> np.ndarray:
+    """c[0..order] of the Jackson-damped Chebyshev expansion of delta(x - s), x = (E - b) / a, s the scaled sigma:
+
+        p(x) = sum_n c_n T_n(x),    c_n = (2 - delta_n0) g_n cos(n arccos s) / (pi sqrt(1 - s^2)),
+
+    g_n = jackson_kernel(order + 1), the damping of `reconstruct`.  p is positive, peaks at s (to O(1 / order^2)), is close to a
+    Gaussian of width pi sqrt(1 - s^2) / order there, and its integral against the Chebyshev weight,
+    int p(x) sqrt(1 - s^2) / sqrt(1 - x^2) dx = g_0, is exactly 1.  A sigma outside the bounds is refused."""
+    lo, hi = _bounds(bounds, "delta_filter")
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order < 0:
+        raise ValueError(f"delta_filter: order = {order!r}: a non-negative integer")
+    s = _scaled_sigma(sigma, lo, hi, "delta_filter")
+    n = np.arange(int(order) + 1, dtype=np.float64)
+    c = 2.0 * jackson_kernel(int(order) + 1) * np.cos(n * math.acos(s)) / (math.pi * math.sqrt(1.0 - s * s))
+    c[0] *= 0.5
+    return c
+
+
+def _dos_at(op, sigma, bounds, num_moments=64, num_vectors=4, seed=0):
+    """rho(sigma), normalised to one level, from a few moments of a few random vectors (fixed seed)"""
+    start = random_phase_block(op.n_local, min(int(num_vectors), 64), op.dtype, seed, device=op.device)
+    mu = chebyshev_moments(op, start, num_moments, bounds)
+    return float(reconstruct(mu.sum(axis=0) / mu[:, 0].sum(), bounds, np.array([float(sigma)]))[0])
+
+
+def filter_order(num_states: int, dimension: int, dos_at_sigma=None, bounds=None, cut: float = FILTER_CUT, sigma=None, op=None) -> int:
+    """the order of delta_filter at which about `num_states` levels see p(E) >= cut p(sigma): the narrowest filter (the largest
+    order) that keeps the window of those levels above the cut.  The `num_states` levels nearest sigma fill the window
+    |E - sigma| <= num_states / (2 dimension dos_at_sigma) (dos_at_sigma: the density of states at sigma, normalised to ONE level,
+    per unit of energy); near its peak p is a Gaussian of width pi sqrt(1 - s^2) / order in x = (E - b) / a, so p >= cut p(sigma)
+    out to sqrt(2 ln(1 / cut)) widths: that estimate is the start, refined on the kernel's own values at the edges of the window
+    (an edge beyond the bounds does not count).  sigma None: the middle of the bounds.
+    dos_at_sigma None: from 64 moments of 4 random vectors of seed 0 on `op` (a diagonalize.LocalOperator).  At least 2."""
+    lo, hi = _bounds(bounds, "filter_order")
+    if isinstance(num_states, bool) or not isinstance(num_states, (int, np.integer)) or num_states < 1:
+        raise ValueError(f"filter_order: num_states = {num_states!r}: a positive integer")
+    if isinstance(dimension, bool) or not isinstance(dimension, (int, np.integer)) or dimension < 1:
+        raise ValueError(f"filter_order: dimension = {dimension!r}: a positive integer")
+    if not 0.0 < float(cut) < 1.0:
+        raise ValueError(f"filter_order: cut = {cut!r}: 0 < cut < 1")
+    s = 0.0 if sigma is None else _scaled_sigma(sigma, lo, hi, "filter_order")
+    if dos_at_sigma is None:
+        if op is None:
+            raise ValueError("filter_order: dos_at_sigma or op is needed")
+        dos_at_sigma = _dos_at(op, 0.5 * (lo + hi) if sigma is None else float(sigma), (lo, hi))
+    dos = float(dos_at_sigma)
+    if not (math.isfinite(dos) and dos > 0.0):
+        raise ValueError(f"filter_order: dos_at_sigma = {dos_at_sigma!r}: a positive number")
+    half_window = min(num_states / (2.0 * dimension * dos) / (0.5 * (hi - lo)), 2.0)  # in x; the whole band is 2 wide
+    guess = max(2, int(math.ceil(math.pi * math.sqrt(1.0 - s * s) * math.sqrt(2.0 * math.log(1.0 / float(cut))) / half_window)))
+    edges = np.array([x for x in (s - half_window, s + half_window) if -1.0 < x < 1.0])
+    if edges.size == 0:
+        return guess
+    # the Jackson kernel is a Gaussian only roughly (its ratio at the Gaussian's cut is some 10 % off): the estimate is refined on
+    # the kernel itself, by bisection -- the largest order at which both edges of the window still see the cut
+    theta, theta_s = np.arccos(edges), math.acos(s)
+
+    def keeps(order):
+        n = np.arange(order + 1, dtype=np.float64)
+        g = jackson_kernel(order + 1) * np.cos(n * theta_s)
+        g[1:] *= 2.0
+        peak = float(g @ np.cos(n * theta_s))
+        return bool(np.all(np.cos(theta[:, None] * n[None, :]) @ g >= float(cut) * peak))
+
+    if not keeps(2):
+        return 2
+    good, bad = 2, guess
+    while keeps(bad):
+        good, bad = bad, 2 * bad
+    while bad - good > 1:
+        mid = (good + bad) // 2
+        if keeps(mid):
+            good = mid
+        else:
+            bad = mid
+    return good
+
+
+def chebyshev_series(op, state, coefficients, bounds=None):
+    """sum_n c_n T_n((H - b) / a) state as a new device tensor: a vector, or an (n, K) block of K <= 64 states with any strides
+    (copied to the interleaved layout).  op: a diagonalize.LocalOperator on one partition over a Hermitian operator; bounds: (lo, hi)
+    enclosing its spectrum (spectral_bounds(op) when None).  Real coefficients keep the sum in op.dtype, complex ones make it
+    complex128.  One MatvecPlan.matvec_block_series: loop and growth guard run in C, one synchronisation per GUARD_EVERY orders;
+    bounds that do not enclose the spectrum raise LsAmdError."""
+    import torch
+
+    K = 1 if state.dim() == 1 else (int(state.shape[1]) if state.dim() == 2 else -1)
+    if K < 0:
+        raise LsAmdError(f"chebyshev_series: state {tuple(state.shape)} must be a vector or an (n, K) block")
+    if K > 64 or K < 1:
+        raise LsAmdError(f"chebyshev_series: K = {K} columns: 1 <= K <= 64")
+    if not op.plan.matrix.isHermitian:
+        raise ValueError("chebyshev_series: the operator is not Hermitian (a Chebyshev series needs a real spectrum)")
+    if len(op.sizes) != 1:
+        raise LsAmdError("chebyshev_series: one-partition plans only")
+    if state.is_complex() and op.dtype != torch.complex128:
+        raise LsAmdError("chebyshev_series: the state is complex and the operator computes in float64: build the operator with "
+                         "dtype=torch.complex128")
+    if state.shape[0] != op.n_local:
+        raise LsAmdError(f"chebyshev_series: state {tuple(state.shape)} must have {op.n_local} rows")
+    c = np.asarray(coefficients).reshape(-1)
+    if c.size < 1:
+        raise ValueError("chebyshev_series: no coefficients")
+    real = not np.iscomplexobj(c) or not np.any(c.imag != 0.0)
+    c = c.real.astype(np.float64) if real else c.astype(np.complex128)
+    bounds = _bounds(bounds if bounds is not None else spectral_bounds(op), "chebyshev_series")
+    X = state.reshape(op.n_local, K).to(op.dtype).contiguous()
+    Z = torch.empty((op.n_local, K), dtype=op.dtype if real else torch.complex128, device=X.device)
+    op.plan.matvec_block_series(X, Z, c, bounds)
+    op.matvecs += K * (len(c) - 1)
+    return Z.reshape(-1) if state.dim() == 1 else Z
+
+
 class _Negated:
     """-H through the operator interface of lanczos_smallest"""
 

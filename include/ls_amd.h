@@ -361,6 +361,24 @@ int ls_amd_block_axpby_acc(int cplx, int z_cplx, int64_t n, int K, void const *d
                            int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col, void *d_z, int64_t z_row,
                            int64_t z_col, double alpha, double beta, double gamma, double c_re, double c_im, double *d_dots,
                            void *stream);
+/* A whole Chebyshev series on a block (polynomial filters: distributed_matvec_amd.kpm.chebyshev_series, the interior eigensolver):
+ *     Z <- sum_{n = 0..N} c_n T_n((H - b) / a) X,    a = (hi - lo) / 2, b = (hi + lo) / 2,
+ * one ls_amd_matvec_block_axpby_acc per order (alpha = 1/a, beta = -b/a, gamma = 0 first; then 2/a, -2b/a, -1) between two work
+ * blocks that ping-pong.  X (any strides) is copied, not written; Z is ASSIGNED.  coeffs: N + 1 (re, im) pairs on the HOST.
+ * d_work: two blocks of n x K elements of the plan's type on the device, or NULL: the plan allocates them (and keeps them until
+ * it is destroyed or a larger K asks for more).  Element types (X, Z), the refusals, the paths and the environment are those of
+ * ls_amd_matvec_block_axpby_acc; refused in addition: N < 0, coeffs == NULL, an imaginary part next to an f64 Z, bounds that are
+ * not finite or not lo < hi, work that overlaps X or Z.
+ * The dots of every order land in a device array that is read back every 64 orders -- the only synchronisations of `stream`, the
+ * last one before the function returns -- for the guard <v_n|v_n> <= (1 + 1e-6) <v_0|v_0>: bounds that do not enclose the
+ * spectrum return non-zero with a message that names lo, hi and the order (Z is then undefined).
+ * A PRIMME matrixMatvec made of this call (the delta filter of kpm.delta_filter, negated) turns primme_smallest into the levels
+ * nearest a target energy: INTEGRATION.md. */
+int ls_amd_matvec_block_series(ls_amd_plan *plan, int K, int N, double const *coeffs, double lo, double hi,
+                               void const *d_x, int64_t x_row, int64_t x_col, void *d_z, int64_t z_row, int64_t z_col, int z_cplx,
+                               void *d_work, void *stream);
+/* the row path of every order: what ls_amd_plan_axpby_kernel_name returns ("k_direct_cheb", "k_pull_gather_cheb", "epilogue") */
+char const *ls_amd_plan_series_kernel_name(ls_amd_plan const *plan, int K);
 int ls_amd_plan_check(ls_amd_plan *plan, void *stream);
 
 /* ------------------------------------------------------------------------------------------
