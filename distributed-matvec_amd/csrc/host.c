@@ -4284,25 +4284,26 @@ char const *ls_amd_plan_block_kernel_name(ls_amd_plan const *pl, int K) {
     return g_blk_names[block_path(pl, K)];
 }
 
-/* K columns, one ls_amd_matvec each; y is cleared first (the single-vector paths accumulate when the operator has no diagonal) */
-static int block_columns(ls_amd_plan *pl, int K, char const *x, int64_t xr, int64_t xc, char *y, int64_t yr, int64_t yc, void *stream) {
-    int64_t const n = pl->parts[0].count;
-    size_t const w = pl->cplx ? 16 : 8;
-    if ((xr != 1 || yr != 1) && !pl->d_blk_cols && lsk_malloc(&pl->d_blk_cols, 2 * w * (size_t)n) != 0) return dev_error();
-    char *const col_x = (char *)pl->d_blk_cols, *const col_y = col_x ? col_x + w * (size_t)n : NULL;
-    for (int k = 0; k < K; ++k) {
-        void const *xin = x + (size_t)k * (size_t)xc * w;
-        void *yk = y + (size_t)k * (size_t)yc * w;
-        void *yout = yr == 1 ? yk : (void *)col_y;
-        if (xr != 1) {
-            DEV(lsk_copy_strided(n, (int)w, xin, xr, col_x, 1, stream));
-            xin = col_x;
-        }
-        DEV(lsk_memset_async(yout, 0, w * (size_t)n, stream));
-        if (ls_amd_matvec(pl, &xin, &yout, stream) != 0) return -1;
-        if (yr != 1) DEV(lsk_copy_strided(n, (int)w, col_y, 1, yk, yr, stream));
-    }
+/* what every entry point asks of an n x K block (element (i, k) at i * r + k * c): no two (i, k) on one element -- non-negative
+ * strides, one of the two nested in the other */
+static int block_strides(char const *who, int64_t n, int K, int64_t r, int64_t c, char const *name) {
+    int ok = r >= 0 && c >= 0;
+    if (ok && K > 1 && n > 1) ok = (c >= 1 && r >= c * K) || (r >= 1 && c >= r * n);
+    else if (ok && K > 1) ok = c >= 1;
+    else if (ok && n > 1) ok = r >= 1;
+    if (!ok)
+        return set_error("%s: strides (row %lld, column %lld) of %s make two elements of the %lld x %d block share "
+                         "storage (need non-negative strides with row >= K * column, or column >= N * row)", who, (long long)r,
+                         (long long)c, name, (long long)n, K);
     return 0;
+}
+/* whether the address ranges of two blocks of K columns meet; each block has its element width (the accumulator of the
+ * time-evolution step is c128 next to f64 vectors) and its number of rows (the two sectors of a cross-sector plan) */
+static int block_overlap(size_t wa, int64_t na, void const *a, int64_t ar, int64_t ac, size_t wb, int64_t nb, void const *b, int64_t br,
+                         int64_t bc, int K) {
+    uintptr_t const a0 = (uintptr_t)a, a1 = a0 + wa * (size_t)((na - 1) * ar + (int64_t)(K - 1) * ac + 1);
+    uintptr_t const b0 = (uintptr_t)b, b1 = b0 + wb * (size_t)((nb - 1) * br + (int64_t)(K - 1) * bc + 1);
+    return a0 < b1 && b0 < a1;
 }
 
 /* packet buffer of the projected block path: whole 256-row tiles, as many rows as LS_AMD_BLOCK_RESOLVE_BYTES (default 1 GiB) allow
@@ -4358,46 +4359,128 @@ static int block_tilemap(ls_amd_plan *pl, lsk_tilemap *tm) {
     return 0;
 }
 
-int ls_amd_matvec_block(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col,
-                        void *stream) {
-    if (!pl) return set_error("ls_amd_matvec_block: plan is NULL");
-    if (K < 1 || K > 64) return set_error("ls_amd_matvec_block: K = %d is outside [1, 64]", K);
+/* ---- one driver for the three block steps on a matvec plan ----
+ * ls_amd_matvec_block (STEP_PLAIN: Y <- H X), ls_amd_matvec_block_axpby (STEP_CHEB: Y <- alpha H X + beta X + gamma Y and two dots)
+ * and ls_amd_matvec_block_axpby_acc (STEP_ACC: that, and Z += c Y) walk a plan the same way; they differ in the launcher of each
+ * path, picked by step_direct / step_gather / step_column_tail below */
+enum { STEP_PLAIN = 0, STEP_CHEB = 1, STEP_ACC = 2 };
+typedef struct block_step {
+    int kind;
+    double alpha, beta, gamma;  /* STEP_CHEB, STEP_ACC */
+    double *d_dots;             /* [2K] or NULL */
+    char *z;                    /* STEP_ACC: the accumulator, its strides (in its own elements) and c */
+    int64_t z_row, z_col;
+    int z_cplx;
+    double c_re, c_im;
+} block_step;
+/* the X and Y of a call: K columns, strides in elements of the plan's dtype */
+typedef struct block_xy { int K; char const *x; int64_t xr, xc; char *y; int64_t yr, yc; } block_xy;
+
+/* the head of every block entry on a matvec plan: the number of rows, 0 where there are none (the dots, if any, cleared), -1 on error */
+static int64_t block_step_rows(char const *who, ls_amd_plan const *pl, int K, double *d_dots, void *stream) {
+    if (!pl) return set_error("%s: plan is NULL", who);
+    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
     if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1)
-        return set_error("ls_amd_matvec_block: one-partition plans only (this plan has P = %d, my_partition = %d)", pl->P, pl->me);
+        return set_error("%s: one-partition plans only (this plan has P = %d, my_partition = %d)", who, pl->P, pl->me);
     int64_t const n = pl->parts[0].count;
-    if (n <= 0) return 0;
-    if (!d_x || !d_y) return set_error("ls_amd_matvec_block: X or Y is NULL");
-    if (K == 1) { x_col = 0; y_col = 0; }
-    /* no two (i, k) on one element: non-negative strides, one of the two nested in the other */
-    int64_t const sr[2] = { x_row, y_row }, sc[2] = { x_col, y_col };
-    for (int v = 0; v < 2; ++v) {
-        int64_t const r = sr[v], c = sc[v];
-        int ok = r >= 0 && c >= 0;
-        if (ok && K > 1 && n > 1) ok = (c >= 1 && r >= c * K) || (r >= 1 && c >= r * n);
-        else if (ok && K > 1) ok = c >= 1;
-        else if (ok && n > 1) ok = r >= 1;
-        if (!ok)
-            return set_error("ls_amd_matvec_block: strides (row %lld, column %lld) of %s make two elements of the %lld x %d block share "
-                             "storage (need non-negative strides with row >= K * column, or column >= N * row)", (long long)r,
-                             (long long)c, v ? "Y" : "X", (long long)n, K);
-    }
+    if (n <= 0 && d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
+    return n > 0 ? n : 0;
+}
+static int block_xy_check(char const *who, ls_amd_plan const *pl, block_xy const *b) {
+    int64_t const n = pl->parts[0].count;
     size_t const w = pl->cplx ? 16 : 8;
-    uintptr_t const x0 = (uintptr_t)d_x, x1 = x0 + w * (size_t)((n - 1) * x_row + (int64_t)(K - 1) * x_col + 1);
-    uintptr_t const y0 = (uintptr_t)d_y, y1 = y0 + w * (size_t)((n - 1) * y_row + (int64_t)(K - 1) * y_col + 1);
-    if (x0 < y1 && y0 < x1) return set_error("ls_amd_matvec_block: X and Y overlap");
-    if (ls_amd_internal_check_y(pl, d_y) != 0) return -1;
-    int const path = block_path(pl, K);
-    if (path == BLK_COLUMNS) return block_columns(pl, K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col, stream);
+    if (block_strides(who, n, b->K, b->xr, b->xc, "X") != 0 || block_strides(who, n, b->K, b->yr, b->yc, "Y") != 0) return -1;
+    if (block_overlap(w, n, b->x, b->xr, b->xc, w, n, b->y, b->yr, b->yc, b->K)) return set_error("%s: X and Y overlap", who);
+    return 0;
+}
+
+static int step_direct(ls_amd_plan *pl, lsk_tilemap tm, block_xy const *b, block_step const *s, void *stream) {
+    part_state const *ps = &pl->parts[0];
+    /* (a non-Hermitian operator's partners outside the basis go to the word nobody reads, as in lsk_direct) */
+    int *const d_err = OEXT(pl->op)->is_hermitian ? pl->d_err : pl->d_err + 1;
+    switch (s->kind) {
+    case STEP_PLAIN:
+        return lsk_direct_blk(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, b->K, b->x, b->xr, b->xc, b->y, b->yr, b->yc, d_err, stream);
+    case STEP_CHEB:
+        return lsk_direct_cheb(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, b->K, b->x, b->xr, b->xc, b->y, b->yr, b->yc, s->alpha,
+                               s->beta, s->gamma, s->d_dots, d_err, stream);
+    default:
+        return lsk_direct_evolve(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, b->K, b->x, b->xr, b->xc, b->y, b->yr, b->yc, s->alpha,
+                                 s->beta, s->gamma, s->z, s->z_row, s->z_col, s->z_cplx, s->c_re, s->c_im, s->d_dots, d_err, stream);
+    }
+}
+/* rows [r0, r1) from the packet streams of pb; a STEP_CHEB / STEP_ACC launch adds its rows' share to the dots (and updates its
+ * own rows of Z) */
+static int step_gather(ls_amd_plan *pl, int64_t r0, int64_t r1, lsk_pullbuf pb, block_xy const *b, block_step const *s, void *stream) {
+    part_state const *ps = &pl->parts[0];
+    switch (s->kind) {
+    case STEP_PLAIN:
+        return lsk_pull_gather_blk(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, b->K, b->x, b->xr, b->xc, b->y, b->yr, b->yc,
+                                   stream);
+    case STEP_CHEB:
+        return lsk_pull_gather_cheb(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, b->K, b->x, b->xr, b->xc, b->y, b->yr, b->yc,
+                                    s->alpha, s->beta, s->gamma, s->d_dots, stream);
+    default:
+        return lsk_pull_gather_evolve(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, b->K, b->x, b->xr, b->xc, b->y, b->yr, b->yc,
+                                      s->alpha, s->beta, s->gamma, s->z, s->z_row, s->z_col, s->z_cplx, s->c_re, s->c_im, s->d_dots, stream);
+    }
+}
+/* column k of the column loop, after ls_amd_matvec left H X_k in col_w: STEP_PLAIN has Y_k there already (copied out where the rows
+ * of Y are strided); the fused steps finish Y_k (and Z_k) from it with the epilogue kernel, k_axpby_dots / k_axpby_acc */
+static int step_column_tail(ls_amd_plan *pl, int k, void const *col_w, block_xy const *b, block_step const *s, void *stream) {
+    int64_t const n = pl->parts[0].count;
+    size_t const w = pl->cplx ? 16 : 8;
+    void const *xk = b->x + (size_t)k * (size_t)b->xc * w;
+    void *yk = b->y + (size_t)k * (size_t)b->yc * w;
+    double *const xx = s->d_dots ? s->d_dots + k : NULL, *const xy = s->d_dots ? s->d_dots + b->K + k : NULL;
+    switch (s->kind) {
+    case STEP_PLAIN:
+        return b->yr != 1 ? lsk_copy_strided(n, (int)w, col_w, 1, yk, b->yr, stream) : 0;
+    case STEP_CHEB:
+        return lsk_axpby_dots(pl->cplx, n, 1, col_w, 1, 0, xk, b->xr, 0, yk, b->yr, 0, s->alpha, s->beta, s->gamma, xx, xy, stream);
+    default:
+        return lsk_axpby_acc(pl->cplx, n, 1, col_w, 1, 0, xk, b->xr, 0, yk, b->yr, 0, s->alpha, s->beta, s->gamma,
+                             s->z + (size_t)k * (size_t)s->z_col * (s->z_cplx ? 16 : 8), s->z_row, 0, s->z_cplx, s->c_re, s->c_im, xx, xy, stream);
+    }
+}
+
+/* the path of every plan without a block kernel (and of K = 1 under `auto`): K columns, one ls_amd_matvec each (it counts and
+ * times itself).  A strided column of X is gathered into one of the plan's two scratch columns; H X_k goes to the other, cleared
+ * first (the single-vector paths accumulate when the operator has no diagonal) -- or, in STEP_PLAIN with contiguous rows of Y,
+ * straight into Y_k, and then the scratch is only allocated where a row stride asks for it */
+static int block_step_columns(ls_amd_plan *pl, block_xy const *b, block_step const *s, void *stream) {
+    int64_t const n = pl->parts[0].count;
+    size_t const w = pl->cplx ? 16 : 8;
+    int const in_place = s->kind == STEP_PLAIN && b->yr == 1;
+    if ((s->kind != STEP_PLAIN || b->xr != 1 || b->yr != 1) && !pl->d_blk_cols && lsk_malloc(&pl->d_blk_cols, 2 * w * (size_t)n) != 0)
+        return dev_error();
+    char *const col_x = (char *)pl->d_blk_cols, *const col_w = col_x ? col_x + w * (size_t)n : NULL;
+    for (int k = 0; k < b->K; ++k) {
+        void const *xin = b->x + (size_t)k * (size_t)b->xc * w;
+        void *wout = in_place ? b->y + (size_t)k * (size_t)b->yc * w : col_w;
+        if (b->xr != 1) {
+            DEV(lsk_copy_strided(n, (int)w, xin, b->xr, col_x, 1, stream));
+            xin = col_x;
+        }
+        DEV(lsk_memset_async(wout, 0, w * (size_t)n, stream));
+        if (ls_amd_matvec(pl, &xin, &wout, stream) != 0) return -1;
+        DEV(step_column_tail(pl, k, col_w, b, s, stream));
+    }
+    return 0;
+}
+
+/* one step on the path block_path() chose, after the entry point's own checks */
+static int block_step_run(ls_amd_plan *pl, int path, block_xy const *b, block_step const *s, void *stream) {
+    if (path == BLK_COLUMNS) return block_step_columns(pl, b, s, stream);
     part_state *ps = &pl->parts[0];
+    int64_t const n = ps->count;
     ls_amd_internal_count_matvec(pl);
     if (path == BLK_DIRECT) {
         lsk_tilemap tm;
         if (block_tilemap(pl, &tm) != 0) return -1;
         int const st = stage_begin(pl, ST_ROWS, stream);
         int const slot = timing_begin(pl, stream);
-        /* (a non-Hermitian operator's partners outside the basis go to the word nobody reads, as in lsk_direct) */
-        DEV(lsk_direct_blk(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, K, d_x, x_row, x_col, d_y, y_row, y_col,
-                           OEXT(pl->op)->is_hermitian ? pl->d_err : pl->d_err + 1, stream));
+        DEV(step_direct(pl, tm, b, s, stream));
         timing_end(pl, slot, stream);
         stage_end(pl, st, stream);
         return 0;
@@ -4411,8 +4494,7 @@ int ls_amd_matvec_block(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, 
     int const slot = timing_begin(pl, stream);
     if (cached > 0) {
         int const st = stage_begin(pl, ST_ROWS, stream);
-        DEV(lsk_pull_gather_blk(pl->dop, pl->dbs, pl->cplx, 0, cached, ps->d_reps, ps->d_norms, pl->pbuf, K, d_x, x_row, x_col, d_y, y_row,
-                                y_col, stream));
+        DEV(step_gather(pl, 0, cached, pl->pbuf, b, s, stream));
         stage_end(pl, st, stream);
     }
     if (cached < n && block_pbuf(pl) != 0) return -1;
@@ -4425,12 +4507,25 @@ int ls_amd_matvec_block(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, 
                                   stream));
         stage_end(pl, st, stream);
         st = stage_begin(pl, ST_ROWS, stream);
-        DEV(lsk_pull_gather_blk(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, K, d_x, x_row, x_col, d_y, y_row, y_col,
-                                stream));
+        DEV(step_gather(pl, r0, r1, pb, b, s, stream));
         stage_end(pl, st, stream);
     }
     timing_end(pl, slot, stream);
     return 0;
+}
+
+int ls_amd_matvec_block(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col,
+                        void *stream) {
+    char const *const who = "ls_amd_matvec_block";
+    int64_t const n = block_step_rows(who, pl, K, NULL, stream);
+    if (n <= 0) return (int)n;
+    if (!d_x || !d_y) return set_error("%s: X or Y is NULL", who);
+    if (K == 1) { x_col = 0; y_col = 0; }
+    block_xy const b = { K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col };
+    if (block_xy_check(who, pl, &b) != 0) return -1;
+    if (ls_amd_internal_check_y(pl, d_y) != 0) return -1;
+    block_step const s = { .kind = STEP_PLAIN };
+    return block_step_run(pl, block_path(pl, K), &b, &s, stream);
 }
 
 /* ============================================================================================ */
@@ -4441,25 +4536,6 @@ char const *ls_amd_plan_axpby_kernel_name(ls_amd_plan const *pl, int K) {
     if (!pl) { set_error("ls_amd_plan_axpby_kernel_name: plan is NULL"); return NULL; }
     if (K < 1 || K > 64) { set_error("ls_amd_plan_axpby_kernel_name: K = %d is outside [1, 64]", K); return NULL; }
     return g_axpby_names[block_path(pl, K)];
-}
-
-/* no two (i, k) on one element: non-negative strides, one of the two nested in the other (the rule of ls_amd_matvec_block) */
-static int axpby_strides(char const *who, int64_t n, int K, int64_t r, int64_t c, char const *name) {
-    int ok = r >= 0 && c >= 0;
-    if (ok && K > 1 && n > 1) ok = (c >= 1 && r >= c * K) || (r >= 1 && c >= r * n);
-    else if (ok && K > 1) ok = c >= 1;
-    else if (ok && n > 1) ok = r >= 1;
-    if (!ok)
-        return set_error("%s: strides (row %lld, column %lld) of %s make two elements of the %lld x %d block share "
-                         "storage (need non-negative strides with row >= K * column, or column >= N * row)", who, (long long)r,
-                         (long long)c, name, (long long)n, K);
-    return 0;
-}
-/* (wa, wb: the element widths of the two blocks -- the accumulator of the time-evolution step is c128 next to f64 vectors) */
-static int axpby_overlap(size_t wa, size_t wb, int64_t n, int K, void const *a, int64_t ar, int64_t ac, void const *b, int64_t br, int64_t bc) {
-    uintptr_t const a0 = (uintptr_t)a, a1 = a0 + wa * (size_t)((n - 1) * ar + (int64_t)(K - 1) * ac + 1);
-    uintptr_t const b0 = (uintptr_t)b, b1 = b0 + wb * (size_t)((n - 1) * br + (int64_t)(K - 1) * bc + 1);
-    return a0 < b1 && b0 < a1;
 }
 
 int ls_amd_block_axpby_dots(int cplx, int64_t n, int K, void const *d_w, int64_t w_row, int64_t w_col, void const *d_x, int64_t x_row,
@@ -4474,106 +4550,31 @@ int ls_amd_block_axpby_dots(int cplx, int64_t n, int K, void const *d_w, int64_t
     }
     if (!d_w || !d_x || !d_y) return set_error("%s: W, X or Y is NULL", who);
     if (K == 1) { w_col = 0; x_col = 0; y_col = 0; }
-    if (axpby_strides(who, n, K, w_row, w_col, "W") != 0 || axpby_strides(who, n, K, x_row, x_col, "X") != 0 ||
-        axpby_strides(who, n, K, y_row, y_col, "Y") != 0)
+    if (block_strides(who, n, K, w_row, w_col, "W") != 0 || block_strides(who, n, K, x_row, x_col, "X") != 0 ||
+        block_strides(who, n, K, y_row, y_col, "Y") != 0)
         return -1;
     size_t const w = cplx ? 16 : 8;
-    if (axpby_overlap(w, w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
-    if (axpby_overlap(w, w, n, K, d_w, w_row, w_col, d_y, y_row, y_col)) return set_error("%s: W and Y overlap", who);
+    if (block_overlap(w, n, d_x, x_row, x_col, w, n, d_y, y_row, y_col, K)) return set_error("%s: X and Y overlap", who);
+    if (block_overlap(w, n, d_w, w_row, w_col, w, n, d_y, y_row, y_col, K)) return set_error("%s: W and Y overlap", who);
     if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
     DEV(lsk_axpby_dots(cplx != 0, n, K, d_w, w_row, w_col, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta, gamma, d_dots,
                        d_dots ? d_dots + K : NULL, stream));
     return 0;
 }
 
-/* the path of every plan without a block kernel (and of K = 1 under `auto`): column k through ls_amd_matvec into the plan's
- * one-column scratch (a strided column of X is gathered into the other scratch column first), then k_axpby_dots on that column */
-static int axpby_columns(ls_amd_plan *pl, int K, char const *x, int64_t xr, int64_t xc, char *y, int64_t yr, int64_t yc, double alpha,
-                         double beta, double gamma, double *d_dots, void *stream) {
-    int64_t const n = pl->parts[0].count;
-    size_t const w = pl->cplx ? 16 : 8;
-    if (!pl->d_blk_cols && lsk_malloc(&pl->d_blk_cols, 2 * w * (size_t)n) != 0) return dev_error();
-    char *const col_x = (char *)pl->d_blk_cols, *const col_w = col_x + w * (size_t)n;
-    for (int k = 0; k < K; ++k) {
-        void const *xk = x + (size_t)k * (size_t)xc * w;
-        void const *xin = xk;
-        void *wout = col_w;
-        if (xr != 1) {
-            DEV(lsk_copy_strided(n, (int)w, xk, xr, col_x, 1, stream));
-            xin = col_x;
-        }
-        DEV(lsk_memset_async(col_w, 0, w * (size_t)n, stream));
-        if (ls_amd_matvec(pl, &xin, &wout, stream) != 0) return -1;
-        DEV(lsk_axpby_dots(pl->cplx, n, 1, col_w, 1, 0, xk, xr, 0, y + (size_t)k * (size_t)yc * w, yr, 0, alpha, beta, gamma,
-                           d_dots ? d_dots + k : NULL, d_dots ? d_dots + K + k : NULL, stream));
-    }
-    return 0;
-}
-
 int ls_amd_matvec_block_axpby(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row,
                               int64_t y_col, double alpha, double beta, double gamma, double *d_dots, void *stream) {
     char const *const who = "ls_amd_matvec_block_axpby";
-    if (!pl) return set_error("%s: plan is NULL", who);
-    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
-    if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1)
-        return set_error("%s: one-partition plans only (this plan has P = %d, my_partition = %d)", who, pl->P, pl->me);
-    int64_t const n = pl->parts[0].count;
-    if (n <= 0) {
-        if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
-        return 0;
-    }
+    int64_t const n = block_step_rows(who, pl, K, d_dots, stream);
+    if (n <= 0) return (int)n;
     if (!d_x || !d_y) return set_error("%s: X or Y is NULL", who);
     if (K == 1) { x_col = 0; y_col = 0; }
-    if (axpby_strides(who, n, K, x_row, x_col, "X") != 0 || axpby_strides(who, n, K, y_row, y_col, "Y") != 0) return -1;
-    size_t const w = pl->cplx ? 16 : 8;
-    if (axpby_overlap(w, w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
+    block_xy const b = { K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col };
+    if (block_xy_check(who, pl, &b) != 0) return -1;
     if (ls_amd_internal_check_y(pl, d_y) != 0) return -1;
     if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
-    int const path = block_path(pl, K);
-    if (path == BLK_COLUMNS)
-        return axpby_columns(pl, K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col, alpha, beta, gamma, d_dots, stream);
-    part_state *ps = &pl->parts[0];
-    ls_amd_internal_count_matvec(pl);
-    if (path == BLK_DIRECT) {
-        lsk_tilemap tm;
-        if (block_tilemap(pl, &tm) != 0) return -1;
-        int const st = stage_begin(pl, ST_ROWS, stream);
-        int const slot = timing_begin(pl, stream);
-        DEV(lsk_direct_cheb(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, K, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta,
-                            gamma, d_dots, OEXT(pl->op)->is_hermitian ? pl->d_err : pl->d_err + 1, stream));
-        timing_end(pl, slot, stream);
-        stage_end(pl, st, stream);
-        return 0;
-    }
-    /* projected, indexed: slot-cache rows first, the others resolved chunk by chunk, exactly as ls_amd_matvec_block; every gather
-     * launch adds its rows' share to the dots */
-    lsk_pullidx ix;
-    memset(&ix, 0, sizeof(ix));
-    ix.tab = pl->gtab->tab;
-    int64_t const cached = pl->slot_cache && pl->slot_cache_valid ? pl->split_rows : 0;
-    int const slot = timing_begin(pl, stream);
-    if (cached > 0) {
-        int const st = stage_begin(pl, ST_ROWS, stream);
-        DEV(lsk_pull_gather_cheb(pl->dop, pl->dbs, pl->cplx, 0, cached, ps->d_reps, ps->d_norms, pl->pbuf, K, d_x, x_row, x_col, d_y, y_row,
-                                 y_col, alpha, beta, gamma, d_dots, stream));
-        stage_end(pl, st, stream);
-    }
-    if (cached < n && block_pbuf(pl) != 0) return -1;
-    for (int64_t r0 = cached; r0 < n; r0 += pl->blk_rows) {
-        int64_t const r1 = r0 + pl->blk_rows < n ? r0 + pl->blk_rows : n;
-        lsk_pullbuf pb = pl->blk_pbuf;
-        pb.row0 = r0;
-        int st = stage_begin(pl, ST_GENERATE, stream);
-        DEV(lsk_tile_pull_resolve(pl->dop, pl->dbs, r0, r1, ps->d_reps, ps->d_norms, ix, ps->d_reps, ps->count, pl->pull_halo, pb, pl->d_err,
-                                  stream));
-        stage_end(pl, st, stream);
-        st = stage_begin(pl, ST_ROWS, stream);
-        DEV(lsk_pull_gather_cheb(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, K, d_x, x_row, x_col, d_y, y_row, y_col,
-                                 alpha, beta, gamma, d_dots, stream));
-        stage_end(pl, st, stream);
-    }
-    timing_end(pl, slot, stream);
-    return 0;
+    block_step const s = { .kind = STEP_CHEB, .alpha = alpha, .beta = beta, .gamma = gamma, .d_dots = d_dots };
+    return block_step_run(pl, block_path(pl, K), &b, &s, stream);
 }
 
 /* ============================================================================================ */
@@ -4605,7 +4606,7 @@ static int acc_check_z(char const *who, int cplx, int z_cplx, int64_t n, int K, 
     if (!d_z) return set_error("%s: Z is NULL", who);
     if (cplx && !z_cplx) return set_error("%s: z_cplx = 0 with c128 vectors: Z must be c128 (an f64 accumulator cannot hold c Y)", who);
     if (!z_cplx && c_im != 0.0) return set_error("%s: z_cplx = 0 with c_im = %g: an f64 Z needs a real c", who, c_im);
-    return axpby_strides(who, n, K, z_row, z_col, "Z");
+    return block_strides(who, n, K, z_row, z_col, "Z");
 }
 
 int ls_amd_block_axpby_acc(int cplx, int z_cplx, int64_t n, int K, void const *d_w, int64_t w_row, int64_t w_col, void const *d_x,
@@ -4621,43 +4622,18 @@ int ls_amd_block_axpby_acc(int cplx, int z_cplx, int64_t n, int K, void const *d
     if (!d_w || !d_x || !d_y) return set_error("%s: W, X or Y is NULL", who);
     if (K == 1) { w_col = 0; x_col = 0; y_col = 0; z_col = 0; }
     if (acc_check_z(who, cplx != 0, z_cplx != 0, n, K, d_z, z_row, z_col, c_im) != 0) return -1;
-    if (axpby_strides(who, n, K, w_row, w_col, "W") != 0 || axpby_strides(who, n, K, x_row, x_col, "X") != 0 ||
-        axpby_strides(who, n, K, y_row, y_col, "Y") != 0)
+    if (block_strides(who, n, K, w_row, w_col, "W") != 0 || block_strides(who, n, K, x_row, x_col, "X") != 0 ||
+        block_strides(who, n, K, y_row, y_col, "Y") != 0)
         return -1;
     size_t const w = cplx ? 16 : 8, wz = z_cplx ? 16 : 8;
-    if (axpby_overlap(w, w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
-    if (axpby_overlap(w, w, n, K, d_w, w_row, w_col, d_y, y_row, y_col)) return set_error("%s: W and Y overlap", who);
-    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_y, y_row, y_col)) return set_error("%s: Z and Y overlap", who);
-    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_x, x_row, x_col)) return set_error("%s: Z and X overlap", who);
-    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_w, w_row, w_col)) return set_error("%s: Z and W overlap", who);
+    if (block_overlap(w, n, d_x, x_row, x_col, w, n, d_y, y_row, y_col, K)) return set_error("%s: X and Y overlap", who);
+    if (block_overlap(w, n, d_w, w_row, w_col, w, n, d_y, y_row, y_col, K)) return set_error("%s: W and Y overlap", who);
+    if (block_overlap(wz, n, d_z, z_row, z_col, w, n, d_y, y_row, y_col, K)) return set_error("%s: Z and Y overlap", who);
+    if (block_overlap(wz, n, d_z, z_row, z_col, w, n, d_x, x_row, x_col, K)) return set_error("%s: Z and X overlap", who);
+    if (block_overlap(wz, n, d_z, z_row, z_col, w, n, d_w, w_row, w_col, K)) return set_error("%s: Z and W overlap", who);
     if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
     DEV(lsk_axpby_acc(cplx != 0, n, K, d_w, w_row, w_col, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta, gamma, d_z, z_row, z_col,
                       z_cplx != 0, c_re, c_im, d_dots, d_dots ? d_dots + K : NULL, stream));
-    return 0;
-}
-
-/* axpby_columns with k_axpby_acc in place of k_axpby_dots: column k of Z is accumulated where column k of Y is finished */
-static int acc_columns(ls_amd_plan *pl, int K, char const *x, int64_t xr, int64_t xc, char *y, int64_t yr, int64_t yc, double alpha,
-                       double beta, double gamma, char *z, int64_t zr, int64_t zc, int z_cplx, double c_re, double c_im, double *d_dots,
-                       void *stream) {
-    int64_t const n = pl->parts[0].count;
-    size_t const w = pl->cplx ? 16 : 8, wz = z_cplx ? 16 : 8;
-    if (!pl->d_blk_cols && lsk_malloc(&pl->d_blk_cols, 2 * w * (size_t)n) != 0) return dev_error();
-    char *const col_x = (char *)pl->d_blk_cols, *const col_w = col_x + w * (size_t)n;
-    for (int k = 0; k < K; ++k) {
-        void const *xk = x + (size_t)k * (size_t)xc * w;
-        void const *xin = xk;
-        void *wout = col_w;
-        if (xr != 1) {
-            DEV(lsk_copy_strided(n, (int)w, xk, xr, col_x, 1, stream));
-            xin = col_x;
-        }
-        DEV(lsk_memset_async(col_w, 0, w * (size_t)n, stream));
-        if (ls_amd_matvec(pl, &xin, &wout, stream) != 0) return -1;
-        DEV(lsk_axpby_acc(pl->cplx, n, 1, col_w, 1, 0, xk, xr, 0, y + (size_t)k * (size_t)yc * w, yr, 0, alpha, beta, gamma,
-                          z + (size_t)k * (size_t)zc * wz, zr, 0, z_cplx, c_re, c_im, d_dots ? d_dots + k : NULL,
-                          d_dots ? d_dots + K + k : NULL, stream));
-    }
     return 0;
 }
 
@@ -4665,30 +4641,20 @@ int ls_amd_matvec_block_axpby_acc(ls_amd_plan *pl, int K, void const *d_x, int64
                                   int64_t y_col, double alpha, double beta, double gamma, void *d_z, int64_t z_row, int64_t z_col,
                                   int z_cplx, double c_re, double c_im, double *d_dots, void *stream) {
     char const *const who = "ls_amd_matvec_block_axpby_acc";
-    if (!pl) return set_error("%s: plan is NULL", who);
-    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
-    if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1)
-        return set_error("%s: one-partition plans only (this plan has P = %d, my_partition = %d)", who, pl->P, pl->me);
-    int64_t const n = pl->parts[0].count;
-    if (n <= 0) {
-        if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
-        return 0;
-    }
+    int64_t const n = block_step_rows(who, pl, K, d_dots, stream);
+    if (n <= 0) return (int)n;
     if (!d_x || !d_y) return set_error("%s: X or Y is NULL", who);
     if (K == 1) { x_col = 0; y_col = 0; z_col = 0; }
     z_cplx = z_cplx != 0;
     if (acc_check_z(who, pl->cplx, z_cplx, n, K, d_z, z_row, z_col, c_im) != 0) return -1;
-    if (axpby_strides(who, n, K, x_row, x_col, "X") != 0 || axpby_strides(who, n, K, y_row, y_col, "Y") != 0) return -1;
+    block_xy const b = { K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col };
+    if (block_xy_check(who, pl, &b) != 0) return -1;
     size_t const w = pl->cplx ? 16 : 8, wz = z_cplx ? 16 : 8;
-    if (axpby_overlap(w, w, n, K, d_x, x_row, x_col, d_y, y_row, y_col)) return set_error("%s: X and Y overlap", who);
-    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_y, y_row, y_col)) return set_error("%s: Z and Y overlap", who);
-    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_x, x_row, x_col)) return set_error("%s: Z and X overlap", who);
+    if (block_overlap(wz, n, d_z, z_row, z_col, w, n, d_y, y_row, y_col, K)) return set_error("%s: Z and Y overlap", who);
+    if (block_overlap(wz, n, d_z, z_row, z_col, w, n, d_x, x_row, x_col, K)) return set_error("%s: Z and X overlap", who);
     if (ls_amd_internal_check_y(pl, d_y) != 0) return -1;
     if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
     int const path = block_path(pl, K);
-    if (path == BLK_COLUMNS)
-        return acc_columns(pl, K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col, alpha, beta, gamma, (char *)d_z, z_row, z_col,
-                           z_cplx, c_re, c_im, d_dots, stream);
     if (acc_split(path)) {
         /* the Chebyshev kernel of the path, then Z += c Y in one streaming pass over the finished Y */
         if (ls_amd_matvec_block_axpby(pl, K, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta, gamma, d_dots, stream) != 0) return -1;
@@ -4696,49 +4662,9 @@ int ls_amd_matvec_block_axpby_acc(ls_amd_plan *pl, int K, void const *d_x, int64
                           NULL, stream));
         return 0;
     }
-    part_state *ps = &pl->parts[0];
-    ls_amd_internal_count_matvec(pl);
-    if (path == BLK_DIRECT) {
-        lsk_tilemap tm;
-        if (block_tilemap(pl, &tm) != 0) return -1;
-        int const st = stage_begin(pl, ST_ROWS, stream);
-        int const slot = timing_begin(pl, stream);
-        DEV(lsk_direct_evolve(pl->dop, pl->dbs, ps->index, pl->cplx, tm, ps->d_reps, K, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta,
-                              gamma, d_z, z_row, z_col, z_cplx, c_re, c_im, d_dots,
-                              OEXT(pl->op)->is_hermitian ? pl->d_err : pl->d_err + 1, stream));
-        timing_end(pl, slot, stream);
-        stage_end(pl, st, stream);
-        return 0;
-    }
-    /* projected, indexed: slot-cache rows first, the others resolved chunk by chunk, exactly as ls_amd_matvec_block_axpby; every
-     * gather launch updates its own rows of Z and adds its rows' share to the dots */
-    lsk_pullidx ix;
-    memset(&ix, 0, sizeof(ix));
-    ix.tab = pl->gtab->tab;
-    int64_t const cached = pl->slot_cache && pl->slot_cache_valid ? pl->split_rows : 0;
-    int const slot = timing_begin(pl, stream);
-    if (cached > 0) {
-        int const st = stage_begin(pl, ST_ROWS, stream);
-        DEV(lsk_pull_gather_evolve(pl->dop, pl->dbs, pl->cplx, 0, cached, ps->d_reps, ps->d_norms, pl->pbuf, K, d_x, x_row, x_col, d_y,
-                                   y_row, y_col, alpha, beta, gamma, d_z, z_row, z_col, z_cplx, c_re, c_im, d_dots, stream));
-        stage_end(pl, st, stream);
-    }
-    if (cached < n && block_pbuf(pl) != 0) return -1;
-    for (int64_t r0 = cached; r0 < n; r0 += pl->blk_rows) {
-        int64_t const r1 = r0 + pl->blk_rows < n ? r0 + pl->blk_rows : n;
-        lsk_pullbuf pb = pl->blk_pbuf;
-        pb.row0 = r0;
-        int st = stage_begin(pl, ST_GENERATE, stream);
-        DEV(lsk_tile_pull_resolve(pl->dop, pl->dbs, r0, r1, ps->d_reps, ps->d_norms, ix, ps->d_reps, ps->count, pl->pull_halo, pb, pl->d_err,
-                                  stream));
-        stage_end(pl, st, stream);
-        st = stage_begin(pl, ST_ROWS, stream);
-        DEV(lsk_pull_gather_evolve(pl->dop, pl->dbs, pl->cplx, r0, r1, ps->d_reps, ps->d_norms, pb, K, d_x, x_row, x_col, d_y, y_row, y_col,
-                                   alpha, beta, gamma, d_z, z_row, z_col, z_cplx, c_re, c_im, d_dots, stream));
-        stage_end(pl, st, stream);
-    }
-    timing_end(pl, slot, stream);
-    return 0;
+    block_step const s = { .kind = STEP_ACC, .alpha = alpha, .beta = beta, .gamma = gamma, .d_dots = d_dots, .z = (char *)d_z, .z_row = z_row,
+                           .z_col = z_col, .z_cplx = z_cplx, .c_re = c_re, .c_im = c_im };
+    return block_step_run(pl, path, &b, &s, stream);
 }
 
 /* ============================================================================================ */
@@ -4753,7 +4679,7 @@ char const *ls_amd_plan_series_kernel_name(ls_amd_plan const *pl, int K) {
     return g_axpby_names[block_path(pl, K)];
 }
 
-/* Z <- 0 for any strides axpby_strides lets through: one memset where the block is dense, else column by column (in slabs of rows)
+/* Z <- 0 for any strides block_strides lets through: one memset where the block is dense, else column by column (in slabs of rows)
  * out of `zeros`, zero_bytes of cleared device memory */
 static int series_clear(char *z, size_t wz, int64_t n, int K, int64_t zr, int64_t zc, void const *zeros, size_t zero_bytes, void *stream) {
     if ((n - 1) * zr + (int64_t)(K - 1) * zc + 1 == n * (int64_t)K) {
@@ -4773,10 +4699,8 @@ static int series_clear(char *z, size_t wz, int64_t n, int K, int64_t zr, int64_
 int ls_amd_matvec_block_series(ls_amd_plan *pl, int K, int N, double const *coeffs, double lo, double hi, void const *d_x, int64_t x_row,
                                int64_t x_col, void *d_z, int64_t z_row, int64_t z_col, int z_cplx, void *d_work, void *stream) {
     char const *const who = "ls_amd_matvec_block_series";
-    if (!pl) return set_error("%s: plan is NULL", who);
-    if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
-    if (pl->P != 1 || pl->me >= 0 || pl->n_local != 1)
-        return set_error("%s: one-partition plans only (this plan has P = %d, my_partition = %d)", who, pl->P, pl->me);
+    int64_t const n = block_step_rows(who, pl, K, NULL, stream);
+    if (n < 0) return -1;
     if (N < 0) return set_error("%s: N = %d is negative", who, N);
     if (!coeffs) return set_error("%s: coeffs is NULL", who);
     if (!(isfinite(lo) && isfinite(hi) && lo < hi)) return set_error("%s: bounds (%.17g, %.17g): need finite lo < hi", who, lo, hi);
@@ -4787,15 +4711,14 @@ int ls_amd_matvec_block_series(ls_amd_plan *pl, int K, int N, double const *coef
         if (!z_cplx && coeffs[2 * i + 1] != 0.0)
             return set_error("%s: z_cplx = 0 with Im coeffs[%d] = %g: an f64 Z needs real coefficients", who, i, coeffs[2 * i + 1]);
     }
-    int64_t const n = pl->parts[0].count;
-    if (n <= 0) return 0;
+    if (n == 0) return 0;
     if (!d_x) return set_error("%s: X is NULL", who);
     if (K == 1) { x_col = 0; z_col = 0; }
     if (acc_check_z(who, pl->cplx, z_cplx, n, K, d_z, z_row, z_col, 0.0) != 0) return -1;
-    if (axpby_strides(who, n, K, x_row, x_col, "X") != 0) return -1;
+    if (block_strides(who, n, K, x_row, x_col, "X") != 0) return -1;
     size_t const w = pl->cplx ? 16 : 8, wz = z_cplx ? 16 : 8;
     size_t const block = w * (size_t)n * (size_t)K;
-    if (axpby_overlap(wz, w, n, K, d_z, z_row, z_col, d_x, x_row, x_col)) return set_error("%s: Z and X overlap", who);
+    if (block_overlap(wz, n, d_z, z_row, z_col, w, n, d_x, x_row, x_col, K)) return set_error("%s: Z and X overlap", who);
     char *work = (char *)d_work;
     if (!work) {
         if (pl->d_series_work && pl->series_cols < K) {
@@ -4810,13 +4733,9 @@ int ls_amd_matvec_block_series(ls_amd_plan *pl, int K, int N, double const *coef
         }
         work = (char *)pl->d_series_work;
     }
-    {
-        uintptr_t const a0 = (uintptr_t)work, a1 = a0 + 2 * block;
-        uintptr_t const x0 = (uintptr_t)d_x, x1 = x0 + w * (size_t)((n - 1) * x_row + (int64_t)(K - 1) * x_col + 1);
-        uintptr_t const z0 = (uintptr_t)d_z, z1 = z0 + wz * (size_t)((n - 1) * z_row + (int64_t)(K - 1) * z_col + 1);
-        if (a0 < x1 && x0 < a1) return set_error("%s: work and X overlap", who);
-        if (a0 < z1 && z0 < a1) return set_error("%s: work and Z overlap", who);
-    }
+    /* (the work buffer: its two interleaved blocks as one of 2 n rows) */
+    if (block_overlap(w, 2 * n, work, K, 1, w, n, d_x, x_row, x_col, K)) return set_error("%s: work and X overlap", who);
+    if (block_overlap(w, 2 * n, work, K, 1, wz, n, d_z, z_row, z_col, K)) return set_error("%s: work and Z overlap", who);
     if (!pl->d_series_dots && lsk_malloc((void **)&pl->d_series_dots, sizeof(double) * SERIES_GUARD_EVERY * 128) != 0) return dev_error();
     double const a = 0.5 * (hi - lo), b = 0.5 * (hi + lo);
     /* the two work blocks in the interleaved layout (row stride K, column stride 1): cur = v_n, oth = v_{n-1}, overwritten by v_{n+1} */
@@ -5986,13 +5905,9 @@ int ls_amd_cross_apply_block(ls_amd_cross *cx, int K, void const *d_x, int64_t x
     if (nd == 0) return 0;
     if (!d_y || (!d_x && ns > 0)) return set_error("%s: NULL %s", who, !d_y ? "Y" : "X");
     if (K == 1) { x_col = 0; y_col = 0; }
-    if (axpby_strides(who, ns, K, x_row, x_col, "X") != 0 || axpby_strides(who, nd, K, y_row, y_col, "Y") != 0) return -1;
+    if (block_strides(who, ns, K, x_row, x_col, "X") != 0 || block_strides(who, nd, K, y_row, y_col, "Y") != 0) return -1;
     size_t const w = cx->cplx ? 16 : 8;
-    if (ns > 0) {
-        uintptr_t const x0 = (uintptr_t)d_x, x1 = x0 + w * (size_t)((ns - 1) * x_row + (int64_t)(K - 1) * x_col + 1);
-        uintptr_t const y0 = (uintptr_t)d_y, y1 = y0 + w * (size_t)((nd - 1) * y_row + (int64_t)(K - 1) * y_col + 1);
-        if (x0 < y1 && y0 < x1) return set_error("%s: X and Y overlap", who);
-    }
+    if (ns > 0 && block_overlap(w, ns, d_x, x_row, x_col, w, nd, d_y, y_row, y_col, K)) return set_error("%s: X and Y overlap", who);
     char *const y = (char *)d_y;
     if (cx->n_groups == 0 || ns == 0) { /* A = 0, or nothing to read: Y = 0 */
         if (y_col == 1 && y_row == K) { DEV(lsk_memset_async(y, 0, w * (size_t)nd * (size_t)K, stream)); return 0; }
@@ -7148,19 +7063,46 @@ char const *ls_amd_expect_kernel_name(ls_amd_expect const *pl) {
     return pl->bs.fermi ? lsk_expect_fermi_kernel_name() : lsk_expect_kernel_name();
 }
 
-int ls_amd_expect_values(ls_amd_expect *pl, ls_amd_dtype dtype, void const *d_psi, double *h_out, void *stream) {
-    char const *who = "ls_amd_expect_values";
-    if (!pl || !d_psi) return set_error("%s: NULL %s", who, !pl ? "plan" : "psi");
+/* ---- what ls_amd_expect_values, ls_amd_expect_values_block and ls_amd_expect_matrix_elements share ---- */
+/* a block of states handed to an entry point, as its messages name it */
+typedef struct expect_block { char const *name; int K; int64_t row, col; } expect_block;
+/* the checks behind the plan, the pointers and the numbers of columns: dtype, characters, output, then the strides of the nb blocks
+ * (all positive, then no two elements on one) */
+static int expect_check_args(char const *who, ls_amd_expect const *pl, ls_amd_dtype dtype, double const *h_out, expect_block const *blk,
+                             int nb) {
     if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
     if (dtype == LS_AMD_F64 && !pl->pm1) return set_error("%s: f64 needs +-1 characters (complex characters: use c128)", who);
     if (!h_out) return set_error("%s: NULL output", who);
-    int const cplx = dtype == LS_AMD_C128, nc = cplx ? 2 : 1;
-    for (int c = 0; c < pl->n_chunks; ++c) {
-        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
-        int const t0 = pl->h_groups[g0].begin, nt = pl->h_groups[g1 - 1].end - t0;
-        DEV(lsk_expect(pl->bs, pl->six, pl->gtab ? pl->gtab->tab : no_gtab(), pl->cons, g1 - g0, pl->d_groups + g0, pl->d_terms, t0, nt, cplx,
-                       pl->n, pl->d_reps, pl->d_norms, d_psi, pl->d_partial, pl->d_out + (size_t)t0 * nc, pl->d_err, stream));
-    }
+    for (int i = 0; i < nb; ++i)
+        if (blk[i].row <= 0 || blk[i].col <= 0)
+            return set_error("%s: strides (row %lld, column %lld) of %s must be positive", who, (long long)blk[i].row, (long long)blk[i].col,
+                             blk[i].name);
+    for (int i = 0; i < nb; ++i)
+        if (block_strides(who, pl->n, blk[i].K, blk[i].row, blk[i].col, blk[i].name) != 0) return -1;
+    return 0;
+}
+/* launch c of a plan: the groups [g0, g1) and their terms [t0, t0 + nt) */
+typedef struct expect_chunk { int g0, g1, t0, nt; } expect_chunk;
+static expect_chunk expect_chunk_of(ls_amd_expect const *pl, int c) {
+    int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1], t0 = pl->h_groups[g0].begin;
+    return (expect_chunk){ g0, g1, t0, pl->h_groups[g1 - 1].end - t0 };
+}
+/* a device buffer of at least `vals` 16-byte values and, where h is given, its host copy: freed and allocated anew by a call that
+ * needs more (*have: what they hold, 0 after a failure) */
+static int expect_grow(char const *who, double **d, double **h, size_t *have, size_t vals) {
+    if (vals <= *have) return 0;
+    if (*d) { lsk_free(*d); *d = NULL; }
+    if (h) { free(*h); *h = NULL; }
+    *have = 0;
+    void *p = NULL;
+    DEV(lsk_malloc(&p, 16 * vals));
+    *d = (double *)p;
+    if (h && !(*h = (double *)malloc(16 * vals))) return set_error("%s: out of host memory", who);
+    *have = vals;
+    return 0;
+}
+/* behind the launches of a call: wait for them and read the flag they raise (cleared again for the next call) */
+static int expect_finish_launches(ls_amd_expect *pl, void *stream) {
     int flag = 0, zero = 0;
     DEV(lsk_sync(stream));
     DEV(lsk_d2h(&flag, pl->d_err, sizeof(int)));
@@ -7170,6 +7112,20 @@ int ls_amd_expect_values(ls_amd_expect *pl, ls_amd_dtype dtype, void const *d_ps
                          "and is not in the basis (the array of representatives does not belong to this basis or is not the whole "
                          "sector: another Hamming weight, a truncated array)");
     }
+    return 0;
+}
+
+int ls_amd_expect_values(ls_amd_expect *pl, ls_amd_dtype dtype, void const *d_psi, double *h_out, void *stream) {
+    char const *who = "ls_amd_expect_values";
+    if (!pl || !d_psi) return set_error("%s: NULL %s", who, !pl ? "plan" : "psi");
+    if (expect_check_args(who, pl, dtype, h_out, NULL, 0) != 0) return -1;
+    int const cplx = dtype == LS_AMD_C128, nc = cplx ? 2 : 1;
+    for (int c = 0; c < pl->n_chunks; ++c) {
+        expect_chunk const ck = expect_chunk_of(pl, c);
+        DEV(lsk_expect(pl->bs, pl->six, pl->gtab ? pl->gtab->tab : no_gtab(), pl->cons, ck.g1 - ck.g0, pl->d_groups + ck.g0, pl->d_terms, ck.t0,
+                       ck.nt, cplx, pl->n, pl->d_reps, pl->d_norms, d_psi, pl->d_partial, pl->d_out + (size_t)ck.t0 * nc, pl->d_err, stream));
+    }
+    if (expect_finish_launches(pl, stream) != 0) return -1;
     if (pl->n_terms > 0) DEV(lsk_d2h(pl->h_out, pl->d_out, 8 * (size_t)pl->n_terms * nc));
     for (int k = 0; k < 2 * pl->n_ops; ++k) h_out[k] = 0.0;
     for (size_t i = 0; i < pl->n_comb; ++i) {
@@ -7205,56 +7161,34 @@ static int expect_block_cols(int nt, int K) {
 }
 
 static int expect_block_kernel(ls_amd_expect *pl, int cplx, int K, char const *psi, int64_t p_row, int64_t p_col, double *h_out, void *stream) {
+    char const *who = "ls_amd_expect_values_block";
     int const nc = cplx ? 2 : 1;
     size_t const w = 8 * (size_t)nc;
     /* the buffers of the block calls: allocated here, at the first call that needs them, and grown by a call with more columns */
     size_t part = 1;
     for (int c = 0; c < pl->n_chunks; ++c) {
-        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
-        size_t const nt = (size_t)(pl->h_groups[g1 - 1].end - pl->h_groups[g0].begin);
+        size_t const nt = (size_t)expect_chunk_of(pl, c).nt;
         size_t const v = nt * (size_t)expect_block_cols((int)nt, K);
         if (v > part) part = v;
     }
     part *= (size_t)lsk_corr_blocks(pl->n);
-    if (part > pl->blk_partial_vals) {
-        if (pl->d_blk_partial) { lsk_free(pl->d_blk_partial); pl->d_blk_partial = NULL; pl->blk_partial_vals = 0; }
-        void *p = NULL;
-        DEV(lsk_malloc(&p, 16 * part));
-        pl->d_blk_partial = (double *)p; pl->blk_partial_vals = part;
-    }
+    if (expect_grow(who, &pl->d_blk_partial, NULL, &pl->blk_partial_vals, part) != 0) return -1;
     size_t const vals = (size_t)(pl->n_terms > 0 ? pl->n_terms : 1) * (size_t)K;
-    if (vals > pl->blk_out_vals) {
-        if (pl->d_blk_out) { lsk_free(pl->d_blk_out); pl->d_blk_out = NULL; }
-        free(pl->h_blk_out); pl->h_blk_out = NULL; pl->blk_out_vals = 0;
-        void *p = NULL;
-        DEV(lsk_malloc(&p, 16 * vals));
-        pl->d_blk_out = (double *)p;
-        pl->h_blk_out = (double *)malloc(16 * vals);
-        if (!pl->h_blk_out) return set_error("ls_amd_expect_values_block: out of host memory");
-        pl->blk_out_vals = vals;
-    }
+    if (expect_grow(who, &pl->d_blk_out, &pl->h_blk_out, &pl->blk_out_vals, vals) != 0) return -1;
     /* the launches: per chunk of terms, per range of columns; a launch writes R[(u - t0) kl + (c - k0)] of its nt terms and kl
      * columns at (t0 K + nt k0) of d_blk_out */
     for (int c = 0; c < pl->n_chunks; ++c) {
-        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
-        int const t0 = pl->h_groups[g0].begin, nt = pl->h_groups[g1 - 1].end - t0;
+        expect_chunk const ck = expect_chunk_of(pl, c);
+        int const t0 = ck.t0, nt = ck.nt;
         int const cols = expect_block_cols(nt, K);
         for (int k0 = 0; k0 < K; k0 += cols) {
             int const kl = K - k0 < cols ? K - k0 : cols;
-            DEV(lsk_expect_blk(pl->bs, pl->six, pl->gtab ? pl->gtab->tab : no_gtab(), pl->cons, g1 - g0, pl->d_groups + g0, pl->d_terms, t0, nt,
-                               cplx, pl->n, pl->d_reps, pl->d_norms, kl, psi + (size_t)k0 * (size_t)p_col * w, p_row, p_col, pl->d_blk_partial,
-                               pl->d_blk_out + ((size_t)t0 * (size_t)K + (size_t)nt * (size_t)k0) * nc, pl->d_err, stream));
+            DEV(lsk_expect_blk(pl->bs, pl->six, pl->gtab ? pl->gtab->tab : no_gtab(), pl->cons, ck.g1 - ck.g0, pl->d_groups + ck.g0, pl->d_terms,
+                               t0, nt, cplx, pl->n, pl->d_reps, pl->d_norms, kl, psi + (size_t)k0 * (size_t)p_col * w, p_row, p_col,
+                               pl->d_blk_partial, pl->d_blk_out + ((size_t)t0 * (size_t)K + (size_t)nt * (size_t)k0) * nc, pl->d_err, stream));
         }
     }
-    int flag = 0, zero = 0;
-    DEV(lsk_sync(stream));
-    DEV(lsk_d2h(&flag, pl->d_err, sizeof(int)));
-    if (flag) {
-        DEV(lsk_h2d(pl->d_err, &zero, sizeof(int)));
-        return set_error("expectation values: the image of a representative under a term keeps the conserved numbers, has non-zero norm "
-                         "and is not in the basis (the array of representatives does not belong to this basis or is not the whole "
-                         "sector: another Hamming weight, a truncated array)");
-    }
+    if (expect_finish_launches(pl, stream) != 0) return -1;
     if (pl->n_terms > 0) DEV(lsk_d2h(pl->h_blk_out, pl->d_blk_out, w * (size_t)pl->n_terms * (size_t)K));
     for (int k = 0; k < 2 * pl->n_ops * K; ++k) h_out[k] = 0.0;
     /* value[k][c] = sum_u w[k][u] R[u][c]: the loop of ls_amd_expect_values per column (comb_u ascends: the chunk follows it) */
@@ -7262,7 +7196,7 @@ static int expect_block_kernel(ls_amd_expect *pl, int cplx, int K, char const *p
     for (size_t i = 0; i < pl->n_comb; ++i) {
         int const u = pl->comb_u[i];
         while (u >= pl->h_groups[pl->chunk_first[ch + 1] - 1].end) ++ch;
-        int const t0 = pl->h_groups[pl->chunk_first[ch]].begin, nt = pl->h_groups[pl->chunk_first[ch + 1] - 1].end - t0;
+        int const t0 = expect_chunk_of(pl, ch).t0, nt = expect_chunk_of(pl, ch).nt;
         int const cols = expect_block_cols(nt, K);
         double const wr = pl->comb_w[2 * i], wi = pl->comb_w[2 * i + 1];
         double *const o = h_out + 2 * (size_t)pl->comb_k[i] * (size_t)K;
@@ -7282,12 +7216,8 @@ int ls_amd_expect_values_block(ls_amd_expect *pl, ls_amd_dtype dtype, int K, voi
     char const *who = "ls_amd_expect_values_block";
     if (!pl || !d_psi) return set_error("%s: NULL %s", who, !pl ? "plan" : "block");
     if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
-    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
-    if (dtype == LS_AMD_F64 && !pl->pm1) return set_error("%s: f64 needs +-1 characters (complex characters: use c128)", who);
-    if (!h_out) return set_error("%s: NULL output", who);
-    if (row_stride <= 0 || col_stride <= 0)
-        return set_error("%s: strides (row %lld, column %lld) of the block must be positive", who, (long long)row_stride, (long long)col_stride);
-    if (axpby_strides(who, pl->n, K, row_stride, col_stride, "the block") != 0) return -1;
+    expect_block const blk = { "the block", K, row_stride, col_stride };
+    if (expect_check_args(who, pl, dtype, h_out, &blk, 1) != 0) return -1;
     int const cplx = dtype == LS_AMD_C128;
     size_t const w = cplx ? 16 : 8;
     char const *const psi = (char const *)d_psi;
@@ -7346,52 +7276,30 @@ int ls_amd_expect_matrix_elements(ls_amd_expect *pl, ls_amd_dtype dtype, int Ka,
     if (!pl || !d_bra || !d_ket) return set_error("%s: NULL %s", who, !pl ? "plan" : !d_bra ? "bra block" : "ket block");
     if (Ka < 1 || Ka > 64) return set_error("%s: Ka = %d is outside [1, 64]", who, Ka);
     if (Kb < 1 || Kb > 64) return set_error("%s: Kb = %d is outside [1, 64]", who, Kb);
-    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
-    if (dtype == LS_AMD_F64 && !pl->pm1) return set_error("%s: f64 needs +-1 characters (complex characters: use c128)", who);
-    if (!h_out) return set_error("%s: NULL output", who);
-    if (bra_row <= 0 || bra_col <= 0)
-        return set_error("%s: strides (row %lld, column %lld) of the bra block must be positive", who, (long long)bra_row, (long long)bra_col);
-    if (ket_row <= 0 || ket_col <= 0)
-        return set_error("%s: strides (row %lld, column %lld) of the ket block must be positive", who, (long long)ket_row, (long long)ket_col);
-    if (axpby_strides(who, pl->n, Ka, bra_row, bra_col, "the bra block") != 0) return -1;
-    if (axpby_strides(who, pl->n, Kb, ket_row, ket_col, "the ket block") != 0) return -1;
+    expect_block const blk[2] = { { "the bra block", Ka, bra_row, bra_col }, { "the ket block", Kb, ket_row, ket_col } };
+    if (expect_check_args(who, pl, dtype, h_out, blk, 2) != 0) return -1;
     int const cplx = dtype == LS_AMD_C128, nc = cplx ? 2 : 1;
     size_t const w = 8 * (size_t)nc;
     char const *const bra = (char const *)d_bra, *const ket = (char const *)d_ket;
     /* the buffers of the matrix calls: allocated here, at the first call, and grown by a call with more pairs of columns */
     size_t part = 1;
     for (int c = 0; c < pl->n_chunks; ++c) {
-        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
-        int const nt = pl->h_groups[g1 - 1].end - pl->h_groups[g0].begin;
+        int const nt = expect_chunk_of(pl, c).nt;
         int kal, kbl;
         expect_matrix_cols(nt, Ka, Kb, &kal, &kbl);
         size_t const v = (size_t)nt * (size_t)kal * (size_t)kbl;
         if (v > part) part = v;
     }
     part *= (size_t)lsk_corr_blocks(pl->n);
-    if (part > pl->mat_partial_vals) {
-        if (pl->d_mat_partial) { lsk_free(pl->d_mat_partial); pl->d_mat_partial = NULL; pl->mat_partial_vals = 0; }
-        void *p = NULL;
-        DEV(lsk_malloc(&p, 16 * part));
-        pl->d_mat_partial = (double *)p; pl->mat_partial_vals = part;
-    }
+    if (expect_grow(who, &pl->d_mat_partial, NULL, &pl->mat_partial_vals, part) != 0) return -1;
     size_t const pairs = (size_t)Ka * (size_t)Kb;
     size_t const vals = (size_t)(pl->n_terms > 0 ? pl->n_terms : 1) * pairs;
-    if (vals > pl->mat_out_vals) {
-        if (pl->d_mat_out) { lsk_free(pl->d_mat_out); pl->d_mat_out = NULL; }
-        free(pl->h_mat_out); pl->h_mat_out = NULL; pl->mat_out_vals = 0;
-        void *p = NULL;
-        DEV(lsk_malloc(&p, 16 * vals));
-        pl->d_mat_out = (double *)p;
-        pl->h_mat_out = (double *)malloc(16 * vals);
-        if (!pl->h_mat_out) return set_error("%s: out of host memory", who);
-        pl->mat_out_vals = vals;
-    }
+    if (expect_grow(who, &pl->d_mat_out, &pl->h_mat_out, &pl->mat_out_vals, vals) != 0) return -1;
     /* the launches: per chunk of terms, per range of bra columns, per range of ket columns; a launch writes
      * R[((u - t0) kla + (a - a0)) klb + (b - b0)] of its nt terms at expect_matrix_at() of d_mat_out */
     for (int c = 0; c < pl->n_chunks; ++c) {
-        int const g0 = pl->chunk_first[c], g1 = pl->chunk_first[c + 1];
-        int const t0 = pl->h_groups[g0].begin, nt = pl->h_groups[g1 - 1].end - t0;
+        expect_chunk const ck = expect_chunk_of(pl, c);
+        int const g0 = ck.g0, g1 = ck.g1, t0 = ck.t0, nt = ck.nt;
         int kal, kbl;
         expect_matrix_cols(nt, Ka, Kb, &kal, &kbl);
         for (int a0 = 0; a0 < Ka; a0 += kal) {
@@ -7405,15 +7313,7 @@ int ls_amd_expect_matrix_elements(ls_amd_expect *pl, ls_amd_dtype dtype, int Ka,
             }
         }
     }
-    int flag = 0, zero = 0;
-    DEV(lsk_sync(stream));
-    DEV(lsk_d2h(&flag, pl->d_err, sizeof(int)));
-    if (flag) {
-        DEV(lsk_h2d(pl->d_err, &zero, sizeof(int)));
-        return set_error("expectation values: the image of a representative under a term keeps the conserved numbers, has non-zero norm "
-                         "and is not in the basis (the array of representatives does not belong to this basis or is not the whole "
-                         "sector: another Hamming weight, a truncated array)");
-    }
+    if (expect_finish_launches(pl, stream) != 0) return -1;
     if (pl->n_terms > 0) DEV(lsk_d2h(pl->h_mat_out, pl->d_mat_out, w * (size_t)pl->n_terms * pairs));
     for (size_t k = 0; k < 2 * (size_t)pl->n_ops * pairs; ++k) h_out[k] = 0.0;
     /* value[k][a][b] = sum_u w[k][u] R[u][a][b]: the loop of ls_amd_expect_values per pair (comb_u ascends: the chunk follows it) */
@@ -7421,7 +7321,7 @@ int ls_amd_expect_matrix_elements(ls_amd_expect *pl, ls_amd_dtype dtype, int Ka,
     for (size_t i = 0; i < pl->n_comb; ++i) {
         int const u = pl->comb_u[i];
         while (u >= pl->h_groups[pl->chunk_first[ch + 1] - 1].end) ++ch;
-        int const t0 = pl->h_groups[pl->chunk_first[ch]].begin, nt = pl->h_groups[pl->chunk_first[ch + 1] - 1].end - t0;
+        int const t0 = expect_chunk_of(pl, ch).t0, nt = expect_chunk_of(pl, ch).nt;
         int kal, kbl;
         expect_matrix_cols(nt, Ka, Kb, &kal, &kbl);
         double const wr = pl->comb_w[2 * i], wi = pl->comb_w[2 * i + 1];

@@ -333,6 +333,17 @@ def test_block_refusals(torch):
         plan.apply_block(buf[:20].view(n1, 2), buf[10:26].view(n2, 2))
     with pytest.raises(D.LsAmdError, match="share storage"):
         plan.apply_block(mk(n1, 2), buf[:2].view(1, 2).expand(n2, 2))
+    # the two layouts every block entry refuses (tests/test_kpm_abi.py): row stride 1, column stride 1 at K = 4, of X and of Y ...
+    with pytest.raises(D.LsAmdError, match=r"share storage"):
+        plan.apply_block(torch.as_strided(buf, (n1, 4), (1, 1)), mk(n2, 4))
+    with pytest.raises(D.LsAmdError, match=r"strides \(row 1, column 1\) of Y make two elements of the 8 x 4 block share storage"):
+        plan.apply_block(mk(n1, 4), torch.as_strided(buf, (n2, 4), (1, 1)))
+    # ... and the interleaved halves of one buffer, whose address ranges overlap (n_src and n_dst rows: 10 and 8)
+    big = torch.zeros((n1, 8), dtype=c128, device="cuda")
+    with pytest.raises(D.LsAmdError, match="X and Y overlap"):
+        plan.apply_block(big[:, :4], big[:n2, 4:])
+    with pytest.raises(D.LsAmdError, match="X and Y overlap"):
+        plan.apply_block(big[:, 4:], big[:n2, :4])
     # ... and nothing of that left a flag or a broken plan behind
     x = _random_block(torch, n1, 2, c128, 1)
     y = _nan_block(torch, n2, 2, c128)

@@ -403,6 +403,15 @@ def test_two_partitions_and_bad_arguments_are_refused(torch):
     y = torch.zeros((n, 4), dtype=dtype, device="cuda")
     rc = L.ls_amd_matvec_block_axpby(pl.h, 4, C.c_void_p(x.data_ptr()), 1, 1, C.c_void_p(y.data_ptr()), 4, 1, 1.0, 0.0, 0.0, None, None)
     assert rc == -1 and "share" in L.ls_amd_last_error().decode()
+    # the two layouts every block entry refuses (tests/test_kpm_abi.py): row stride 1, column stride 1 at K = 4, of Y as of X above ...
+    rc = L.ls_amd_matvec_block_axpby(pl.h, 4, C.c_void_p(x.data_ptr()), 4, 1, C.c_void_p(y.data_ptr()), 1, 1, 1.0, 0.0, 0.0, None, None)
+    assert rc == -1 and "(row 1, column 1) of Y" in L.ls_amd_last_error().decode() and "share storage" in L.ls_amd_last_error().decode()
+    # ... and the interleaved halves of one buffer, whose address ranges overlap
+    big = torch.zeros((n, 8), dtype=dtype, device="cuda")
+    with pytest.raises(D.LsAmdError, match="X and Y overlap"):
+        pl.matvec_block_axpby(big[:, :4], big[:, 4:], 1.0, 0.0, 0.0)
+    with pytest.raises(D.LsAmdError, match="X and Y overlap"):
+        pl.matvec_block_axpby(big[:, 4:], big[:, :4], 1.0, 0.0, 0.0)
 
 
 def test_non_hermitian_hamiltonian_is_refused(torch):

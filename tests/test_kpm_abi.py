@@ -83,6 +83,30 @@ def test_epilogue_refuses_bad_strides_and_overlap_without_a_device():
     assert "NULL" in L.ls_amd_last_error().decode()
 
 
+def test_the_two_layouts_every_block_entry_refuses_without_a_device():
+    """row stride 1, column stride 1 at K = 4, and the interleaved halves of one buffer: the stride rule and the overlap rule are one
+    pair of helpers behind every block entry point, and these are the two cases their GPU tests ask of the entries that need a live
+    plan (ls_amd_matvec_block in test_gpu_block_matvec.py, ls_amd_matvec_block_axpby in test_gpu_kpm.py, ls_amd_cross_apply_block in
+    test_gpu_cross_block.py); here through the entry that needs none"""
+    L = _lib()
+    w = (C.c_double * 16)()
+    x = (C.c_double * 16)()
+    y = (C.c_double * 16)()
+    for which in range(3):
+        strides = [(4, 1), (4, 1), (4, 1)]
+        strides[which] = (1, 1)
+        (wr, wc), (xr, xc), (yr, yc) = strides
+        assert L.ls_amd_block_axpby_dots(0, 4, 4, _vp(w), wr, wc, _vp(x), xr, xc, _vp(y), yr, yc, 1.0, 0.0, 0.0, None, None) == -1
+        msg = L.ls_amd_last_error().decode()
+        assert "share storage" in msg and "(row 1, column 1)" in msg and f"of {'WXY'[which]} " in msg and "4 x 4 block" in msg, msg
+    big = (C.c_double * 32)()
+    second = C.c_void_p(C.addressof(big) + 4 * 8)  # X = big[:, :4], Y = big[:, 4:] of a 4 x 8 interleaved buffer
+    assert L.ls_amd_block_axpby_dots(0, 4, 4, _vp(w), 4, 1, _vp(big), 8, 1, second, 8, 1, 1.0, 0.0, 0.0, None, None) == -1
+    assert "X and Y overlap" in L.ls_amd_last_error().decode()
+    assert L.ls_amd_block_axpby_dots(0, 4, 4, _vp(big), 8, 1, _vp(x), 4, 1, second, 8, 1, 1.0, 0.0, 0.0, None, None) == -1
+    assert "W and Y overlap" in L.ls_amd_last_error().decode()
+
+
 def _stats():
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
