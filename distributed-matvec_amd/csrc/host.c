@@ -1757,6 +1757,14 @@ struct ls_amd_plan {
     uint64_t *d_chain_rec; /* fused records (lsk_chain_pack) replacing reps + the first cached pair */
     void *d_chain_wave;    /* 32-bit states and ranks: word table + one 8-byte header per 64 rows (setup_chain_headers); headed wave-rows do not read their records */
     int chain_row_bytes;   /* plan bytes per row the kernel streams with the headers, rounded up */
+    int chain_headed;      /* the wave headers are in use (not all ones) */
+    int chain_headers_apply; /* ... or would be without LS_AMD_CHAIN_RECORDS=1 */
+    /* paired tiles (setup_chain_pairs, lsk_chain_paired): tile map of the paired launch, headers of its second segments, rows between
+     * the two segments of a tile, first paired row; d_tilemap then covers the other rows only */
+    int chain_paired;
+    void *d_tilemap_pair, *d_chain_hdr_b;
+    lsk_tilemap tilemap_pair;
+    int64_t chain_pair_d, chain_pair_a0, chain_pair_rows;
     double chain_v[2];
     int64_t chain_row0; /* global rank of the first local row (replicated-x plans) */
     void *d_htab;        /* hash table {rep -> x * norm(rep)} of the tile-pull families */
@@ -2296,6 +2304,72 @@ static int tilemap_host(int64_t n, int TILE, int64_t chunk, uint64_t **out, int6
     *slots_out = slots;
     return 0;
 }
+/* Paired tiles of the chain kernel (k_chain_pair_t, lsk_chain_paired).  In the combinadic order of the weight-k words of L sites the
+ * rows whose two top bits are 01 are R01 = [C(L-2, k), C(L-1, k)), those with 10 the next d = C(L-2, k-1) rows, and rows R01 + j and
+ * R01 + d + j differ in those two bits only: bond L - 2 connects them.  [a0, a1) = the whole 512-row segments of R01; 0 when there is
+ * none (or the ranks leave 32 bits). */
+static int chain_pair_range(int L, int k, int64_t *a0, int64_t *a1, int64_t *d) {
+    if (L < 14 || L > 32 || k < 1 || k > L - 1) return 0;
+    uint64_t C[33][33];
+    memset(C, 0, sizeof(C));
+    for (int n = 0; n <= 32; ++n) { C[n][0] = 1; for (int j = 1; j <= n; ++j) C[n][j] = C[n - 1][j - 1] + (j <= n - 1 ? C[n - 1][j] : 0); }
+    int64_t const r01 = (int64_t)C[L - 2][k], r10 = (int64_t)C[L - 1][k];
+    *d = r10 - r01;
+    *a0 = (r01 + 511) & ~(int64_t)511;
+    *a1 = r10 & ~(int64_t)511;
+    return *a1 > *a0;
+}
+#define CHAIN_TILE_PLAIN 0x8000 /* bit 63 of a tile-map entry (k_chain_t on fused records): this tile runs on its records, not on wave headers */
+static int tilemap_deal(tile_list const *all, int64_t chunk, uint64_t **out, int64_t *slots_out) {
+    int64_t const tiles = all->n;
+    int64_t per[8] = {0, 0, 0, 0, 0, 0, 0, 0}, slots = 0;
+    if (chunk > 0) for (int64_t q = 0; q < tiles; ++q) ++per[(q / chunk) % 8];
+    else for (int k = 0; k < 8; ++k) per[k] = tiles * (k + 1) / 8 - tiles * k / 8; /* XCD k: the k-th contiguous eighth */
+    for (int k = 0; k < 8; ++k) if (per[k] > slots) slots = per[k];
+    uint64_t *flat = (uint64_t *)calloc((size_t)(8 * slots > 0 ? 8 * slots : 1), sizeof(uint64_t));
+    if (!flat) return set_error("out of memory");
+    int64_t fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int k0 = 0;
+    for (int64_t q = 0; q < tiles; ++q) {
+        int k;
+        if (chunk > 0) k = (int)((q / chunk) % 8);
+        else { while (q >= tiles * (k0 + 1) / 8) ++k0; k = k0; }
+        flat[k * slots + fill[k]++] = all->e[q];
+    }
+    *out = flat;
+    *slots_out = slots;
+    return 0;
+}
+/* The two tile maps of a paired plan: `pairs` = one entry per paired tile (first row of its first segment, 1024 rows), `rest` =
+ * tiles of at most TILE rows over [0, a0), [a1, a0 + d) and [a1 + d, n), cut at the multiples of TILE; a tile that starts or ends
+ * off the 64-row grid of the wave headers (the second segments do) is flagged CHAIN_TILE_PLAIN, and one that starts off it ends at
+ * the next multiple of 64.  Both are dealt like tilemap_host does.  Every row lies in exactly one tile of the two maps. */
+static int tilemap_paired_host(int64_t n, int TILE, int64_t chunk, int64_t a0, int64_t a1, int64_t d, uint64_t **rest, int64_t *rest_slots,
+                               uint64_t **pairs, int64_t *pair_slots) {
+    tile_list all[2];
+    memset(all, 0, sizeof(all));
+    int64_t const piece[3][2] = {{0, a0}, {a1, a0 + d}, {a1 + d, n}};
+    int64_t total = 0;
+    for (int p = 0; p < 3; ++p)
+        for (int64_t pos = piece[p][0]; pos < piece[p][1];) {
+            int64_t end = (pos / TILE + 1) * TILE;
+            if (pos & 63) end = (pos | 63) + 1;
+            if (end > piece[p][1]) end = piece[p][1];
+            int const plain = (pos & 63) != 0 || ((end & 63) != 0 && end != n);
+            tile_push(&all[0], pos, (end - pos) | (plain ? CHAIN_TILE_PLAIN : 0));
+            total += end - pos;
+            pos = end;
+        }
+    for (int64_t i0 = a0; i0 < a1; i0 += 512) { tile_push(&all[1], i0, 1024); total += 1024; }
+    int rc = total == n ? 0 : set_error("internal error: paired tile maps cover %lld of %lld rows", (long long)total, (long long)n);
+    *rest = *pairs = NULL;
+    if (!rc) rc = tilemap_deal(&all[0], chunk, rest, rest_slots);
+    if (!rc) rc = tilemap_deal(&all[1], chunk, pairs, pair_slots);
+    if (rc) { free(*rest); free(*pairs); *rest = *pairs = NULL; }
+    free(all[0].e);
+    free(all[1].e);
+    return rc;
+}
 static int build_tilemap(ls_amd_plan *pl, int64_t n, int TILE) {
     uint64_t *flat = NULL;
     int64_t slots = 0;
@@ -2350,6 +2424,18 @@ int64_t ls_amd_test_tilemap(int64_t n, int tile_rows, int64_t chunk, uint64_t **
     *entries = NULL;
     if (tilemap_host(n, tile_rows, chunk, entries, &slots) < 0) return -1;
     return slots;
+}
+/* test hook (host only): the two tile maps of the paired chain plan of the weight-`weight` words of L sites.  Returns 1 and fills
+ * everything, 0 when that basis has no whole paired segment (nothing is filled), < 0 on error.  out[0..4] = n, a0, a1, d, then the
+ * slots per XCD of `rest` and `pairs` in out[4], out[5]. */
+int ls_amd_test_tilemap_paired(int L, int weight, int tile_rows, int64_t chunk, uint64_t **rest, uint64_t **pairs, int64_t *out) {
+    int64_t a0, a1, d, n = 1;
+    *rest = *pairs = NULL;
+    if (!chain_pair_range(L, weight, &a0, &a1, &d)) return 0;
+    for (int j = 1; j <= weight; ++j) n = n * (L - weight + j) / j;
+    if (tilemap_paired_host(n, tile_rows, chunk, a0, a1, d, rest, &out[4], pairs, &out[5]) != 0) return -1;
+    out[0] = n; out[1] = a0; out[2] = a1; out[3] = d;
+    return 1;
 }
 void ls_amd_test_free(void *p) { free(p); }
 /* host-only test hooks of the static index table (lsk_gtab): shape for n keys of L bits, sequential build into a malloc'ed
@@ -2440,7 +2526,7 @@ int ls_amd_test_chain_wave_tables(int low_site, uint16_t *U, uint16_t *Rg, int *
 static int setup_chain_headers(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t const *d_reps, int nc, uint64_t xmask, void *stream) {
     int const L = NBITS(pl->op->basis);
     char const *e = getenv("LS_AMD_CHAIN_RECORDS");
-    int headed = !(e && atoi(e) != 0) && L >= 13 && L <= 32 && pl->dbs.proj == LSK_PROJ_NONE && pl->chain_row0 == 0 &&
+    int headed = L >= 13 && L <= 32 && pl->dbs.proj == LSK_PROJ_NONE && pl->chain_row0 == 0 &&
                  pl->family == FAMILY_DIRECT_PULL && pl->dbs.hamming_weight >= 0 && nc <= 1;
     int lo = -1, hi = -1;
     if (headed && nc == 1) {
@@ -2448,6 +2534,10 @@ static int setup_chain_headers(ls_amd_plan *pl, lsk_index index, int64_t n, uint
         hi = 63 - __builtin_clzll(xmask);
         if (lo >= 12 || hi < 12) { headed = 0; lo = hi = -1; }
     }
+    /* (the records switch leaves the shape of the plan alone: the tiles of a plan the headers serve are paired with or without them,
+     * setup_chain_pairs, so the two give the same y to the bit) */
+    pl->chain_headers_apply = headed;
+    if (e && atoi(e) != 0) { headed = 0; lo = hi = -1; }
     int const words = lsk_chain_words();
     int64_t const n_hdr = (n + 63) / 64;
     uint16_t U[4096], Rg[4096];
@@ -2468,10 +2558,67 @@ static int setup_chain_headers(ls_amd_plan *pl, lsk_index index, int64_t n, uint
     free(tab);
     if (rc) { lsk_free(q); return dev_error(); }
     pl->d_chain_wave = q;
+    pl->chain_headed = headed;
     /* plan bytes per row: 8 per wave-row + 64 rows of records (f64: 8 bytes; c128: the 4-byte state + 4 per cached pair) per
      * wave-row still on them, rounded up; all on records: theirs */
     int const rec = pl->cplx ? 4 + 4 * nc : 8;
     pl->chain_row_bytes = headed ? (int)((8 * (uint64_t)n_hdr + 64 * (uint64_t)rec * (uint64_t)plain + (uint64_t)n - 1) / (uint64_t)n) : rec;
+    return 0;
+}
+/* Paired tiles (k_chain_pair_t; chain_pair_range, tilemap_paired_host): f64 plans on fused records that the wave headers serve (in use,
+ * or all ones under LS_AMD_CHAIN_RECORDS=1: the second segments' headers follow; so: 13..32 sites, 32-bit ranks, one partition that starts at row 0, at most one cached pair) of >= 14 sites whose operator has bond
+ * L - 2 inside a run and whose basis holds a whole 512-row segment of R01.  The plan's tile map is rebuilt without the paired rows,
+ * which get a tile map and a launch of their own; the second segments get headers of their own (they lie off the 64-row grid).
+ * Every other plan, and every plan under LS_AMD_CHAIN_PAIRED=0 (A/B runs, tests), is left as it is.  hi = the cached pair's site
+ * >= 12 (< 0: none).  No room for the extra arrays: the plan stays unpaired. */
+static int setup_chain_pairs(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t const *d_reps, int hi, void *stream) {
+    char const *e = getenv("LS_AMD_CHAIN_PAIRED");
+    int const L = NBITS(pl->op->basis);
+    if ((e && atoi(e) == 0) || !pl->chain_headers_apply || pl->cplx || !pl->d_chain_rec || pl->chain_cached > 1 || pl->chain_row0 != 0 ||
+        pl->n_local != 1 || pl->family != FAMILY_DIRECT_PULL)
+        return 0;
+    int top = 0;
+    for (int q = 0; q < pl->dop.runs.n_runs; ++q)
+        if (pl->dop.runs.lo0[q] <= L - 2 && L - 2 < pl->dop.runs.lo0[q] + pl->dop.runs.cnt[q]) top = 1;
+    int64_t a0, a1, d;
+    if (!top || !chain_pair_range(L, pl->dbs.hamming_weight, &a0, &a1, &d) || a1 + d > n) return 0;
+    uint64_t *rest = NULL, *pairs = NULL;
+    int64_t rest_slots = 0, pair_slots = 0;
+    char const *ce = getenv("LS_AMD_TILE_CHUNK");
+    int64_t const chunk = ce ? atoll(ce) : 256; /* (build_tilemap's default for these tiles) */
+    if (tilemap_paired_host(n, lsk_chain_tile_rows(0), chunk > 0 ? chunk : 0, a0, a1, d, &rest, &rest_slots, &pairs, &pair_slots) != 0) return -1;
+    void *d_rest = NULL, *d_pairs = NULL, *d_hdr = NULL;
+    int64_t const n_b = a1 - a0; /* rows of the second segments: [a0 + d, a1 + d) */
+    unsigned long long plain = 0;
+    int rc = lsk_malloc(&d_rest, sizeof(uint64_t) * (size_t)(8 * rest_slots > 0 ? 8 * rest_slots : 1)) ||
+             lsk_malloc(&d_pairs, sizeof(uint64_t) * (size_t)(8 * pair_slots)) || lsk_malloc(&d_hdr, 8 * (size_t)(n_b / 64) + 8);
+    if (!rc) {
+        unsigned long long *d_plain = (unsigned long long *)((char *)d_hdr + 8 * (size_t)(n_b / 64));
+        rc = lsk_h2d(d_rest, rest, sizeof(uint64_t) * (size_t)(8 * rest_slots)) || lsk_h2d(d_pairs, pairs, sizeof(uint64_t) * (size_t)(8 * pair_slots)) ||
+             lsk_h2d(d_plain, &plain, 8) || lsk_chain_headers(pl->dbs, index, n_b, d_reps + a0 + d, pl->chain_headed, hi, d_hdr, d_plain, stream) ||
+             lsk_sync(stream);
+        if (rc) { free(rest); free(pairs); lsk_free(d_rest); lsk_free(d_pairs); lsk_free(d_hdr); return dev_error(); }
+    }
+    free(rest);
+    free(pairs);
+    if (rc) { /* no room */
+        if (d_rest) lsk_free(d_rest);
+        if (d_pairs) lsk_free(d_pairs);
+        if (d_hdr) lsk_free(d_hdr);
+        return 0;
+    }
+    lsk_free(pl->d_tilemap);
+    pl->d_tilemap = d_rest;
+    pl->tilemap.entries = (uint64_t const *)d_rest;
+    pl->tilemap.slots_per_xcd = rest_slots;
+    pl->d_tilemap_pair = d_pairs;
+    pl->tilemap_pair.entries = (uint64_t const *)d_pairs;
+    pl->tilemap_pair.slots_per_xcd = pair_slots;
+    pl->d_chain_hdr_b = d_hdr;
+    pl->chain_pair_d = d;
+    pl->chain_pair_a0 = a0;
+    pl->chain_pair_rows = 2 * (a1 - a0);
+    pl->chain_paired = 1;
     return 0;
 }
 /* tile map with 1024-row tiles + the cache of partner ranks of the exchange pairs outside the runs (for a ring: the
@@ -2564,6 +2711,7 @@ static int setup_chain(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t con
             pl->chain_cached = 0;
             return 0;
         }
+        if (setup_chain_pairs(pl, index, n, d_reps, pl->chain_cached > 0 ? 63 - __builtin_clzll(cx[0]) : -1, stream) != 0) return -1;
     }
     pl->has_chain = 1;
     return 0;
@@ -3523,6 +3671,8 @@ void ls_amd_plan_destroy(ls_amd_plan *pl) {
     if (pl->d_chain_cache) lsk_free(pl->d_chain_cache);
     if (pl->d_chain_rec) lsk_free(pl->d_chain_rec);
     if (pl->d_chain_wave) lsk_free(pl->d_chain_wave);
+    if (pl->d_tilemap_pair) lsk_free(pl->d_tilemap_pair);
+    if (pl->d_chain_hdr_b) lsk_free(pl->d_chain_hdr_b);
     if (pl->d_pair_recs) lsk_free(pl->d_pair_recs);
     for (int k = 0; k < 6; ++k) if (pl->d_hub[k]) lsk_free(pl->d_hub[k]);
     if (pl->d_pair_rows) lsk_free(pl->d_pair_rows);
@@ -3851,6 +4001,10 @@ int ls_amd_plan_row_bytes(ls_amd_plan const *pl) {
     if (pl->family == FAMILY_TILE_PULL || pl->family == FAMILY_REPL_TILE) return 16;
     return 8;
 }
+/* rows that the plan's paired launch computes (k_chain_pair_t, setup_chain_pairs); 0: the plan runs on k_chain_t alone, or not on it */
+int64_t ls_amd_plan_chain_paired_rows(ls_amd_plan const *pl) {
+    return pl->has_chain && pl->chain_paired ? pl->chain_pair_rows : 0;
+}
 int64_t ls_amd_plan_nnz(ls_amd_plan const *pl) { return pl->nnz; }
 int ls_amd_plan_send_counts(ls_amd_plan const *pl, int round, int64_t *counts) {
     if (pl->family != FAMILY_TILE) { for (int d = 0; d < pl->P; ++d) counts[d] = 0; return 0; }
@@ -4126,11 +4280,14 @@ int ls_amd_matvec(ls_amd_plan *pl, void const *const *d_x, void *const *d_y, voi
         part_state *ps = &pl->parts[0];
         int const st = stage_begin(pl, ST_ROWS, stream);
         int slot = timing_begin(pl, stream);
-        if (pl->has_chain)
+        if (pl->has_chain) {
             DEV(lsk_chain(pl->dop, pl->dbs, ps->index, pl->cplx, pl->chain_wide, pl->d_chain_rec != NULL, pl->tilemap, ps->count,
                           pl->d_chain_rec ? pl->d_chain_rec : ps->d_reps, 0, ps->count, d_x[0], d_y[0], pl->chain_cached,
                           pl->d_chain_cache, pl->chain_v[0], pl->chain_v[1], pl->d_chain_wave, stream));
-        else if (pl->has_pairs)
+            if (pl->chain_paired) /* the rows that tile map leaves out (setup_chain_pairs) */
+                DEV(lsk_chain_paired(pl->dop, pl->dbs, pl->tilemap_pair, ps->count, pl->d_chain_rec, d_x[0], d_y[0], pl->chain_cached, pl->chain_v[0],
+                                     pl->d_chain_wave, pl->chain_pair_d, pl->chain_pair_a0, pl->d_chain_hdr_b, NBITS(pl->op->basis) - 2, stream));
+        } else if (pl->has_pairs)
             DEV(lsk_pairs(pl->pairs, pl->dbs.hamming_weight, pl->cplx, pl->tilemap, ps->count, d_x[0], d_y[0], stream));
         else if (pl->has_hubbard)
             DEV(lsk_hubbard_apply(pl->hubbard, pl->dop, pl->cplx, pl->tilemap, d_x[0], d_y[0], stream));

@@ -666,6 +666,19 @@ extern "C" int lsk_direct_gx(lsk_operator op, lsk_basis bs, lsk_index ix, int cp
 // Measured on chain_32 f64 (gpurun_out/r2/ablate_sweep.log, pairs dropped from the top): streaming part 2.85 ms, the 12
 // LDS pairs +2.2 ms, pairs 12..19 +1.25 ms (mostly L2 hits), pairs 20..30 +3.1-3.75 ms (every gather misses the L2:
 // 27 GB at the fabric rate), the cached ring-closing pair +1.0-1.6 ms.
+//
+// Paired tiles (k_chain_pair_t; f64 on fused records with wave headers, >= 14 sites): in the combinadic order the rows whose two top
+// site bits are 01 are one contiguous range R01 and those with 10 the next one, both D = C(L-2, k-1) rows long, and bond L - 2 maps
+// row R01 + j onto row R01 + D + j.  A paired tile is 512 rows of R01 and their 512 partners: both are in the block's LDS anyway, so
+// that bond's partner is the row's own place in the other segment's core -- one LDS read instead of a far gather that always
+// misses the L2 (51.6 % of the rows of chain_32 have it).  LDS stays what it was: two windows of 512 + 2 x 256 (+ 2) rows are 2052
+// rows against 2050, the halo of 256 serves pairs 0..10, and pair 11 (partners up to 462 rows away) reads LDS when every partner of
+// the wave-row lies inside the window -- the rows of a wave move together, about half of the wave-rows -- and gathers otherwise (L1 /
+// L2 hits mostly).  The second segments lie off the 64-row grid of the wave headers (D mod 64 = 16 on chain_32) and have headers
+// of their own, made from their first row on.  The rows outside the whole 512-row segments of R01 and their partners stay with
+// k_chain_t, in a launch of its own; its tiles that start or end off the grid are flagged to run on their records.  Measured on
+// chain_32: 48.5 -> 46.9 GB per matvec and 2 % of its time (profiles/chain_paired_tiles_ab.txt); with pair 11 always gathered: no
+// gain.  Every term enters a row's sum where k_chain_t adds it, so the two kernels give the same y to the bit.
 // ---------------------------------------------------------------------------------------------
 constexpr int kChainHalo = 512;    // >= C(11, 5)
 constexpr int kChainLdsPairs = 12; // pairs lo < 12 are served from the LDS window
@@ -692,23 +705,31 @@ constexpr int kChainFarC = 6; // complex: 6 x 16 bytes in flight per lane
 // answers 7 -- a straggler round of blocks, measured +24 % (13.1 vs 10.7 ms on chain_32)
 // (f64: 7 blocks = what 22.5 KB of LDS admit; c128: bounds 4 / 5 / 6 measure 14.56 / 14.55 / 14.57 ms; the 64-bit f64
 // instantiations -- 33..64 sites, no in-tree config -- need 6: at 7 they spill 20-40 bytes per lane to scratch)
-template <typename W, typename R, bool CPLX, int TILE, bool REC>
-__global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) == 8 ? 6 : 7))) void k_chain_t(lsk_runs runs, int n_diag, lsk_term const *__restrict__ diag,
+// what a paired launch adds (PAIR, below): d = rows between the two segments of a tile, a0 = first row of the paired part of R01,
+// hdr_b = wave headers of the paired part of R10 (two u32 per 64 rows from its first row), bond = L - 2
+struct chain_pair_args { int64_t d, a0; uint32_t const *hdr_b; int bond; };
+template <typename W, typename R, bool CPLX, int TILE, bool REC, bool PAIR>
+__device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk_term const *__restrict__ diag,
                                                     int hamming_weight, uint4 const *__restrict__ g_img, int img16, int kc,
                                                     int near_off,
                                                     uint64_t const *__restrict__ tilemap, int64_t slots_per_xcd, int64_t n,
                                                     uint64_t const *__restrict__ reps, void const *__restrict__ x_v,
                                                     void *__restrict__ y_v, int n_cached,
                                                     R const *__restrict__ cache, double cv0, double cv1, int64_t row0,
-                                                    int64_t n_x, uint32_t const *__restrict__ wave_plan) {
+                                                    int64_t n_x, uint32_t const *__restrict__ wave_plan, chain_pair_args const &pr) {
     typedef typename ChainX<CPLX>::type X;
     typedef WordTraits<W> WT;
     constexpr int NB = ChainTraits<W, R>::NB;
     // complex vectors: 11 LDS pairs and a 256-row halo (>= C(10, 5)) keep the block at 20.7 KB like the f64 one, i.e. more
     // resident blocks per CU; pair 11 then gathers from global memory (its partners are <= 462 rows away: L1 / L2 hits)
-    constexpr int HALO = CPLX ? 256 : kChainHalo;
-    constexpr int LDSP = CPLX ? 11 : kChainLdsPairs;
-    constexpr int WINDOW = TILE + 2 * HALO + 2;
+    // PAIR (f64 on fused records only): a tile is two segments of SEG rows, D rows apart, each with a 256-row halo; the two windows
+    // lie one after the other in s_x (WSEG rows each, 2052 in all against 2050), and pair 11 gathers as in the complex kernel
+    constexpr int HALO = (CPLX || PAIR) ? 256 : kChainHalo;
+    constexpr int LDSP = (CPLX || PAIR) ? 11 : kChainLdsPairs;
+    constexpr int SEG = TILE / 2;
+    constexpr int WSEG = SEG + 2 * HALO + 2;
+    constexpr int WINDOW = PAIR ? 2 * WSEG : TILE + 2 * HALO + 2;
+    static_assert(!PAIR || (REC && !CPLX && SEG % kBlock == 0 && SEG % 64 == 0), "paired tiles: f64 on fused records");
     constexpr int FAR = CPLX ? kChainFarC : kChainFar;
     constexpr R kNone = ~(R)0;
     constexpr int hb = kChainLdsPairs; // pairs from here up are priced once per wave where its rows agree on them
@@ -747,10 +768,16 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
     constexpr int NSUB = TILE / kBlock;
     for (int64_t t = blockIdx.x >> 3; t < slots_per_xcd; t += blocks_per_xcd) {
         const uint64_t slot = tilemap[t];
-        const int cnt = (int)(slot >> 48);
-        if (cnt == 0) continue; // block-uniform
+        // (fused records: bits 59..63 of an entry are flags, kChainTilePlain = this tile starts or ends off the 64-row grid of the
+        // wave headers and runs on its records; a paired tile is always whole)
+        const int cnt_slot = REC ? (int)((slot >> 48) & 0x7ffu) : (int)(slot >> 48);
+        if (cnt_slot == 0) continue; // block-uniform
+        const int cnt = PAIR ? TILE : cnt_slot;
         const int64_t i0 = (int64_t)(slot & 0xffffffffffffULL);
         const int64_t w0 = (row0 + i0 - HALO) & ~(int64_t)1; // first row of the window (even; may be < 0)
+        const int64_t w0b = PAIR ? (i0 + pr.d - HALO) & ~(int64_t)1 : 0; // (paired tiles: of the second segment's window)
+        // row of the tile that this thread works on in iteration s, as an offset from i0
+        auto row_off = [&](int s) -> int { return PAIR ? (s >> 1) * (int)pr.d + (s & 1) * kBlock + (int)threadIdx.x : s * kBlock + threadIdx.x; };
         W a_next = 0;
         R t0_next = kNone, t1_next = kNone;
         // REC: `reps` is the plan's fused record array, row -> sigma (low word) | partner rank of the first cached pair
@@ -774,7 +801,14 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
         // the headers of this wave's NSUB wave-rows (tiles start at multiples of TILE): lane s holds word [0] of iteration s's,
         // lane NSUB + s its word [1] (the lanes from 2 NSUB on repeat them: no lane mask to keep)
         uint32_t hq = ~0u;
-        if (HDR) {
+        if (PAIR) {
+            // iterations 0-1 walk the first segment (today's headers), 2-3 the second, whose rows are D further on and off the
+            // 64-row grid: its headers were made from its own first row on (pr.hdr_b)
+            const uint32_t s = (uint32_t)lane % NSUB;
+            const uint32_t wr = (threadIdx.x >> 6) + (s & 1u) * (kBlock / 64);
+            const uint32_t word = ((uint32_t)lane / NSUB) % 2;
+            hq = (s >> 1) ? pr.hdr_b[2 * ((uint32_t)((i0 - pr.a0) >> 6) + wr) + word] : wave_plan[kChainWords + 2 * ((uint32_t)(i0 >> 6) + wr) + word];
+        } else if (HDR && !(REC && (slot >> 63))) {
             const uint32_t hw = 2 * (uint32_t)(i0 >> 6) + 2 * ((threadIdx.x >> 6) + (uint32_t)(lane % NSUB) * (kBlock / 64)) + (lane / NSUB) % 2;
             if (((int64_t)(hw >> 1) << 6) < n) hq = wave_plan[kChainWords + hw];
         }
@@ -800,7 +834,7 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
             double const *xd = (double const *)x_v;
             double *sd = (double *)s_x;
             for (int j = 2 * threadIdx.x; j < WINDOW; j += 2 * kBlock) {
-                const int64_t row = w0 + j;
+                const int64_t row = (PAIR && j >= WSEG) ? w0b + (j - WSEG) : w0 + j; // (WSEG is even: a pair of rows stays in its window)
                 double2 v;
                 if (row >= 0 && row + 1 < n_x) v = *reinterpret_cast<double2 const *>(xd + row);
                 else { v.x = (row >= 0 && row < n_x) ? xd[row] : 0.0; v.y = (row + 1 >= 0 && row + 1 < n_x) ? xd[row + 1] : 0.0; }
@@ -810,23 +844,26 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
         }
         __syncthreads();
         const int own0 = (int)(row0 + i0 - w0);
+        const int own0b = PAIR ? WSEG + (int)(i0 + pr.d - w0b) : 0; // first row of the second segment in s_x
         X y_pending = cx_zero<X>(); // stored one iteration late (see k_chain)
         int r_pending = -1;         // (row of the tile: one register, not two)
 #pragma unroll 1
         for (int sub = 0; sub < TILE / kBlock; ++sub) {
-            const int r = sub * kBlock + threadIdx.x;
+            const int r = row_off(sub);
             if (r_pending >= 0) cx_store_nt(y + i0 + r_pending, y_pending);
             r_pending = -1;
             W a = a_next;
             R t0 = t0_next;
             const R t1 = t1_next;
             const uint64_t ex = ex_next;
-            if (sub + 1 < TILE / kBlock && (sub + 1) * kBlock + wave0 < cnt) {
+            if (PAIR) {
+                if (sub + 1 < TILE / kBlock) fetch_row(sub + 1, i0 + row_off(sub + 1));
+            } else if (sub + 1 < TILE / kBlock && (sub + 1) * kBlock + wave0 < cnt) {
                 const int64_t in = i0 + (r + kBlock < cnt ? r + kBlock : cnt - 1);
                 fetch_row(sub + 1, in);
             }
-            if (sub * kBlock + wave0 >= cnt) continue; // wave-uniform: the whole wave is past the end
-            const bool ghost = r >= cnt;
+            if (!PAIR && sub * kBlock + wave0 >= cnt) continue; // wave-uniform: the whole wave is past the end
+            const bool ghost = !PAIR && r >= cnt;
             const int64_t i = i0 + (ghost ? cnt - 1 : r);
             const R ig = (R)(row0 + i);
             // The rows of a wave ascend, so every lane shares the common prefix of the first and the last state: pairs at or
@@ -849,7 +886,10 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
                 const W adiff = a0 ^ readlane_t<W>(a, 63);
                 ubit = adiff == 0 ? 0 : (int)(8 * sizeof(W)) - (sizeof(W) == 4 ? __clz((int)(uint32_t)adiff) : __clzll((long long)(uint64_t)adiff));
             }
-            const int jr = own0 + (int)(i - i0);
+            // (paired tiles: jp = this row's place in the OTHER segment's core, where its partner across bond L - 2 lies)
+            const int jl = PAIR ? (sub & 1) * kBlock + (int)threadIdx.x : 0;
+            const int jr = PAIR ? ((sub >> 1) ? own0b : own0) + jl : own0 + (int)(i - i0);
+            const int jp = PAIR ? ((sub >> 1) ? own0 : own0b) + jl : 0;
             const X xr = s_x[jr];
             // cached pairs: only the anti-aligned lanes gather (the aligned ones multiply their own x by zero, as ever)
             X g0 = n_cached > 0 ? xr : cx_zero<X>(), g1 = n_cached > 1 ? xr : cx_zero<X>();
@@ -865,6 +905,7 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
                 const int lo0 = runs.lo0[q];
                 int lo_end = lo0 + runs.cnt[q];
                 const double vr = runs.v_re[q];
+                const bool top_here = PAIR && lo0 <= pr.bond && pr.bond < lo_end; // the run of bond L - 2
                 int k = WT::popc(a & (W)(((uint64_t)1 << lo0) - 1));
                 int lo = lo0;
                 const int e1 = lo_end < LDSP ? lo_end : LDSP;
@@ -885,7 +926,9 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
                     const int ps = in_run ? p : 0;
                     const W hi = a0 >> ps;
                     const bool bit = hi & 1;
-                    const bool act = in_run && (((hi >> 1) & 1) != (W)bit);
+                    // (paired tiles: bond L - 2 is anti-aligned in every row and is served from LDS below; the two top bits are
+                    // the same in all rows of a segment, so that bond is always among these wave-uniform ones)
+                    const bool act = in_run && (((hi >> 1) & 1) != (W)bit) && !(PAIR && p == pr.bond);
                     const int kk = hamming_weight - WT::popc(hi); // set bits below p
                     const R d = s_binom[ps * kc + (kk < 0 ? 0 : kk)];
                     off = bit ? d : (R)(0 - d);
@@ -947,6 +990,23 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
                     const int j = bit ? jr + d : jr - d;
                     cx_fma(vr, s_x[act ? j : WINDOW], acc);
                 }
+                if (PAIR && lo == LDSP && lo < lo_end) {
+                    // pair 11 of a paired tile: its partners lie up to 462 rows away, the halo is 256 -- but the rows of a wave move
+                    // together, so for about half of the wave-rows every partner is inside the segment's window: those read LDS
+                    const bool bit = (a >> LDSP) & 1;
+                    const bool act = (tdiff >> LDSP) & 1;
+                    const int d = (int)s_binom[LDSP * kc + k];
+                    const int j = bit ? jr + d : jr - d;
+                    const int sb = (sub >> 1) * WSEG;
+                    if (__builtin_amdgcn_ballot_w64(act && (j < sb || j >= sb + WSEG)) == 0)
+                        cx_fma(vr, s_x[act ? j : WINDOW], acc);
+                    else { // (here, not in the middle loop: the terms enter the sum in k_chain_t's order, so y is the same to the bit)
+                        const R idx = act ? (bit ? (R)(ig + (R)d) : (R)(ig - (R)d)) : ig;
+                        cx_fma(act ? vr : 0.0, x[idx], acc);
+                    }
+                    k += bit ? 1 : 0;
+                    ++lo;
+                }
 #pragma unroll
                 for (int u = 0; u < FAR; ++u) cx_fma(vr, xv[u], acc); // zero-filled slots included: counting the gathers and
                                                                       // branching around idle fmas measured slower (7.72 vs 7.59 ms)
@@ -964,6 +1024,7 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
 #pragma unroll
                     for (int u = 0; u < 4; ++u) cx_fma(vr, xw[u], acc);
                 }
+                if (top_here) cx_fma(vr, s_x[jp], acc); // (block-uniform; bond L - 2 is the last far pair of its run: k_chain_t's order)
                 // ---- middle pairs (and far pairs of a wave that straddles two high parts) --------------
 #pragma unroll 4
                 for (; lo < lo_end; ++lo) {
@@ -984,6 +1045,29 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
         }
         if (r_pending >= 0) cx_store_nt(y + i0 + r_pending, y_pending);
     }
+}
+template <typename W, typename R, bool CPLX, int TILE, bool REC>
+__global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) == 8 ? 6 : 7))) void k_chain_t(lsk_runs runs, int n_diag, lsk_term const *__restrict__ diag,
+                                                    int hamming_weight, uint4 const *__restrict__ g_img, int img16, int kc,
+                                                    int near_off,
+                                                    uint64_t const *__restrict__ tilemap, int64_t slots_per_xcd, int64_t n,
+                                                    uint64_t const *__restrict__ reps, void const *__restrict__ x_v,
+                                                    void *__restrict__ y_v, int n_cached,
+                                                    R const *__restrict__ cache, double cv0, double cv1, int64_t row0,
+                                                    int64_t n_x, uint32_t const *__restrict__ wave_plan) {
+    chain_rows<W, R, CPLX, TILE, REC, false>(runs, n_diag, diag, hamming_weight, g_img, img16, kc, near_off, tilemap, slots_per_xcd, n, reps, x_v, y_v,
+                                             n_cached, cache, cv0, cv1, row0, n_x, wave_plan, chain_pair_args{0, 0, nullptr, -1});
+}
+// The paired launch of the headline shape (32-bit states and ranks, f64, fused records + wave headers, one cached pair at most, the
+// whole basis in one partition): the same rows body over tiles of two 512-row segments that bond L - 2 maps onto each other.
+__global__ __launch_bounds__(kBlock, 7) void k_chain_pair_t(lsk_runs runs, int n_diag, lsk_term const *__restrict__ diag, int hamming_weight,
+                                                            uint4 const *__restrict__ g_img, int img16, int kc, int near_off,
+                                                            uint64_t const *__restrict__ tilemap, int64_t slots_per_xcd, int64_t n,
+                                                            uint64_t const *__restrict__ reps, void const *__restrict__ x_v,
+                                                            void *__restrict__ y_v, int n_cached, double cv0, chain_pair_args pr,
+                                                            uint32_t const *__restrict__ wave_plan) {
+    chain_rows<uint32_t, uint32_t, false, 1024, true, true>(runs, n_diag, diag, hamming_weight, g_img, img16, kc, near_off, tilemap, slots_per_xcd, n,
+                                                            reps, x_v, y_v, n_cached, nullptr, cv0, 0.0, 0, n, wave_plan, pr);
 }
 
 // cache[i] = rank of reps[i] ^ xmask when exactly one of the two bits of xmask is set in reps[i], else ~0;
@@ -1216,6 +1300,23 @@ extern "C" int lsk_chain(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, 
     if (!wide_ranks) return cplx ? launch_chain<uint64_t, uint32_t, true, 512, false>(LSK_CHAIN_ARGS) : launch_chain<uint64_t, uint32_t, false, 1024, false>(LSK_CHAIN_ARGS);
     return cplx ? launch_chain<uint64_t, uint64_t, true, 512, false>(LSK_CHAIN_ARGS) : launch_chain<uint64_t, uint64_t, false, 1024, false>(LSK_CHAIN_ARGS);
 #undef LSK_CHAIN_ARGS
+}
+extern "C" int lsk_chain_paired(lsk_operator op, lsk_basis bs, lsk_tilemap tm_pair, int64_t n, uint64_t const *records, void const *x, void *y,
+                                int n_cached, double cv0, void const *wave_plan, int64_t d, int64_t a0, void const *hdr_b, int bond, void *stream) {
+    if (n == 0 || tm_pair.slots_per_xcd == 0) return 0;
+    if (bs.number_sites < 14 || bs.number_sites > 32 || bond != bs.number_sites - 2 || n_cached > 1 || !wave_plan || !hdr_b || !tm_pair.entries ||
+        d < 512 || (a0 & 511) || a0 + d + 512 > n) {
+        snprintf(g_err, sizeof(g_err), "lsk_chain_paired: plan out of range");
+        return -1;
+    }
+    ChainImage img;
+    if (chain_lds_image(4, ChainTraits<uint32_t, uint32_t>::NB, bs.hamming_weight, 8, 11, &img) != 0) return -1;
+    chain_pair_args pr = {d, a0, (uint32_t const *)hdr_b, bond};
+    hipLaunchKernelGGL(k_chain_pair_t, dim3((unsigned)(tm_pair.slots_per_xcd * 8)), dim3(kBlock), (size_t)img.bytes, (hipStream_t)stream, op.runs,
+                       op.n_diag, op.diag, bs.hamming_weight, img.dev, img.bytes / 16, img.kc, img.near_off, tm_pair.entries,
+                       tm_pair.slots_per_xcd, n, records, x, y, n_cached, cv0, pr, (uint32_t const *)wave_plan);
+    LSK_LAUNCH_CHECK();
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

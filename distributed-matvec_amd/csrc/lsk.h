@@ -274,6 +274,13 @@ int lsk_chain_tile_rows(int cplx);
 int lsk_chain(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, int wide_ranks, int fused_records, lsk_tilemap tm,
               int64_t n, uint64_t const *reps, int64_t row0, int64_t n_x, void const *x, void *y, int n_cached,
               void const *cache, double cv0, double cv1, void const *wave_plan, void *stream);
+/* The paired launch (k_chain_pair_t) next to lsk_chain() of a plan with 32-bit states and ranks, f64 vectors, fused records and wave
+ * headers, row0 == 0 and n_x == n: every non-empty entry of tm_pair is the first row i0 of a tile of two 512-row segments, rows
+ * [i0, i0 + 512) and [i0 + d, i0 + d + 512), which bond `bond` (= sites - 2, inside one of the operator's runs) maps onto each other
+ * row by row; the plan's other tile map leaves those rows out.  a0 = the lowest i0 (a multiple of 512), hdr_b = lsk_chain_headers of
+ * the rows from a0 + d on (the second segments lie off the 64-row grid of the plan's headers). */
+int lsk_chain_paired(lsk_operator op, lsk_basis bs, lsk_tilemap tm_pair, int64_t n, uint64_t const *records, void const *x, void *y,
+                     int n_cached, double cv0, void const *wave_plan, int64_t d, int64_t a0, void const *hdr_b, int bond, void *stream);
 /* ---- staged row kernel for arbitrary exchange pairs (k_pairs_t, k_rows.hip): Heisenberg / XXZ on any lattice -------------
  * pairs are sorted by class: [0, n_near) both sites below bit 11, [n_near, n_near + n_str) i < 11 <= j, then both >= 11 */
 #define LSK_MAX_PAIRS 128

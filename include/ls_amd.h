@@ -855,6 +855,14 @@ int ls_amd_basis_group_character(ls_hs_basis const *basis, int element, double *
  * Returns the number of entries per list; *entries (malloc'ed, release with ls_amd_test_free) holds the 8 lists
  * (first row | rows << 48; 0 = empty slot); < 0 on error. */
 int64_t ls_amd_test_tilemap(int64_t n, int tile_rows, int64_t chunk, uint64_t **entries);
+/* Rows of y that the plan's paired launch computes (k_chain_pair_t: tiles of two 512-row segments that the top bond of a chain maps
+ * onto each other); 0 for every plan that runs on k_chain_t alone (LS_AMD_CHAIN_PAIRED=0 forces that) or not on it at all. */
+int64_t ls_amd_plan_chain_paired_rows(ls_amd_plan const *pl);
+/* Host-only test hook: the two tile maps of the paired chain plan (k_chain_pair_t) of the weight-`weight` words of L sites -- `pairs`:
+ * first row of every tile of two 512-row segments d rows apart, `rest`: the tiles of all other rows (bit 63 of an entry: that tile
+ * runs on its records).  Returns 1 (out[0..5] = rows, first and one-past-last paired row of the first segments, d, slots per XCD of
+ * rest and of pairs), 0 when the basis has no whole paired segment, < 0 on error; free both with ls_amd_test_free. */
+int ls_amd_test_tilemap_paired(int L, int weight, int tile_rows, int64_t chunk, uint64_t **rest, uint64_t **pairs, int64_t *out);
 void ls_amd_test_free(void *p);
 /* Host-only test hook: the near-window search of the staged pull kernel for projected bases (k_tile_pull): position of
  * `key` among the ascending reps[0, n) (n <= 1280, stored as saturating 32-bit offsets from reps[0] exactly as a tile
