@@ -151,6 +151,12 @@ def load():
         "ls_amd_plan_axpby_kernel_name": (C.c_char_p, [vp, C.c_int]),
         "ls_amd_block_axpby_dots": (C.c_int, [C.c_int, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, C.c_int64,
                                               C.c_int64, C.c_double, C.c_double, C.c_double, vp, vp]),
+        "ls_amd_block_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64,
+                                        vp, vp]),
+        "ls_amd_block_gram_work_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+        "ls_amd_block_gram_kernel_name": (C.c_char_p, [C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64]),
+        "ls_amd_matvec_block_axpby_gram": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                                     C.c_double, vp, vp]),
         "ls_amd_matvec_block_axpby_acc": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                                     C.c_double, vp, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, vp, vp]),
         "ls_amd_plan_acc_kernel_name": (C.c_char_p, [vp, C.c_int]),

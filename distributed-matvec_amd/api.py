@@ -699,6 +699,48 @@ class MatvecPlan:
             _lib.check(-1)
         return name.decode()
 
+    def matvec_block_axpby_gram(self, x, y, alpha, beta, gamma, gram, check: bool = True):
+        """matvec_block_axpby with matrix-valued dots (ls_amd_matvec_block_axpby_gram): the same step on the same path -- y is
+        bit-identical to matvec_block_axpby's -- followed by one Gram launch, gram[0] = X^+ X, gram[1] = X^+ Y with the new Y.
+        gram: a contiguous device tensor of 2 K K elements of the plan's dtype (e.g. shape (2, K, K)), assigned; it must not
+        overlap x or y.  gram_kernel(K) names the form of the Gram launch."""
+        torch = _torch()
+        who = "matvec_block_axpby_gram"
+        if self.P != 1 or self.me >= 0:
+            raise _lib.LsAmdError(f"{who}: one-partition plans only (this plan has P = {self.P}, my_partition = {self.me})")
+        want = torch.complex128 if self.cplx else torch.float64
+        for name, t in (("x", x), ("y", y)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise _lib.LsAmdError(f"{who}: {name} must be a 2-D (N, K) tensor")
+            if t.dtype != want:
+                raise _lib.LsAmdError(f"{who}: {name} is {t.dtype}, the plan computes in {want}")
+            if t.device.type != "cuda":
+                raise _lib.LsAmdError(f"{who}: {name} must be a device tensor")
+        n = self.reps[0].numel()
+        if tuple(x.shape) != tuple(y.shape) or x.shape[0] != n:
+            raise _lib.LsAmdError(f"{who}: x {tuple(x.shape)} and y {tuple(y.shape)} must both be ({n}, K)")
+        K = int(x.shape[1])
+        if not isinstance(gram, torch.Tensor) or gram.device.type != "cuda" or gram.dtype != want or not gram.is_contiguous() \
+                or gram.numel() != 2 * K * K:
+            raise _lib.LsAmdError(f"{who}: gram must be a contiguous device tensor of 2 K K = {2 * K * K} elements of {want}")
+        _lib.check(_lib.load().ls_amd_matvec_block_axpby_gram(self.h, K, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
+                                                              C.c_void_p(y.data_ptr()), y.stride(0), y.stride(1), float(alpha), float(beta),
+                                                              float(gamma), C.c_void_p(gram.data_ptr()), _stream_ptr()))
+        if check:
+            self.check()
+
+    def gram_kernel(self, K: int, x=None, y=None) -> str:
+        """form of the Gram launch of matvec_block_axpby_gram for K columns: "k_block_gram_mfma" for interleaved blocks (the
+        layout assumed when x and y are not given) of K >= 8 columns -- of any K under LS_AMD_GRAM=mfma --, "k_block_gram" for
+        narrower blocks, other strides or under LS_AMD_GRAM=valu"""
+        K = int(K)
+        xs = (K, 1) if x is None else (x.stride(0), x.stride(1))
+        ys = (K, 1) if y is None else (y.stride(0), y.stride(1))
+        name = _lib.load().ls_amd_block_gram_kernel_name(int(self.cplx), K, xs[0], xs[1], K, ys[0], ys[1])
+        if name is None:
+            _lib.check(-1)
+        return name.decode()
+
     def matvec_block_axpby_acc(self, x, y, alpha, beta, gamma, z, c, dots=None, check: bool = True):
         """matvec_block_axpby, and Z[:, k] <- Z[:, k] + c Y[:, k] with the new Y where the kernel stores it
         (ls_amd_matvec_block_axpby_acc): one order of the Chebyshev series of e^{-iHt} per call.  z: an (N, K) device tensor with

@@ -1798,6 +1798,8 @@ struct ls_amd_plan {
     lsk_tilemap blk_tilemap;
     void *d_blk_tilemap;
     void *d_blk_cols; /* [2][count] elements */
+    void *d_gram_work;        /* ls_amd_matvec_block_axpby_gram: the partials of the Gram launch, gram_work_bytes of them */
+    size_t gram_work_bytes;
     void *d_series_work;      /* ls_amd_matvec_block_series without caller's work: two blocks of count x series_cols elements */
     int series_cols;
     double *d_series_dots;    /* [64][2 * 64]: the dots of 64 orders */
@@ -2109,6 +2111,9 @@ static void block_free(ls_amd_plan *pl) {
     memset(&pl->blk_tilemap, 0, sizeof(pl->blk_tilemap));
     if (pl->d_blk_cols) lsk_free(pl->d_blk_cols);
     pl->d_blk_cols = NULL;
+    if (pl->d_gram_work) lsk_free(pl->d_gram_work);
+    pl->d_gram_work = NULL;
+    pl->gram_work_bytes = 0;
     if (pl->d_series_work) lsk_free(pl->d_series_work);
     pl->d_series_work = NULL;
     pl->series_cols = 0;
@@ -4732,6 +4737,103 @@ int ls_amd_matvec_block_axpby(ls_amd_plan *pl, int K, void const *d_x, int64_t x
     if (d_dots) DEV(lsk_memset_async(d_dots, 0, sizeof(double) * 2 * (size_t)K, stream));
     block_step const s = { .kind = STEP_CHEB, .alpha = alpha, .beta = beta, .gamma = gamma, .d_dots = d_dots };
     return block_step_run(pl, block_path(pl, K), &b, &s, stream);
+}
+
+/* ============================================================================================ */
+/* Gram matrices of blocks (k_gram.hip): ls_amd_block_gram, and the Chebyshev step followed by   */
+/* X^+ X and X^+ Y (ls_amd_matvec_block_axpby_gram) -- the matrix-valued moments of kpm.py       */
+/* ============================================================================================ */
+/* a block the MFMA form reads as it lies: column stride 1 (or one column) and a row stride equal to its width */
+static int gram_interleaved(int K, int64_t row, int64_t col) { return row == K && (K == 1 || col == 1); }
+/* LS_AMD_GRAM=auto|mfma|valu, read at every call: `valu` takes k_block_gram everywhere; `mfma` forces k_block_gram_mfma where it
+ * applies (every block interleaved); anything else is the rule the measurements decided ("Matrix moments"):
+ * the MFMA form from 8 columns on -- below that most of its 16 operand columns are padding and k_block_gram is faster */
+enum { GRAM_MFMA_MIN_COLS = 8 };
+static int gram_use_mfma(int all_interleaved, int Ka, int Kb) {
+    char const *e = getenv("LS_AMD_GRAM");
+    if (e && strcmp(e, "valu") == 0) return 0;
+    if (e && strcmp(e, "mfma") == 0) return all_interleaved;
+    return all_interleaved && Ka >= GRAM_MFMA_MIN_COLS && Kb >= GRAM_MFMA_MIN_COLS;
+}
+int64_t ls_amd_block_gram_work_bytes(int64_t n, int Ka, int Kb, int cplx) {
+    if (n < 0 || Ka < 1 || Ka > 64 || Kb < 1 || Kb > 64) {
+        set_error("ls_amd_block_gram_work_bytes: n = %lld, Ka = %d, Kb = %d: need n >= 0 and 1 <= Ka, Kb <= 64", (long long)n, Ka, Kb);
+        return -1;
+    }
+    /* (room for two ket blocks, whatever the call has) */
+    return (int64_t)lsk_block_gram_blocks(n, Ka, Kb, cplx != 0) * 2 * Ka * Kb * (cplx ? 16 : 8);
+}
+char const *ls_amd_block_gram_kernel_name(int cplx, int Ka, int64_t a_row, int64_t a_col, int Kb, int64_t b_row, int64_t b_col) {
+    if (Ka < 1 || Ka > 64 || Kb < 1 || Kb > 64) {
+        set_error("ls_amd_block_gram_kernel_name: Ka = %d, Kb = %d: each is outside [1, 64]", Ka, Kb);
+        return NULL;
+    }
+    return lsk_block_gram_kernel_name(gram_use_mfma(gram_interleaved(Ka, a_row, a_col) && gram_interleaved(Kb, b_row, b_col), Ka, Kb));
+}
+/* [p, p + bytes) against an n x K block of elements of w bytes */
+static int range_overlaps_block(void const *p, size_t bytes, size_t w, int64_t n, void const *b, int64_t br, int64_t bc, int K) {
+    uintptr_t const p0 = (uintptr_t)p, p1 = p0 + bytes;
+    uintptr_t const b0 = (uintptr_t)b, b1 = b0 + w * (size_t)((n - 1) * br + (int64_t)(K - 1) * bc + 1);
+    return p0 < b1 && b0 < p1;
+}
+int ls_amd_block_gram(int cplx, int64_t n, int Ka, void const *d_a, int64_t a_row, int64_t a_col, int Kb, void const *d_b, int64_t b_row,
+                      int64_t b_col, void *d_work, int64_t work_bytes, void *d_out, void *stream) {
+    char const *const who = "ls_amd_block_gram";
+    if (Ka < 1 || Ka > 64) return set_error("%s: Ka = %d is outside [1, 64]", who, Ka);
+    if (Kb < 1 || Kb > 64) return set_error("%s: Kb = %d is outside [1, 64]", who, Kb);
+    if (n < 0) return set_error("%s: n = %lld is negative", who, (long long)n);
+    if (!d_out) return set_error("%s: the output is NULL", who);
+    size_t const w = cplx ? 16 : 8;
+    if (n == 0) {
+        DEV(lsk_memset_async(d_out, 0, w * (size_t)Ka * (size_t)Kb, stream));
+        return 0;
+    }
+    if (!d_a || !d_b) return set_error("%s: A or B is NULL", who);
+    if (!d_work) return set_error("%s: the work buffer is NULL", who);
+    if (Ka == 1) a_col = 0;
+    if (Kb == 1) b_col = 0;
+    if (block_strides(who, n, Ka, a_row, a_col, "A") != 0 || block_strides(who, n, Kb, b_row, b_col, "B") != 0) return -1;
+    int64_t const need = ls_amd_block_gram_work_bytes(n, Ka, Kb, cplx) / 2; /* (one ket block) */
+    if (work_bytes < need) return set_error("%s: work_bytes = %lld, this call needs %lld (ls_amd_block_gram_work_bytes)", who, (long long)work_bytes, (long long)need);
+    if (range_overlaps_block(d_out, w * (size_t)Ka * (size_t)Kb, w, n, d_a, a_row, a_col, Ka) ||
+        range_overlaps_block(d_out, w * (size_t)Ka * (size_t)Kb, w, n, d_b, b_row, b_col, Kb))
+        return set_error("%s: the output overlaps A or B", who);
+    if (range_overlaps_block(d_work, (size_t)need, w, n, d_a, a_row, a_col, Ka) || range_overlaps_block(d_work, (size_t)need, w, n, d_b, b_row, b_col, Kb))
+        return set_error("%s: the work buffer overlaps A or B", who);
+    int const mfma = gram_use_mfma(gram_interleaved(Ka, a_row, a_col) && gram_interleaved(Kb, b_row, b_col), Ka, Kb);
+    DEV(lsk_block_gram(cplx != 0, n, Ka, d_a, a_row, a_col, Kb, 1, d_b, b_row, b_col, NULL, 0, 0, mfma, (double *)d_work, (double *)d_out, stream));
+    return 0;
+}
+int ls_amd_matvec_block_axpby_gram(ls_amd_plan *pl, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row,
+                                   int64_t y_col, double alpha, double beta, double gamma, void *d_gram, void *stream) {
+    char const *const who = "ls_amd_matvec_block_axpby_gram";
+    int64_t const n = block_step_rows(who, pl, K, NULL, stream);
+    if (n < 0) return -1;
+    if (!d_gram) return set_error("%s: the Gram output is NULL", who);
+    size_t const w = pl->cplx ? 16 : 8, gram_bytes = 2 * w * (size_t)K * (size_t)K;
+    if (n == 0) {
+        DEV(lsk_memset_async(d_gram, 0, gram_bytes, stream));
+        return 0;
+    }
+    if (!d_x || !d_y) return set_error("%s: X or Y is NULL", who);
+    if (K == 1) { x_col = 0; y_col = 0; }
+    block_xy const b = { K, (char const *)d_x, x_row, x_col, (char *)d_y, y_row, y_col };
+    if (block_xy_check(who, pl, &b) != 0) return -1;
+    if (range_overlaps_block(d_gram, gram_bytes, w, n, d_x, x_row, x_col, K) || range_overlaps_block(d_gram, gram_bytes, w, n, d_y, y_row, y_col, K))
+        return set_error("%s: the Gram output overlaps X or Y", who);
+    size_t const need = (size_t)ls_amd_block_gram_work_bytes(n, K, K, pl->cplx);
+    if (pl->gram_work_bytes < need) {
+        if (pl->d_gram_work) lsk_free(pl->d_gram_work);
+        pl->d_gram_work = NULL;
+        pl->gram_work_bytes = 0;
+        if (lsk_malloc(&pl->d_gram_work, need) != 0) return dev_error();
+        pl->gram_work_bytes = need;
+    }
+    if (ls_amd_matvec_block_axpby(pl, K, d_x, x_row, x_col, d_y, y_row, y_col, alpha, beta, gamma, NULL, stream) != 0) return -1;
+    int const mfma = gram_use_mfma(gram_interleaved(K, x_row, x_col) && gram_interleaved(K, y_row, y_col), K, K);
+    DEV(lsk_block_gram(pl->cplx, n, K, d_x, x_row, x_col, K, 2, d_x, x_row, x_col, d_y, y_row, y_col, mfma, (double *)pl->d_gram_work,
+                       (double *)d_gram, stream));
+    return 0;
 }
 
 /* ============================================================================================ */

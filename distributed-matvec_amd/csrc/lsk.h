@@ -513,6 +513,16 @@ int lsk_pull_gather_cheb(lsk_operator op, lsk_basis bs, int cplx, int64_t row0, 
 int lsk_axpby_dots(int cplx, int64_t n, int K, void const *w, int64_t wr, int64_t wc, void const *x, int64_t xr, int64_t xc,
                    void *y, int64_t yr, int64_t yc, double alpha, double beta, double gamma, double *d_xx, double *d_xy,
                    void *stream);
+/* ---- Gram matrices of blocks (ls_amd_block_gram, ls_amd_matvec_block_axpby_gram; k_gram.hip):
+ *     out[(ket Ka + a) Kb + b] = sum_r conj(A[r][a]) B_ket[r][b],  ket < nket (1 or 2; b2 is not read when nket == 1),
+ * ASSIGNED, in elements of the vector type; strides in elements.  mfma != 0: k_block_gram_mfma, for which every block must have
+ * column stride 1 (or one column) and a row stride equal to its width; else k_block_gram, any strides.  partial: the caller's
+ * scratch of lsk_block_gram_blocks(n, Ka, Kb, cplx) x nket Ka Kb elements.  No floating-point atomics. */
+int lsk_block_gram_blocks(int64_t n, int Ka, int Kb, int cplx);
+char const *lsk_block_gram_kernel_name(int mfma);
+int lsk_block_gram(int cplx, int64_t n, int Ka, void const *a, int64_t a_row, int64_t a_col, int Kb, int nket, void const *b1,
+                   int64_t b1_row, int64_t b1_col, void const *b2, int64_t b2_row, int64_t b2_col, int mfma, double *partial,
+                   double *out, void *stream);
 /* ---- accumulate step of Chebyshev time evolution (ls_amd_matvec_block_axpby_acc; k_evolve.hip): the Chebyshev step above, and
  * Z[i, k] += (c_re + i c_im) Y[i, k] with the new Y where it is stored.  Z: K columns of its own strides (in ITS elements), c128 when
  * z_cplx != 0, else f64 (then c_im == 0 and f64 vectors).  The row kernels want a c128 Z 16-byte aligned. */

@@ -5,7 +5,13 @@ matvec reaches.  H~ = (H - b) / a maps the spectrum into [-1, 1] (a = (hi - lo) 
 The recurrence v_{n+1} = 2 H~ v_n - v_{n-1} is one call of MatvecPlan.matvec_block_axpby per step (ls_amd_matvec_block_axpby: the
 update and both dot products of the step happen where the block kernels store their result), and every step yields two moments
 (mu_2n = 2 <v_n|v_n> - mu_0, mu_2n+1 = 2 <v_n|v_n+1> - mu_1): M moments cost M / 2 steps and two blocks of memory.  One-partition
-plans.  The Jackson-damped series is summed on the host."""
+plans.  The Jackson-damped series is summed on the host.
+
+Matrix-valued moments mu_n[a][b] = <v_a|T_n(H~)|v_b> of the K columns of a block come from the same recurrence with the two dots
+of the step replaced by the two K x K Gram matrices X^+ X and X^+ Y (MatvecPlan.matvec_block_axpby_gram; csrc/k_gram.hip): the
+doubling formulas hold for matrices, so K columns of matvecs give all K^2 entries (polarisation needs K^2 columns).  They feed the
+spectral matrix S_ab(w) = <psi|A_a^+ delta(w - H) A_b|psi> (spectral_matrix, reconstruct_matrix), the retarded Green's matrix
+(greens_matrix) and cross correlators <v_a|e^{-iHt}|v_b> on any time grid (cross_correlation)."""
 from __future__ import annotations
 
 import math
@@ -15,6 +21,11 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import LsAmdError
+
+__all__ = ["KpmResult", "KpmMatrixResult", "jackson_kernel", "reconstruct", "chebyshev_grid", "moments_from_dots", "check_guard",
+           "chebyshev_moments", "delta_filter", "filter_order", "chebyshev_series", "spectral_bounds", "random_phase_block",
+           "density_of_states", "spectral_function", "block_gram", "moment_matrices_from_grams", "chebyshev_moment_matrices",
+           "reconstruct_matrix", "greens_matrix", "cross_correlation", "spectral_matrix"]
 
 GUARD_EVERY = 64      # steps between two read-backs of the dots (the only host synchronisations of the recurrence)
 GUARD_SLACK = 1e-6    # ||T_n(H~) v0||^2 <= (1 + slack) ||v0||^2 while the spectrum lies inside the bounds
@@ -144,6 +155,238 @@ def chebyshev_moments(op, start, num_moments: int, bounds) -> np.ndarray:
     if checked < steps:
         read_back(steps)
     return moments_from_dots(host, K, M)
+
+
+# ---------------------------------------------------------------------------------------------
+# matrix-valued moments
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class KpmMatrixResult:
+    moments: np.ndarray       # [M, K, K] complex128: mu_n[a][b] = <v_a|T_n(H~)|v_b>, v_a = A_a|psi>
+    bounds: tuple             # (lo, hi) the spectrum was rescaled with
+    matvecs: int              # columns that went through H (K per step, M / 2 steps)
+    kernel: str               # MatvecPlan.axpby_kernel(K)
+    gram_kernel: str          # MatvecPlan.gram_kernel(K): "k_block_gram_mfma" or "k_block_gram"
+    state: object = None      # the state |psi> the operators were applied to (device tensor)
+    target_states: object = None  # the (n, K) block of the v_a on the basis the moments were computed on (device tensor)
+    seconds: float = 0.0
+    step_seconds: float = 0.0
+
+
+def _gram_into(a, b, out, work):
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from .api import _stream_ptr
+
+    _lib.check(_lib.load().ls_amd_block_gram(int(a.dtype == torch.complex128), int(a.shape[0]), int(a.shape[1]), C.c_void_p(a.data_ptr()),
+                                             a.stride(0), a.stride(1), int(b.shape[1]), C.c_void_p(b.data_ptr()), b.stride(0), b.stride(1),
+                                             C.c_void_p(work.data_ptr()), work.numel() * 8, C.c_void_p(out.data_ptr()), _stream_ptr()))
+
+
+def _gram_work(n, Ka, Kb, dtype, device):
+    import torch
+
+    from . import _lib
+
+    need = int(_lib.load().ls_amd_block_gram_work_bytes(int(n), int(Ka), int(Kb), int(dtype == torch.complex128)))
+    if need < 0:
+        _lib.check(-1)
+    return torch.empty(max(1, need // 8), dtype=torch.float64, device=device)
+
+
+def block_gram(a, b):
+    """G = A^+ B, G[i][j] = sum_r conj(A[r, i]) B[r, j], of the (n, Ka) and (n, Kb) device tensors a and b (both float64 or both
+    complex128, any strides, Ka, Kb <= 64) as a new (Ka, Kb) device tensor (ls_amd_block_gram).  Interleaved blocks (contiguous
+    (n, K) tensors) of at least 8 columns run on the f64 MFMA, narrower ones and other strides on the vector ALU;
+    LS_AMD_GRAM=mfma|valu overrides that.  Sums in a fixed order: two calls return equal bytes.  Allocates its own scratch."""
+    import torch
+
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise LsAmdError(f"block_gram: {name} must be a 2-D (n, K) tensor")
+        if t.device.type != "cuda":
+            raise LsAmdError(f"block_gram: {name} must be a device tensor")
+        if t.dtype not in (torch.float64, torch.complex128) or t.dtype != a.dtype:
+            raise LsAmdError(f"block_gram: {name} is {t.dtype}; a and b must both be float64 or both complex128")
+        if not 1 <= int(t.shape[1]) <= 64:
+            raise LsAmdError(f"block_gram: {name} has K = {int(t.shape[1])} columns: 1 <= K <= 64")
+    if a.shape[0] != b.shape[0]:
+        raise LsAmdError(f"block_gram: a {tuple(a.shape)} and b {tuple(b.shape)} must have the same number of rows")
+    out = torch.empty((int(a.shape[1]), int(b.shape[1])), dtype=a.dtype, device=a.device)
+    _gram_into(a, b, out, _gram_work(a.shape[0], a.shape[1], b.shape[1], a.dtype, a.device))
+    return out
+
+
+def moment_matrices_from_grams(grams, num_moments: int) -> np.ndarray:
+    """grams [steps, 2, K, K] (row n: V_n^+ V_n, then V_n^+ V_n+1, V_n = T_n(H~) V_0) -> moments [M, K, K] complex128 by the doubling
+    formulas mu_2n = 2 V_n^+ V_n - mu_0, mu_2n+1 = 2 V_n^+ V_n+1 - mu_1, each symmetrised as (mu + mu^+) / 2 (T_n(H~) is Hermitian;
+    the two Gram matrices are so up to rounding)"""
+    g = np.asarray(grams).astype(np.complex128)
+    steps, K = g.shape[0], g.shape[-1]
+    mu = np.empty((2 * steps, K, K), dtype=np.complex128)
+    mu[0], mu[1] = g[0, 0], g[0, 1]
+    for n in range(1, steps):
+        mu[2 * n] = 2.0 * g[n, 0] - mu[0]
+        mu[2 * n + 1] = 2.0 * g[n, 1] - mu[1]
+    mu = mu[:int(num_moments)]
+    return 0.5 * (mu + mu.conj().transpose(0, 2, 1))
+
+
+def chebyshev_moment_matrices(op, start, num_moments: int, bounds, bra=None) -> np.ndarray:
+    """mu_n[a][b] = <v_a|T_n(H~)|v_b> for the K columns of the (n, K) device block `start`, n < num_moments: [M, K, K] complex128
+    (Hermitian; real up to rounding on a float64 operator).  op: a diagonalize.LocalOperator on one partition.  One
+    MatvecPlan.matvec_block_axpby_gram per step, two moments per step; the Gram matrices of all steps land in one device array,
+    read back (the only synchronisation) every GUARD_EVERY steps for the growth guard on the diagonal of X^+ X.
+    bra: an (n, Ka) device block Phi -> [M, Ka, K], mu_n = Phi^+ T_n(H~) V_0 -- one order per step (the doubling needs bra = ket):
+    matvec_block_axpby and one block_gram, e.g. for <phi_a|e^{-iHt}|psi_b> through cross_correlation."""
+    import torch
+
+    M = int(num_moments)
+    if M < 2:
+        raise ValueError(f"num_moments = {num_moments!r}: at least 2")
+    lo, hi = _bounds(bounds, "chebyshev_moment_matrices")
+    if len(op.sizes) != 1:
+        raise LsAmdError("kpm: one-partition plans only")
+    if start.dim() != 2 or start.shape[0] != op.n_local:
+        raise LsAmdError(f"kpm: start {tuple(start.shape)} must be an ({op.n_local}, K) block")
+    a, b = 0.5 * (hi - lo), 0.5 * (hi + lo)
+    K = int(start.shape[1])
+    if not 1 <= K <= 64:
+        raise LsAmdError(f"kpm: K = {K} columns: 1 <= K <= 64")
+    X = start.to(op.dtype).contiguous().clone()
+    Y = torch.empty_like(X)
+    plan = op.plan
+    checked = 0
+    if bra is not None:
+        if bra.dim() != 2 or bra.shape[0] != op.n_local or not 1 <= int(bra.shape[1]) <= 64:
+            raise LsAmdError(f"kpm: bra {tuple(bra.shape)} must be an ({op.n_local}, Ka) block, 1 <= Ka <= 64")
+        phi = bra.to(op.dtype).contiguous()
+        Ka = int(phi.shape[1])
+        steps = M - 1
+        out = torch.zeros((M, Ka, K), dtype=op.dtype, device=X.device)
+        work = _gram_work(op.n_local, Ka, K, op.dtype, X.device)
+        dots = torch.zeros((steps, 2 * K), dtype=torch.float64, device=X.device)
+        host = np.empty((steps, 2 * K), dtype=np.float64)
+
+        def read_back(upto):
+            nonlocal checked
+            host[checked:upto] = dots[checked:upto].cpu().numpy()
+            plan.check()
+            check_guard(np.concatenate([host[:1], host[checked:upto]]), K, (lo, hi), first_step=checked - 1)
+            checked = upto
+
+        _gram_into(phi, X, out[0], work)
+        for s in range(steps):
+            if s == 0:
+                plan.matvec_block_axpby(X, Y, 1.0 / a, -b / a, 0.0, dots=dots[0], check=False)
+            else:
+                plan.matvec_block_axpby(X, Y, 2.0 / a, -2.0 * b / a, -1.0, dots=dots[s], check=False)
+            X, Y = Y, X
+            _gram_into(phi, X, out[s + 1], work)
+            op.matvecs += K
+            if (s + 1) % GUARD_EVERY == 0:
+                read_back(s + 1)
+        if checked < steps:
+            read_back(steps)
+        return out.cpu().numpy().astype(np.complex128)
+
+    steps = (M + 1) // 2
+    grams = torch.zeros((steps, 2, K, K), dtype=op.dtype, device=X.device)
+    host = np.empty((steps, 2, K, K), dtype=np.complex128)
+
+    def read_back(upto):  # noqa: F811
+        nonlocal checked
+        host[checked:upto] = grams[checked:upto].cpu().numpy()
+        plan.check()
+        norms = np.zeros((upto - checked + 1, 2 * K), dtype=np.float64)
+        norms[0, :K] = np.diagonal(host[0, 0]).real
+        norms[1:, :K] = np.diagonal(host[checked:upto, 0], axis1=1, axis2=2).real
+        check_guard(norms, K, (lo, hi), first_step=checked - 1)
+        checked = upto
+
+    for s in range(steps):
+        if s == 0:
+            plan.matvec_block_axpby_gram(X, Y, 1.0 / a, -b / a, 0.0, grams[0], check=False)
+        else:
+            plan.matvec_block_axpby_gram(X, Y, 2.0 / a, -2.0 * b / a, -1.0, grams[s], check=False)
+        X, Y = Y, X
+        op.matvecs += K
+        if (s + 1) % GUARD_EVERY == 0:
+            read_back(s + 1)
+    if checked < steps:
+        read_back(steps)
+    return moment_matrices_from_grams(host, M)
+
+
+def _matrix_series(moments, bounds, energies, who):
+    """(x inside the bounds, theta, the damped coefficients (2 - delta_n0) g_n mu_n [M, ...], a) shared by the two reconstructions"""
+    mu = np.asarray(moments, dtype=np.complex128)
+    if mu.ndim != 3:
+        raise ValueError(f"{who}: moments {mu.shape} must be [M, Ka, Kb]")
+    lo, hi = _bounds(bounds, who)
+    a, b = 0.5 * (hi - lo), 0.5 * (hi + lo)
+    c = mu * jackson_kernel(mu.shape[0])[:, None, None]
+    c[1:] *= 2.0
+    x = (np.asarray(energies, dtype=np.float64).reshape(-1) - b) / a
+    inside = np.abs(x) < 1.0
+    return inside, np.arccos(np.where(inside, x, 0.0)), c, a
+
+
+def reconstruct_matrix(moments, bounds, energies) -> np.ndarray:
+    """S_ab(E) = 1 / (pi a sqrt(1 - x^2)) [g_0 mu_0 + 2 sum_n g_n mu_n T_n(x)]_ab, x = (E - b) / a, zero outside the bounds: the
+    Jackson-damped series of `reconstruct`, entry by entry, of the moments [M, Ka, Kb] at the energies [E] -> complex128
+    [E, Ka, Kb].  For Hermitian moments of one block (Ka = Kb) every S(E) is Hermitian and -- the kernel being positive --
+    positive semi-definite."""
+    inside, theta, c, a = _matrix_series(moments, bounds, energies, "reconstruct_matrix")
+    out = np.zeros((theta.size,) + c.shape[1:], dtype=np.complex128)
+    n = np.arange(c.shape[0], dtype=np.float64)
+    for e0 in range(0, theta.size, 4096):
+        e1 = min(theta.size, e0 + 4096)
+        T = np.cos(theta[e0:e1, None] * n[None, :])
+        out[e0:e1] = np.tensordot(T, c, axes=(1, 0)) / (math.pi * a * np.sin(theta[e0:e1]))[:, None, None]
+    out[~inside] = 0.0
+    return out
+
+
+def greens_matrix(moments, bounds, energies) -> np.ndarray:
+    """the retarded G_ab(E + i0) = <v_a|(E + i0 - H)^-1|v_b> from the same damped series,
+        G(E) = -i / (a sqrt(1 - x^2)) [g_0 mu_0 + 2 sum_n g_n mu_n e^{-i n arccos x}],
+    complex128 [E, Ka, Kb], zero outside the bounds.  Its spectral part is the reconstruction: with Hermitian moments
+    -(G - G^+) / (2 pi i) = reconstruct_matrix(moments, bounds, energies), and entry by entry -Im G_aa / pi = S_aa on the diagonal."""
+    inside, theta, c, a = _matrix_series(moments, bounds, energies, "greens_matrix")
+    out = np.zeros((theta.size,) + c.shape[1:], dtype=np.complex128)
+    n = np.arange(c.shape[0], dtype=np.float64)
+    for e0 in range(0, theta.size, 4096):
+        e1 = min(theta.size, e0 + 4096)
+        ph = np.exp(-1j * theta[e0:e1, None] * n[None, :])
+        out[e0:e1] = -1j * np.tensordot(ph, c, axes=(1, 0)) / (a * np.sin(theta[e0:e1]))[:, None, None]
+    out[~inside] = 0.0
+    return out
+
+
+def cross_correlation(moments, bounds, times, eps: float = 1e-12) -> np.ndarray:
+    """C_ab(t) = <v_a|e^{-iHt}|v_b> = e^{-ibt} sum_n (2 - delta_n0) (-i)^n J_n(a t) mu_n[a][b] from the undamped moment matrices
+    [M, Ka, Kb] of chebyshev_moment_matrices for the same bounds, at the times [T] -> complex128 [T, Ka, Kb].  Host only; the
+    time grid is free (every time is one sum over the same moments).  ValueError when there are fewer moments than the order the
+    series needs for `eps` at some time, as in evolve.autocorrelation."""
+    from .evolve import propagator_coefficients
+
+    mu = np.asarray(moments, dtype=np.complex128)
+    if mu.ndim != 3:
+        raise ValueError(f"cross_correlation: moments {mu.shape} must be [M, Ka, Kb]")
+    lo, hi = _bounds(bounds, "cross_correlation")
+    ts = np.atleast_1d(np.asarray(times, dtype=np.float64))
+    M = mu.shape[0]
+    out = np.empty((len(ts),) + mu.shape[1:], dtype=np.complex128)
+    for j, t in enumerate(ts):
+        c, pref = propagator_coefficients(float(t), (lo, hi), eps)
+        if len(c) > M:
+            raise ValueError(f"cross_correlation: t = {float(t)!r} needs {len(c)} moments for eps = {eps!r}, {M} were given")
+        out[j] = pref * np.tensordot(c, mu[:len(c)], axes=(0, 0))
+    return out
 
 
 FILTER_CUT = 0.17    # filter_order: the levels wanted see p(E) >= cut p(sigma) (POLFED, PRL 125, 156601; DESIGN section 5)
@@ -520,6 +763,102 @@ def spectral_function(config, operator, state=None, num_moments: int = 256, ener
         energies = chebyshev_grid(bounds, 2 * int(num_moments))
     energies = np.asarray(energies, dtype=np.float64)
     S = reconstruct(mu[0], bounds, energies)
+    res.step_seconds = t2 - t1
+    res.seconds = time.perf_counter() - t0
+    return energies, S, res
+
+
+def _operators_of(operators, obs, who):
+    from . import api
+
+    try:
+        ops = list(operators)
+    except TypeError:
+        raise ValueError(f"{who}: operators: a list of api.Operator or of indices of the config's observables") from None
+    if not 1 <= len(ops) <= 64:
+        raise ValueError(f"{who}: {len(ops)} operators: 1 <= K <= 64")
+    out = []
+    for k, o in enumerate(ops):
+        if isinstance(o, (int, np.integer)) and not isinstance(o, bool):
+            if not 0 <= int(o) < len(obs):
+                raise ValueError(f"{who}: operators[{k}] = {o}: the config has {len(obs)} observables")
+            out.append(obs[int(o)])
+        elif isinstance(o, api.Operator):
+            out.append(o)
+        else:
+            raise ValueError(f"{who}: operators[{k}]: an api.Operator or the index of one of the config's observables")
+    return out
+
+
+def spectral_matrix(config, operators, state=None, num_moments: int = 256, energies=None, bounds=None, dtype=None,
+                    eps: float = 1e-10, target=None, groups: str = "same"):
+    """The spectral matrix S_ab(w) = <psi|A_a^+ delta(w - H) A_b|psi> of K operators on the absolute energy scale of H
+    -> (energies, S [E, K, K] complex128, KpmMatrixResult).  operators: a list of api.Operator on the basis of the config, or of
+    indices of the config's `observables`.  state, bounds, energies, dtype, eps, target and groups as spectral_function: without a
+    target every operator must map the basis into itself; with one, every operator must map the config's sector into that ONE
+    target sector (the refusal names the operator that does not), v_a = A_a psi is one api.CrossSectorPlan per operator into one
+    column of an interleaved (n, K) block, and the config's Hamiltonian is re-compiled on the target basis.  The K^2 moment
+    series come from K columns of matvecs (chebyshev_moment_matrices)."""
+    import torch
+
+    from . import api, config as _config
+    from .diagonalize import LocalOperator, lanczos_smallest
+
+    who = "spectral_matrix"
+    t0 = time.perf_counter()
+    basis, h, obs = _load(config, observables=True)
+    ops = _operators_of(operators, obs, who)
+    K = len(ops)
+    dtype = dtype or torch.float64
+    reps, _ = api.enumerateStates(basis, 1)
+    if target is not None:
+        tbasis = _target_basis(target)
+        if groups not in api.CrossSectorPlan.GROUPS:
+            raise ValueError(f"groups = {groups!r} is none of 'same', 'restrict', 'project'")
+        if groups != "project":
+            for k, A in enumerate(ops):
+                try:
+                    A.mapsSector(tbasis, explain=True, signs=True, subgroup=groups == "restrict")
+                except LsAmdError as e:
+                    raise LsAmdError(f"{who}: operators[{k}] does not map the config's sector into the target sector: {e}") from None
+        h_t = api.Operator.fromSpec(tbasis, _config.OperatorSpec(_terms_of(h)))
+        if not h_t.isHermitian:
+            raise ValueError("kpm: the Hamiltonian is not Hermitian (Chebyshev moments need a real spectrum)")
+        treps, _ = api.enumerateStates(tbasis, 1)
+    if state is None:
+        state = lanczos_smallest(LocalOperator(h, reps, dtype), num_evals=1, eps=eps).eigenvectors[0]
+    state = state.to(dtype).contiguous()
+    if state.dim() != 1 or state.numel() != reps[0].numel():
+        raise LsAmdError(f"kpm: state {tuple(state.shape)} must be a vector of {reps[0].numel()} elements")
+    op = LocalOperator(h_t, treps, dtype) if target is not None else LocalOperator(h, reps, dtype)
+    if bounds is None:
+        bounds = spectral_bounds(op)
+    bounds = (float(bounds[0]), float(bounds[1]))
+    V0 = torch.zeros((op.n_local, K), dtype=dtype, device=state.device)
+    col = torch.zeros(op.n_local, dtype=dtype, device=state.device)
+    for k, A in enumerate(ops):
+        col.zero_()
+        if target is not None:
+            cross = api.CrossSectorPlan(A, reps[0], tbasis, treps[0], dtype, groups=groups)
+            cross.apply(state, col)
+            cross.destroy()
+        else:
+            try:
+                api.MatvecPlan(A, reps, dtype).matvec([state], [col])
+            except LsAmdError as e:
+                raise LsAmdError(f"{who}: operators[{k}] cannot be applied inside the config's sector: {e}") from None
+        V0[:, k] = col
+    before = op.matvecs
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    mu = chebyshev_moment_matrices(op, V0, num_moments, bounds)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    res = KpmMatrixResult(mu, bounds, op.matvecs - before, op.plan.axpby_kernel(K), op.plan.gram_kernel(K), state=state, target_states=V0)
+    if energies is None:
+        energies = chebyshev_grid(bounds, 2 * int(num_moments))
+    energies = np.asarray(energies, dtype=np.float64)
+    S = reconstruct_matrix(mu, bounds, energies)
     res.step_seconds = t2 - t1
     res.seconds = time.perf_counter() - t0
     return energies, S, res

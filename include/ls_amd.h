@@ -341,6 +341,34 @@ char const *ls_amd_plan_axpby_kernel_name(ls_amd_plan const *plan, int K);
 int ls_amd_block_axpby_dots(int cplx, int64_t n, int K, void const *d_w, int64_t w_row, int64_t w_col, void const *d_x, int64_t x_row,
                             int64_t x_col, void *d_y, int64_t y_row, int64_t y_col, double alpha, double beta, double gamma,
                             double *d_dots, void *stream);
+/* The Gram matrix of two blocks of vectors, no plan (k_gram.hip):
+ *     d_out[a * Kb + b] = sum_r conj(A[r, a]) * B[r, b],   a < Ka, b < Kb,
+ * in elements of the vector type (cplx != 0: c128, else f64), ASSIGNED.  A: Ka columns of n rows, B: Kb columns of n rows, strides
+ * in elements as everywhere; 1 <= Ka, Kb <= 64.  d_work: device scratch of at least ls_amd_block_gram_work_bytes(n, Ka, Kb, cplx)
+ * bytes (that figure has room for the two ket blocks of ls_amd_matvec_block_axpby_gram; one suffices here and half of it is
+ * accepted).  Blocks with column stride 1 and row stride K can go through the f64 MFMA (k_block_gram_mfma: the memory layout is the
+ * operand layout); any other strides go through k_block_gram on the vector ALU.  LS_AMD_GRAM, read at every call: `mfma` takes the
+ * MFMA form wherever it applies, `valu` never, `auto` (the default) where it applies and min(Ka, Kb) >= 8 -- below that the
+ * vector-ALU form measured faster.
+ * Rows are dealt to workgroups and waves by a fixed function of n, waves are summed in wave order and workgroups in block order:
+ * no floating-point atomics, and two calls return equal bytes.  Refused before any launch: NULL pointers, Ka or Kb outside
+ * [1, 64], n < 0, strides that make two elements share storage, too little work, an output or work buffer that overlaps A or B. */
+int ls_amd_block_gram(int cplx, int64_t n, int Ka, void const *d_a, int64_t a_row, int64_t a_col, int Kb, void const *d_b,
+                      int64_t b_row, int64_t b_col, void *d_work, int64_t work_bytes, void *d_out, void *stream);
+int64_t ls_amd_block_gram_work_bytes(int64_t n, int Ka, int Kb, int cplx); /* -1: refused */
+/* "k_block_gram_mfma" or "k_block_gram": the form a call with these widths and strides takes under the current LS_AMD_GRAM */
+char const *ls_amd_block_gram_kernel_name(int cplx, int Ka, int64_t a_row, int64_t a_col, int Kb, int64_t b_row, int64_t b_col);
+/* The Chebyshev step with matrix-valued dots: ls_amd_matvec_block_axpby with d_dots = NULL on whatever path it takes (Y is
+ * bit-identical to that call's), then ONE Gram launch over X and the new Y,
+ *     d_gram[a * K + b]         = sum_r conj(X[r, a]) * X[r, b],
+ *     d_gram[K * K + a * K + b] = sum_r conj(X[r, a]) * Y[r, b],
+ * 2 K K elements of the plan's type, assigned; X is read once by it.  The partials of the launch live in a buffer the plan
+ * allocates on first use and frees with itself.  Refused before any launch: what ls_amd_matvec_block_axpby refuses (a NULL plan,
+ * K outside [1, 64], a plan of more than one partition, NULL pointers, aliasing strides, X and Y that overlap), and a d_gram that
+ * is NULL or overlaps X or Y. */
+int ls_amd_matvec_block_axpby_gram(ls_amd_plan *plan, int K, void const *d_x, int64_t x_row, int64_t x_col,
+                                   void *d_y, int64_t y_row, int64_t y_col, double alpha, double beta, double gamma,
+                                   void *d_gram, void *stream);
 /* The accumulate step of Chebyshev time evolution: ls_amd_matvec_block_axpby, and the running sum of the series where the new Y
  * is stored,
  *     Z[i,k] <- Z[i,k] + (c_re + i c_im) * Y[i,k]   (the new Y),
