@@ -1761,10 +1761,10 @@ struct ls_amd_plan {
     int chain_headers_apply; /* ... or would be without LS_AMD_CHAIN_RECORDS=1 */
     /* paired tiles (setup_chain_pairs, lsk_chain_paired): tile map of the paired launch, headers of its second segments, rows between
      * the two segments of a tile, first paired row; d_tilemap then covers the other rows only */
-    int chain_paired;
-    void *d_tilemap_pair, *d_chain_hdr_b;
+    int chain_paired, chain_pair_levels; /* (the deepest level that holds a range) */
+    void *d_tilemap_pair, *d_chain_hdr_b; /* (two words per slot; the headers of every range's second segments) */
     lsk_tilemap tilemap_pair;
-    int64_t chain_pair_d, chain_pair_a0, chain_pair_rows;
+    int64_t chain_pair_rows[8]; /* rows paired at level 1, 2, ... ([0] unused) */
     double chain_v[2];
     int64_t chain_row0; /* global rank of the first local row (replicated-x plans) */
     void *d_htab;        /* hash table {rep -> x * norm(rep)} of the tile-pull families */
@@ -2309,20 +2309,45 @@ static int tilemap_host(int64_t n, int TILE, int64_t chunk, uint64_t **out, int6
     *slots_out = slots;
     return 0;
 }
-/* Paired tiles of the chain kernel (k_chain_pair_t, lsk_chain_paired).  In the combinadic order of the weight-k words of L sites the
- * rows whose two top bits are 01 are R01 = [C(L-2, k), C(L-1, k)), those with 10 the next d = C(L-2, k-1) rows, and rows R01 + j and
- * R01 + d + j differ in those two bits only: bond L - 2 connects them.  [a0, a1) = the whole 512-row segments of R01; 0 when there is
- * none (or the ranks leave 32 bits). */
-static int chain_pair_range(int L, int k, int64_t *a0, int64_t *a1, int64_t *d) {
+/* Paired tiles of the chain kernel (k_chain_pair_t, lsk_chain_paired).  Read the top site bits as disjoint pairs (L-1, L-2), (L-3, L-4),
+ * ...: levels 1, 2, ...  A row belongs to the first level, from the top, whose two bits differ; flipping them (bond b = L - 2 level)
+ * keeps it there, so no row is claimed twice.  Fix a pattern h of the level - 1 higher pairs (each 00 or 11) and let m = k - popc(h) - 1
+ * be the set bits below b: in the combinadic order of the weight-k words the rows with pair bits 01 are
+ * base(h) + [C(b, m + 1), C(b + 1, m + 1)), those with 10 the next d = C(b, m) rows, and rows R01 + j and R01 + d + j differ in those two
+ * bits only (base(h) = the rank terms of the set bits of h; level 1: R01 = [C(L-2, k), C(L-1, k))).  A range = the whole 512-row
+ * segments [a0, a1) of one R01; hdr0 = where the wave headers of its second segments start, in headers, all ranges in one array.
+ * Levels go on while b >= 12 (a far pair) and bond b lies in `bonds` (bit b: inside an exchange run), `levels` at most; ranges come in
+ * (level, h ascending) order.  Returns their number, at most CHAIN_MAX_RANGES = 2^6 - 1 (six levels). */
+#define CHAIN_MAX_PAIR_LEVELS 6
+#define CHAIN_PAIR_LEVELS_DEFAULT 2 /* LS_AMD_CHAIN_PAIR_LEVELS; chain_32: 3, 4 and 6 measure 0.01-0.03 ms below 2, under 3 x the run-to-run spread (profiles/chain_pair_levels_ab.txt) */
+#define CHAIN_MAX_RANGES 63
+typedef struct { int level, bond; int64_t a0, a1, d, hdr0; } chain_range;
+static int chain_pair_ranges(int L, int k, int levels, uint64_t bonds, chain_range *out) {
     if (L < 14 || L > 32 || k < 1 || k > L - 1) return 0;
     uint64_t C[33][33];
     memset(C, 0, sizeof(C));
     for (int n = 0; n <= 32; ++n) { C[n][0] = 1; for (int j = 1; j <= n; ++j) C[n][j] = C[n - 1][j - 1] + (j <= n - 1 ? C[n - 1][j] : 0); }
-    int64_t const r01 = (int64_t)C[L - 2][k], r10 = (int64_t)C[L - 1][k];
-    *d = r10 - r01;
-    *a0 = (r01 + 511) & ~(int64_t)511;
-    *a1 = r10 & ~(int64_t)511;
-    return *a1 > *a0;
+    if (levels > CHAIN_MAX_PAIR_LEVELS) levels = CHAIN_MAX_PAIR_LEVELS;
+    int nr = 0;
+    int64_t hdr = 0;
+    for (int lv = 1; lv <= levels; ++lv) {
+        int const b = L - 2 * lv;
+        if (b < 12 || !((bonds >> b) & 1)) break;
+        for (int h = 0; h < (1 << (lv - 1)); ++h) { /* bit t of h: the pair (b + 2 t + 3, b + 2 t + 2) is 11 */
+            int const m = k - 2 * __builtin_popcount((unsigned)h) - 1;
+            if (m < 0 || m > b) continue;
+            int64_t base = 0;
+            int idx = m + 1; /* set bits at or below the pair of this level */
+            for (int t = 0; t < lv - 1; ++t)
+                if ((h >> t) & 1) { base += (int64_t)C[b + 2 * t + 2][idx + 1] + (int64_t)C[b + 2 * t + 3][idx + 2]; idx += 2; }
+            int64_t const r01 = base + (int64_t)C[b][m + 1], r10 = base + (int64_t)C[b + 1][m + 1];
+            chain_range r = {lv, b, (r01 + 511) & ~(int64_t)511, r10 & ~(int64_t)511, r10 - r01, hdr};
+            if (r.a1 <= r.a0) continue;
+            hdr += (r.a1 - r.a0) / 64;
+            out[nr++] = r;
+        }
+    }
+    return nr;
 }
 #define CHAIN_TILE_PLAIN 0x8000 /* bit 63 of a tile-map entry (k_chain_t on fused records): this tile runs on its records, not on wave headers */
 static int tilemap_deal(tile_list const *all, int64_t chunk, uint64_t **out, int64_t *slots_out) {
@@ -2345,31 +2370,50 @@ static int tilemap_deal(tile_list const *all, int64_t chunk, uint64_t **out, int
     *slots_out = slots;
     return 0;
 }
-/* The two tile maps of a paired plan: `pairs` = one entry per paired tile (first row of its first segment, 1024 rows), `rest` =
- * tiles of at most TILE rows over [0, a0), [a1, a0 + d) and [a1 + d, n), cut at the multiples of TILE; a tile that starts or ends
- * off the 64-row grid of the wave headers (the second segments do) is flagged CHAIN_TILE_PLAIN, and one that starts off it ends at
- * the next multiple of 64.  Both are dealt like tilemap_host does.  Every row lies in exactly one tile of the two maps. */
-static int tilemap_paired_host(int64_t n, int TILE, int64_t chunk, int64_t a0, int64_t a1, int64_t d, uint64_t **rest, int64_t *rest_slots,
-                               uint64_t **pairs, int64_t *pair_slots) {
+/* The two tile maps of a paired plan: `pairs` = one entry per paired tile (first row of its first segment | the id of its range << 32,
+ * 1024 rows), in ascending row order over all ranges; `rest` = tiles of at most TILE rows over the rows outside every range's segments
+ * [a0, a1) and [a0 + d, a1 + d), cut at the multiples of TILE; a tile that starts or ends off the 64-row grid of the wave headers (the
+ * second segments do) is flagged CHAIN_TILE_PLAIN, and one that starts off it ends at the next multiple of 64.  Both are dealt like
+ * tilemap_host does, `pairs` in chunks of pair_chunk.  Every row lies in exactly one tile of the two maps. */
+typedef struct { int64_t lo, hi; int id; } chain_span;
+static int chain_span_cmp(void const *pa, void const *pb) {
+    int64_t const a = ((chain_span const *)pa)->lo, b = ((chain_span const *)pb)->lo;
+    return a < b ? -1 : a > b;
+}
+static int tilemap_paired_host(int64_t n, int TILE, int64_t chunk, int64_t pair_chunk, chain_range const *rg, int nr, uint64_t **rest,
+                               int64_t *rest_slots, uint64_t **pairs, int64_t *pair_slots) {
     tile_list all[2];
     memset(all, 0, sizeof(all));
-    int64_t const piece[3][2] = {{0, a0}, {a1, a0 + d}, {a1 + d, n}};
-    int64_t total = 0;
-    for (int p = 0; p < 3; ++p)
-        for (int64_t pos = piece[p][0]; pos < piece[p][1];) {
+    chain_span sp[2 * CHAIN_MAX_RANGES];
+    *rest = *pairs = NULL;
+    if (nr < 1 || nr > CHAIN_MAX_RANGES) return set_error("internal error: %d paired ranges", nr);
+    for (int r = 0; r < nr; ++r) {
+        sp[2 * r] = (chain_span){rg[r].a0, rg[r].a1, r};
+        sp[2 * r + 1] = (chain_span){rg[r].a0 + rg[r].d, rg[r].a1 + rg[r].d, -1};
+    }
+    qsort(sp, (size_t)(2 * nr), sizeof(chain_span), chain_span_cmp);
+    int64_t total = 0, from = 0;
+    int rc = 0;
+    for (int q = 0; q <= 2 * nr && !rc; ++q) {
+        int64_t const to = q < 2 * nr ? sp[q].lo : n;
+        if (to < from || (q < 2 * nr && sp[q].hi > n)) { rc = set_error("internal error: paired ranges overlap"); break; }
+        for (int64_t pos = from; pos < to;) {
             int64_t end = (pos / TILE + 1) * TILE;
             if (pos & 63) end = (pos | 63) + 1;
-            if (end > piece[p][1]) end = piece[p][1];
+            if (end > to) end = to;
             int const plain = (pos & 63) != 0 || ((end & 63) != 0 && end != n);
             tile_push(&all[0], pos, (end - pos) | (plain ? CHAIN_TILE_PLAIN : 0));
             total += end - pos;
             pos = end;
         }
-    for (int64_t i0 = a0; i0 < a1; i0 += 512) { tile_push(&all[1], i0, 1024); total += 1024; }
-    int rc = total == n ? 0 : set_error("internal error: paired tile maps cover %lld of %lld rows", (long long)total, (long long)n);
-    *rest = *pairs = NULL;
+        if (q == 2 * nr) break;
+        if (sp[q].id >= 0)
+            for (int64_t i0 = sp[q].lo; i0 < sp[q].hi; i0 += 512) { tile_push(&all[1], i0 | ((int64_t)sp[q].id << 32), 1024); total += 1024; }
+        from = sp[q].hi;
+    }
+    if (!rc && total != n) rc = set_error("internal error: paired tile maps cover %lld of %lld rows", (long long)total, (long long)n);
     if (!rc) rc = tilemap_deal(&all[0], chunk, rest, rest_slots);
-    if (!rc) rc = tilemap_deal(&all[1], chunk, pairs, pair_slots);
+    if (!rc) rc = tilemap_deal(&all[1], pair_chunk, pairs, pair_slots);
     if (rc) { free(*rest); free(*pairs); *rest = *pairs = NULL; }
     free(all[0].e);
     free(all[1].e);
@@ -2434,13 +2478,38 @@ int64_t ls_amd_test_tilemap(int64_t n, int tile_rows, int64_t chunk, uint64_t **
  * everything, 0 when that basis has no whole paired segment (nothing is filled), < 0 on error.  out[0..4] = n, a0, a1, d, then the
  * slots per XCD of `rest` and `pairs` in out[4], out[5]. */
 int ls_amd_test_tilemap_paired(int L, int weight, int tile_rows, int64_t chunk, uint64_t **rest, uint64_t **pairs, int64_t *out) {
-    int64_t a0, a1, d, n = 1;
+    int64_t n = 1;
+    chain_range r[CHAIN_MAX_RANGES];
     *rest = *pairs = NULL;
-    if (!chain_pair_range(L, weight, &a0, &a1, &d)) return 0;
+    if (chain_pair_ranges(L, weight, 1, ~0ULL, r) != 1) return 0;
     for (int j = 1; j <= weight; ++j) n = n * (L - weight + j) / j;
-    if (tilemap_paired_host(n, tile_rows, chunk, a0, a1, d, rest, &out[4], pairs, &out[5]) != 0) return -1;
-    out[0] = n; out[1] = a0; out[2] = a1; out[3] = d;
+    if (tilemap_paired_host(n, tile_rows, chunk, chunk, r, 1, rest, &out[4], pairs, &out[5]) != 0) return -1;
+    out[0] = n; out[1] = r[0].a0; out[2] = r[0].a1; out[3] = r[0].d;
     return 1;
+}
+/* test hook (host only): the same for up to `levels` levels of a ring (every bond inside a run), with the table of ranges.  Returns
+ * the number of ranges (0: no whole paired segment, nothing is filled), < 0 on error.  out[0..3] = n, slots per XCD of `rest` and of
+ * `pairs`, levels in use; *ranges = six int64 per range, in table order (a tile of `pairs` names its range in bits 32..47): level,
+ * bond, a0, a1, d, first header of its second segments.  Free the three arrays with ls_amd_test_free. */
+int ls_amd_test_tilemap_pair_levels(int L, int weight, int tile_rows, int64_t chunk, int64_t pair_chunk, int levels, uint64_t **rest,
+                                    uint64_t **pairs, int64_t **ranges, int64_t *out) {
+    int64_t n = 1;
+    chain_range r[CHAIN_MAX_RANGES];
+    *rest = *pairs = NULL;
+    *ranges = NULL;
+    int const nr = levels >= 1 ? chain_pair_ranges(L, weight, levels, ~0ULL, r) : 0;
+    if (nr == 0) return 0;
+    for (int j = 1; j <= weight; ++j) n = n * (L - weight + j) / j;
+    int64_t *t = (int64_t *)malloc(sizeof(int64_t) * 6 * (size_t)nr);
+    if (!t) return set_error("out of memory");
+    if (tilemap_paired_host(n, tile_rows, chunk, pair_chunk, r, nr, rest, &out[1], pairs, &out[2]) != 0) { free(t); return -1; }
+    for (int q = 0; q < nr; ++q) {
+        int64_t const row[6] = {r[q].level, r[q].bond, r[q].a0, r[q].a1, r[q].d, r[q].hdr0};
+        memcpy(t + 6 * q, row, sizeof(row));
+    }
+    out[0] = n; out[3] = r[nr - 1].level;
+    *ranges = t;
+    return nr;
 }
 void ls_amd_test_free(void *p) { free(p); }
 /* host-only test hooks of the static index table (lsk_gtab): shape for n keys of L bits, sequential build into a malloc'ed
@@ -2570,10 +2639,12 @@ static int setup_chain_headers(ls_amd_plan *pl, lsk_index index, int64_t n, uint
     pl->chain_row_bytes = headed ? (int)((8 * (uint64_t)n_hdr + 64 * (uint64_t)rec * (uint64_t)plain + (uint64_t)n - 1) / (uint64_t)n) : rec;
     return 0;
 }
-/* Paired tiles (k_chain_pair_t; chain_pair_range, tilemap_paired_host): f64 plans on fused records that the wave headers serve (in use,
+/* Paired tiles (k_chain_pair_t; chain_pair_ranges, tilemap_paired_host): f64 plans on fused records that the wave headers serve (in use,
  * or all ones under LS_AMD_CHAIN_RECORDS=1: the second segments' headers follow; so: 13..32 sites, 32-bit ranks, one partition that starts at row 0, at most one cached pair) of >= 14 sites whose operator has bond
- * L - 2 inside a run and whose basis holds a whole 512-row segment of R01.  The plan's tile map is rebuilt without the paired rows,
- * which get a tile map and a launch of their own; the second segments get headers of their own (they lie off the 64-row grid).
+ * L - 2 inside a run and whose basis holds a whole 512-row segment of some range, down to level LS_AMD_CHAIN_PAIR_LEVELS (at 1: the top
+ * bond alone) and to the first level whose bond is in no run.  The plan's tile map is rebuilt without the paired rows, which get a tile
+ * map (dealt in chunks of LS_AMD_PAIR_TILE_CHUNK, default: as the other map) and a launch of their own; the second segments get headers
+ * of their own (they lie off the 64-row grid), and every tile of that launch carries its range's d and bond next to its entry.
  * Every other plan, and every plan under LS_AMD_CHAIN_PAIRED=0 (A/B runs, tests), is left as it is.  hi = the cached pair's site
  * >= 12 (< 0: none).  No room for the extra arrays: the plan stays unpaired. */
 static int setup_chain_pairs(ls_amd_plan *pl, lsk_index index, int64_t n, uint64_t const *d_reps, int hi, void *stream) {
@@ -2582,26 +2653,52 @@ static int setup_chain_pairs(ls_amd_plan *pl, lsk_index index, int64_t n, uint64
     if ((e && atoi(e) == 0) || !pl->chain_headers_apply || pl->cplx || !pl->d_chain_rec || pl->chain_cached > 1 || pl->chain_row0 != 0 ||
         pl->n_local != 1 || pl->family != FAMILY_DIRECT_PULL)
         return 0;
-    int top = 0;
+    uint64_t bonds = 0; /* bit b: bond (b, b + 1) lies inside an exchange run */
     for (int q = 0; q < pl->dop.runs.n_runs; ++q)
-        if (pl->dop.runs.lo0[q] <= L - 2 && L - 2 < pl->dop.runs.lo0[q] + pl->dop.runs.cnt[q]) top = 1;
-    int64_t a0, a1, d;
-    if (!top || !chain_pair_range(L, pl->dbs.hamming_weight, &a0, &a1, &d) || a1 + d > n) return 0;
+        for (int b = pl->dop.runs.lo0[q]; b < pl->dop.runs.lo0[q] + (pl->dop.runs.cnt[q] & 0xffff) && b < 64; ++b) bonds |= 1ULL << b;
+    char const *le = getenv("LS_AMD_CHAIN_PAIR_LEVELS");
+    int levels = le ? atoi(le) : CHAIN_PAIR_LEVELS_DEFAULT;
+    if (levels < 1) levels = 1;
+    chain_range rg[CHAIN_MAX_RANGES];
+    int const nr = chain_pair_ranges(L, pl->dbs.hamming_weight, levels, bonds, rg);
+    if (nr == 0) return 0;
+    for (int r = 0; r < nr; ++r) if (rg[r].a1 + rg[r].d > n || rg[r].d < 512) return 0;
     uint64_t *rest = NULL, *pairs = NULL;
     int64_t rest_slots = 0, pair_slots = 0;
-    char const *ce = getenv("LS_AMD_TILE_CHUNK");
+    char const *ce = getenv("LS_AMD_TILE_CHUNK"), *pe = getenv("LS_AMD_PAIR_TILE_CHUNK");
     int64_t const chunk = ce ? atoll(ce) : 256; /* (build_tilemap's default for these tiles) */
-    if (tilemap_paired_host(n, lsk_chain_tile_rows(0), chunk > 0 ? chunk : 0, a0, a1, d, &rest, &rest_slots, &pairs, &pair_slots) != 0) return -1;
+    int64_t const pair_chunk = pe ? atoll(pe) : chunk;
+    if (tilemap_paired_host(n, lsk_chain_tile_rows(0), chunk > 0 ? chunk : 0, pair_chunk > 0 ? pair_chunk : 0, rg, nr, &rest, &rest_slots, &pairs,
+                            &pair_slots) != 0)
+        return -1;
+    /* the paired map as the kernel reads it: two words per slot, the entry and d | header of the tile's second segment << 32 |
+     * bond << 59 (lsk_chain_paired) */
+    int64_t const n_hdr = rg[nr - 1].hdr0 + (rg[nr - 1].a1 - rg[nr - 1].a0) / 64;
+    size_t const pair_words = 2 * (size_t)(8 * pair_slots);
+    uint64_t *wide = (uint64_t *)calloc(pair_words, sizeof(uint64_t));
+    if (!wide || n_hdr >= (1LL << 27)) { free(wide); free(rest); free(pairs); return wide ? 0 : set_error("out of memory"); }
+    for (size_t q = 0; q < pair_words / 2; ++q) {
+        uint64_t const en = pairs[q];
+        if (!(en >> 48)) continue;
+        chain_range const *r = &rg[(en >> 32) & 0xffff];
+        int64_t const i0 = (int64_t)(en & 0xffffffffULL);
+        wide[2 * q] = en;
+        wide[2 * q + 1] = (uint64_t)r->d | (uint64_t)(r->hdr0 + (i0 - r->a0) / 64) << 32 | (uint64_t)r->bond << 59;
+    }
+    free(pairs);
+    pairs = wide;
     void *d_rest = NULL, *d_pairs = NULL, *d_hdr = NULL;
-    int64_t const n_b = a1 - a0; /* rows of the second segments: [a0 + d, a1 + d) */
     unsigned long long plain = 0;
     int rc = lsk_malloc(&d_rest, sizeof(uint64_t) * (size_t)(8 * rest_slots > 0 ? 8 * rest_slots : 1)) ||
-             lsk_malloc(&d_pairs, sizeof(uint64_t) * (size_t)(8 * pair_slots)) || lsk_malloc(&d_hdr, 8 * (size_t)(n_b / 64) + 8);
+             lsk_malloc(&d_pairs, sizeof(uint64_t) * pair_words) || lsk_malloc(&d_hdr, 8 * (size_t)n_hdr + 8);
     if (!rc) {
-        unsigned long long *d_plain = (unsigned long long *)((char *)d_hdr + 8 * (size_t)(n_b / 64));
-        rc = lsk_h2d(d_rest, rest, sizeof(uint64_t) * (size_t)(8 * rest_slots)) || lsk_h2d(d_pairs, pairs, sizeof(uint64_t) * (size_t)(8 * pair_slots)) ||
-             lsk_h2d(d_plain, &plain, 8) || lsk_chain_headers(pl->dbs, index, n_b, d_reps + a0 + d, pl->chain_headed, hi, d_hdr, d_plain, stream) ||
-             lsk_sync(stream);
+        unsigned long long *d_plain = (unsigned long long *)((char *)d_hdr + 8 * (size_t)n_hdr);
+        rc = lsk_h2d(d_rest, rest, sizeof(uint64_t) * (size_t)(8 * rest_slots)) || lsk_h2d(d_pairs, pairs, sizeof(uint64_t) * pair_words) ||
+             lsk_h2d(d_plain, &plain, 8);
+        for (int r = 0; r < nr && !rc; ++r) /* rows of the range's second segments: [a0 + d, a1 + d) */
+            rc = lsk_chain_headers(pl->dbs, index, rg[r].a1 - rg[r].a0, d_reps + rg[r].a0 + rg[r].d, pl->chain_headed, hi,
+                                   (char *)d_hdr + 8 * (size_t)rg[r].hdr0, d_plain, stream);
+        if (!rc) rc = lsk_sync(stream);
         if (rc) { free(rest); free(pairs); lsk_free(d_rest); lsk_free(d_pairs); lsk_free(d_hdr); return dev_error(); }
     }
     free(rest);
@@ -2620,9 +2717,9 @@ static int setup_chain_pairs(ls_amd_plan *pl, lsk_index index, int64_t n, uint64
     pl->tilemap_pair.entries = (uint64_t const *)d_pairs;
     pl->tilemap_pair.slots_per_xcd = pair_slots;
     pl->d_chain_hdr_b = d_hdr;
-    pl->chain_pair_d = d;
-    pl->chain_pair_a0 = a0;
-    pl->chain_pair_rows = 2 * (a1 - a0);
+    memset(pl->chain_pair_rows, 0, sizeof(pl->chain_pair_rows));
+    for (int r = 0; r < nr; ++r) pl->chain_pair_rows[rg[r].level] += 2 * (rg[r].a1 - rg[r].a0);
+    pl->chain_pair_levels = rg[nr - 1].level;
     pl->chain_paired = 1;
     return 0;
 }
@@ -4008,8 +4105,13 @@ int ls_amd_plan_row_bytes(ls_amd_plan const *pl) {
 }
 /* rows that the plan's paired launch computes (k_chain_pair_t, setup_chain_pairs); 0: the plan runs on k_chain_t alone, or not on it */
 int64_t ls_amd_plan_chain_paired_rows(ls_amd_plan const *pl) {
-    return pl->has_chain && pl->chain_paired ? pl->chain_pair_rows : 0;
+    return pl->has_chain && pl->chain_paired ? pl->chain_pair_rows[1] : 0;
 }
+/* ... across the bond of `level` (1: bond L - 2, 2: L - 4, ...), and the deepest level at which the plan pairs rows (0: unpaired) */
+int64_t ls_amd_plan_chain_paired_rows_at(ls_amd_plan const *pl, int level) {
+    return pl->has_chain && pl->chain_paired && level >= 1 && level <= CHAIN_MAX_PAIR_LEVELS ? pl->chain_pair_rows[level] : 0;
+}
+int ls_amd_plan_chain_pair_levels(ls_amd_plan const *pl) { return pl->has_chain && pl->chain_paired ? pl->chain_pair_levels : 0; }
 int64_t ls_amd_plan_nnz(ls_amd_plan const *pl) { return pl->nnz; }
 int ls_amd_plan_send_counts(ls_amd_plan const *pl, int round, int64_t *counts) {
     if (pl->family != FAMILY_TILE) { for (int d = 0; d < pl->P; ++d) counts[d] = 0; return 0; }
@@ -4291,7 +4393,7 @@ int ls_amd_matvec(ls_amd_plan *pl, void const *const *d_x, void *const *d_y, voi
                           pl->d_chain_cache, pl->chain_v[0], pl->chain_v[1], pl->d_chain_wave, stream));
             if (pl->chain_paired) /* the rows that tile map leaves out (setup_chain_pairs) */
                 DEV(lsk_chain_paired(pl->dop, pl->dbs, pl->tilemap_pair, ps->count, pl->d_chain_rec, d_x[0], d_y[0], pl->chain_cached, pl->chain_v[0],
-                                     pl->d_chain_wave, pl->chain_pair_d, pl->chain_pair_a0, pl->d_chain_hdr_b, NBITS(pl->op->basis) - 2, stream));
+                                     pl->d_chain_wave, pl->d_chain_hdr_b, stream));
         } else if (pl->has_pairs)
             DEV(lsk_pairs(pl->pairs, pl->dbs.hamming_weight, pl->cplx, pl->tilemap, ps->count, d_x[0], d_y[0], stream));
         else if (pl->has_hubbard)

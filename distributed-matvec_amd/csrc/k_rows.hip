@@ -679,6 +679,13 @@ extern "C" int lsk_direct_gx(lsk_operator op, lsk_basis bs, lsk_index ix, int cp
 // k_chain_t, in a launch of its own; its tiles that start or end off the grid are flagged to run on their records.  Measured on
 // chain_32: 48.5 -> 46.9 GB per matvec and 2 % of its time (profiles/chain_paired_tiles_ab.txt); with pair 11 always gathered: no
 // gain.  Every term enters a row's sum where k_chain_t adds it, so the two kernels give the same y to the bit.
+// Pairing levels: the same holds one pair of site bits further down.  Read the top bits as disjoint pairs (L-1, L-2), (L-3, L-4),
+// ...: levels 1, 2, ...  A row whose higher pairs are all 00 or 11 and whose level's pair is 01 has its partner across bond
+// L - 2 level exactly D' rows further on, range by range (one range per pattern of the higher pairs; host.c: chain_pair_ranges), and
+// no row belongs to two levels.  A paired tile carries its range's D and bond next to its map entry, so one launch serves all
+// ranges.  A deeper bond's term is added after the far pairs of its run, not between them: up to level - 1 anti-aligned pairs lie
+// above it, so those rows differ from k_chain_t's in the last bits (measured 2.8e-16 of max |y| on chain_32).  chain_32: 51.6 % of
+// the rows pair at level 1, 76.5 % down to level 2, 94.4 % down to level 4 (profiles/chain_pair_levels_ab.txt).
 // ---------------------------------------------------------------------------------------------
 constexpr int kChainHalo = 512;    // >= C(11, 5)
 constexpr int kChainLdsPairs = 12; // pairs lo < 12 are served from the LDS window
@@ -705,9 +712,12 @@ constexpr int kChainFarC = 6; // complex: 6 x 16 bytes in flight per lane
 // answers 7 -- a straggler round of blocks, measured +24 % (13.1 vs 10.7 ms on chain_32)
 // (f64: 7 blocks = what 22.5 KB of LDS admit; c128: bounds 4 / 5 / 6 measure 14.56 / 14.55 / 14.57 ms; the 64-bit f64
 // instantiations -- 33..64 sites, no in-tree config -- need 6: at 7 they spill 20-40 bytes per lane to scratch)
-// what a paired launch adds (PAIR, below): d = rows between the two segments of a tile, a0 = first row of the paired part of R01,
-// hdr_b = wave headers of the paired part of R10 (two u32 per 64 rows from its first row), bond = L - 2
-struct chain_pair_args { int64_t d, a0; uint32_t const *hdr_b; int bond; };
+// what a paired launch adds (PAIR, below): its tile map has two u64 per tile -- the entry as the host deals it (first row in bits
+// 0..31, its range in bits 32..47, 1024 rows) and what the tile needs of its range, so that nothing is looked up before the first
+// loads go out: bits 0..31 = d, the rows between the two segments of the tile; bits 32..58 = the header of the tile's second segment
+// in hdr_b; bits 59..63 = the range's bond.  hdr_b = the wave headers of all second segments (two u32 per 64 rows, each range's made
+// from its second segments' first row on, range after range)
+struct chain_pair_args { uint32_t const *hdr_b; };
 template <typename W, typename R, bool CPLX, int TILE, bool REC, bool PAIR>
 __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk_term const *__restrict__ diag,
                                                     int hamming_weight, uint4 const *__restrict__ g_img, int img16, int kc,
@@ -717,6 +727,7 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
                                                     void *__restrict__ y_v, int n_cached,
                                                     R const *__restrict__ cache, double cv0, double cv1, int64_t row0,
                                                     int64_t n_x, uint32_t const *__restrict__ wave_plan, chain_pair_args const &pr) {
+    uint32_t const *__restrict__ const pair_hdr = pr.hdr_b;
     typedef typename ChainX<CPLX>::type X;
     typedef WordTraits<W> WT;
     constexpr int NB = ChainTraits<W, R>::NB;
@@ -755,6 +766,7 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
     const int64_t blocks_per_xcd = gridDim.x >> 3;
     const int lane = threadIdx.x & 63;
     tilemap += (int64_t)xcd * slots_per_xcd;
+    if constexpr (PAIR) tilemap += (int64_t)xcd * slots_per_xcd; // (two words per tile)
     uint32_t const *__restrict__ reps32 = reinterpret_cast<uint32_t const *>(reps);
     // Wave headers (HDR: 32-bit states and ranks; lsk_chain_headers): wave_plan = the word table, kChainWords x u32 in (weight,
     // value) order: 12-bit word | its rank after the cached pair's low site is flipped << 16 | that site's bit << 31; then two
@@ -767,17 +779,22 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
     constexpr bool HDR = REC || (CPLX && sizeof(W) == 4 && sizeof(R) == 4);
     constexpr int NSUB = TILE / kBlock;
     for (int64_t t = blockIdx.x >> 3; t < slots_per_xcd; t += blocks_per_xcd) {
-        const uint64_t slot = tilemap[t];
+        const uint64_t slot = tilemap[PAIR ? 2 * t : t];
         // (fused records: bits 59..63 of an entry are flags, kChainTilePlain = this tile starts or ends off the 64-row grid of the
         // wave headers and runs on its records; a paired tile is always whole)
         const int cnt_slot = REC ? (int)((slot >> 48) & 0x7ffu) : (int)(slot >> 48);
         if (cnt_slot == 0) continue; // block-uniform
         const int cnt = PAIR ? TILE : cnt_slot;
-        const int64_t i0 = (int64_t)(slot & 0xffffffffffffULL);
+        const int64_t i0 = (int64_t)(slot & (PAIR ? 0xffffffffULL : 0xffffffffffffULL)); // (paired tiles: bits 32..47 = the range)
+        // (paired tiles: the tile's range -- block-uniform, scalar loads)
+        const uint64_t slot1 = PAIR ? tilemap[2 * t + 1] : 0;
+        const int64_t pr_d = PAIR ? (int64_t)(uint32_t)slot1 : 0;
+        const uint32_t pr_hdr = PAIR ? (uint32_t)(slot1 >> 32) & 0x7ffffffu : 0u;
+        const int pr_bond = PAIR ? (int)(slot1 >> 59) : -1;
         const int64_t w0 = (row0 + i0 - HALO) & ~(int64_t)1; // first row of the window (even; may be < 0)
-        const int64_t w0b = PAIR ? (i0 + pr.d - HALO) & ~(int64_t)1 : 0; // (paired tiles: of the second segment's window)
+        const int64_t w0b = PAIR ? (i0 + pr_d - HALO) & ~(int64_t)1 : 0; // (paired tiles: of the second segment's window)
         // row of the tile that this thread works on in iteration s, as an offset from i0
-        auto row_off = [&](int s) -> int { return PAIR ? (s >> 1) * (int)pr.d + (s & 1) * kBlock + (int)threadIdx.x : s * kBlock + threadIdx.x; };
+        auto row_off = [&](int s) -> int { return PAIR ? (s >> 1) * (int)pr_d + (s & 1) * kBlock + (int)threadIdx.x : s * kBlock + threadIdx.x; };
         W a_next = 0;
         R t0_next = kNone, t1_next = kNone;
         // REC: `reps` is the plan's fused record array, row -> sigma (low word) | partner rank of the first cached pair
@@ -803,11 +820,12 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
         uint32_t hq = ~0u;
         if (PAIR) {
             // iterations 0-1 walk the first segment (today's headers), 2-3 the second, whose rows are D further on and off the
-            // 64-row grid: its headers were made from its own first row on (pr.hdr_b)
+            // 64-row grid: its headers were made from its own first row on (hdr_b)
             const uint32_t s = (uint32_t)lane % NSUB;
             const uint32_t wr = (threadIdx.x >> 6) + (s & 1u) * (kBlock / 64);
             const uint32_t word = ((uint32_t)lane / NSUB) % 2;
-            hq = (s >> 1) ? pr.hdr_b[2 * ((uint32_t)((i0 - pr.a0) >> 6) + wr) + word] : wave_plan[kChainWords + 2 * ((uint32_t)(i0 >> 6) + wr) + word];
+            hq = (s >> 1) ? pair_hdr[2u * (pr_hdr + wr) + word]
+                          : wave_plan[kChainWords + 2 * ((uint32_t)(i0 >> 6) + wr) + word];
         } else if (HDR && !(REC && (slot >> 63))) {
             const uint32_t hw = 2 * (uint32_t)(i0 >> 6) + 2 * ((threadIdx.x >> 6) + (uint32_t)(lane % NSUB) * (kBlock / 64)) + (lane / NSUB) % 2;
             if (((int64_t)(hw >> 1) << 6) < n) hq = wave_plan[kChainWords + hw];
@@ -844,7 +862,7 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
         }
         __syncthreads();
         const int own0 = (int)(row0 + i0 - w0);
-        const int own0b = PAIR ? WSEG + (int)(i0 + pr.d - w0b) : 0; // first row of the second segment in s_x
+        const int own0b = PAIR ? WSEG + (int)(i0 + pr_d - w0b) : 0; // first row of the second segment in s_x
         X y_pending = cx_zero<X>(); // stored one iteration late (see k_chain)
         int r_pending = -1;         // (row of the tile: one register, not two)
 #pragma unroll 1
@@ -886,7 +904,7 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
                 const W adiff = a0 ^ readlane_t<W>(a, 63);
                 ubit = adiff == 0 ? 0 : (int)(8 * sizeof(W)) - (sizeof(W) == 4 ? __clz((int)(uint32_t)adiff) : __clzll((long long)(uint64_t)adiff));
             }
-            // (paired tiles: jp = this row's place in the OTHER segment's core, where its partner across bond L - 2 lies)
+            // (paired tiles: jp = this row's place in the OTHER segment's core, where its partner across the range's bond lies)
             const int jl = PAIR ? (sub & 1) * kBlock + (int)threadIdx.x : 0;
             const int jr = PAIR ? ((sub >> 1) ? own0b : own0) + jl : own0 + (int)(i - i0);
             const int jp = PAIR ? ((sub >> 1) ? own0 : own0b) + jl : 0;
@@ -905,7 +923,7 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
                 const int lo0 = runs.lo0[q];
                 int lo_end = lo0 + runs.cnt[q];
                 const double vr = runs.v_re[q];
-                const bool top_here = PAIR && lo0 <= pr.bond && pr.bond < lo_end; // the run of bond L - 2
+                const bool bond_here = PAIR && lo0 <= pr_bond && pr_bond < lo_end; // the run of the range's bond
                 int k = WT::popc(a & (W)(((uint64_t)1 << lo0) - 1));
                 int lo = lo0;
                 const int e1 = lo_end < LDSP ? lo_end : LDSP;
@@ -926,9 +944,9 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
                     const int ps = in_run ? p : 0;
                     const W hi = a0 >> ps;
                     const bool bit = hi & 1;
-                    // (paired tiles: bond L - 2 is anti-aligned in every row and is served from LDS below; the two top bits are
-                    // the same in all rows of a segment, so that bond is always among these wave-uniform ones)
-                    const bool act = in_run && (((hi >> 1) & 1) != (W)bit) && !(PAIR && p == pr.bond);
+                    // (paired tiles: the range's bond is anti-aligned in every row and is served from LDS below; all rows of a segment
+                    // share the bits from the bond up, so that bond is always among these wave-uniform ones)
+                    const bool act = in_run && (((hi >> 1) & 1) != (W)bit) && !(PAIR && p == pr_bond);
                     const int kk = hamming_weight - WT::popc(hi); // set bits below p
                     const R d = s_binom[ps * kc + (kk < 0 ? 0 : kk)];
                     off = bit ? d : (R)(0 - d);
@@ -1024,7 +1042,12 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
 #pragma unroll
                     for (int u = 0; u < 4; ++u) cx_fma(vr, xw[u], acc);
                 }
-                if (top_here) cx_fma(vr, s_x[jp], acc); // (block-uniform; bond L - 2 is the last far pair of its run: k_chain_t's order)
+                // (block-uniform.  The top bond is the last far pair of its run: k_chain_t's order.  A deeper range's bond has up to
+                // level - 1 anti-aligned pairs above it, whose terms k_chain_t adds after this one: those rows differ from k_chain_t's
+                // in the last bits.  Giving the bond its own place among the gathers -- its slot filled from LDS, or a compare per
+                // slot when the terms are added -- measured 0.15 and 0.03 ms slower per matvec on chain_32, more than the deeper
+                // levels gain: profiles/chain_pair_levels_ab.txt)
+                if (bond_here) cx_fma(vr, s_x[jp], acc);
                 // ---- middle pairs (and far pairs of a wave that straddles two high parts) --------------
 #pragma unroll 4
                 for (; lo < lo_end; ++lo) {
@@ -1056,7 +1079,7 @@ __global__ __launch_bounds__(kBlock, (CPLX || sizeof(R) == 8 ? 5 : (sizeof(W) ==
                                                     R const *__restrict__ cache, double cv0, double cv1, int64_t row0,
                                                     int64_t n_x, uint32_t const *__restrict__ wave_plan) {
     chain_rows<W, R, CPLX, TILE, REC, false>(runs, n_diag, diag, hamming_weight, g_img, img16, kc, near_off, tilemap, slots_per_xcd, n, reps, x_v, y_v,
-                                             n_cached, cache, cv0, cv1, row0, n_x, wave_plan, chain_pair_args{0, 0, nullptr, -1});
+                                             n_cached, cache, cv0, cv1, row0, n_x, wave_plan, chain_pair_args{nullptr});
 }
 // The paired launch of the headline shape (32-bit states and ranks, f64, fused records + wave headers, one cached pair at most, the
 // whole basis in one partition): the same rows body over tiles of two 512-row segments that bond L - 2 maps onto each other.
@@ -1064,10 +1087,10 @@ __global__ __launch_bounds__(kBlock, 7) void k_chain_pair_t(lsk_runs runs, int n
                                                             uint4 const *__restrict__ g_img, int img16, int kc, int near_off,
                                                             uint64_t const *__restrict__ tilemap, int64_t slots_per_xcd, int64_t n,
                                                             uint64_t const *__restrict__ reps, void const *__restrict__ x_v,
-                                                            void *__restrict__ y_v, int n_cached, double cv0, chain_pair_args pr,
+                                                            void *__restrict__ y_v, int n_cached, double cv0, uint32_t const *__restrict__ pair_hdr,
                                                             uint32_t const *__restrict__ wave_plan) {
     chain_rows<uint32_t, uint32_t, false, 1024, true, true>(runs, n_diag, diag, hamming_weight, g_img, img16, kc, near_off, tilemap, slots_per_xcd, n,
-                                                            reps, x_v, y_v, n_cached, nullptr, cv0, 0.0, 0, n, wave_plan, pr);
+                                                            reps, x_v, y_v, n_cached, nullptr, cv0, 0.0, 0, n, wave_plan, chain_pair_args{pair_hdr});
 }
 
 // cache[i] = rank of reps[i] ^ xmask when exactly one of the two bits of xmask is set in reps[i], else ~0;
@@ -1302,19 +1325,17 @@ extern "C" int lsk_chain(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, 
 #undef LSK_CHAIN_ARGS
 }
 extern "C" int lsk_chain_paired(lsk_operator op, lsk_basis bs, lsk_tilemap tm_pair, int64_t n, uint64_t const *records, void const *x, void *y,
-                                int n_cached, double cv0, void const *wave_plan, int64_t d, int64_t a0, void const *hdr_b, int bond, void *stream) {
+                                int n_cached, double cv0, void const *wave_plan, void const *hdr_b, void *stream) {
     if (n == 0 || tm_pair.slots_per_xcd == 0) return 0;
-    if (bs.number_sites < 14 || bs.number_sites > 32 || bond != bs.number_sites - 2 || n_cached > 1 || !wave_plan || !hdr_b || !tm_pair.entries ||
-        d < 512 || (a0 & 511) || a0 + d + 512 > n) {
+    if (bs.number_sites < 14 || bs.number_sites > 32 || n_cached > 1 || !wave_plan || !hdr_b || !tm_pair.entries || n >= 0xffffffffLL) {
         snprintf(g_err, sizeof(g_err), "lsk_chain_paired: plan out of range");
         return -1;
     }
     ChainImage img;
     if (chain_lds_image(4, ChainTraits<uint32_t, uint32_t>::NB, bs.hamming_weight, 8, 11, &img) != 0) return -1;
-    chain_pair_args pr = {d, a0, (uint32_t const *)hdr_b, bond};
     hipLaunchKernelGGL(k_chain_pair_t, dim3((unsigned)(tm_pair.slots_per_xcd * 8)), dim3(kBlock), (size_t)img.bytes, (hipStream_t)stream, op.runs,
                        op.n_diag, op.diag, bs.hamming_weight, img.dev, img.bytes / 16, img.kc, img.near_off, tm_pair.entries,
-                       tm_pair.slots_per_xcd, n, records, x, y, n_cached, cv0, pr, (uint32_t const *)wave_plan);
+                       tm_pair.slots_per_xcd, n, records, x, y, n_cached, cv0, (uint32_t const *)hdr_b, (uint32_t const *)wave_plan);
     LSK_LAUNCH_CHECK();
     return 0;
 }

@@ -275,12 +275,14 @@ int lsk_chain(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, int wide_ra
               int64_t n, uint64_t const *reps, int64_t row0, int64_t n_x, void const *x, void *y, int n_cached,
               void const *cache, double cv0, double cv1, void const *wave_plan, void *stream);
 /* The paired launch (k_chain_pair_t) next to lsk_chain() of a plan with 32-bit states and ranks, f64 vectors, fused records and wave
- * headers, row0 == 0 and n_x == n: every non-empty entry of tm_pair is the first row i0 of a tile of two 512-row segments, rows
- * [i0, i0 + 512) and [i0 + d, i0 + d + 512), which bond `bond` (= sites - 2, inside one of the operator's runs) maps onto each other
- * row by row; the plan's other tile map leaves those rows out.  a0 = the lowest i0 (a multiple of 512), hdr_b = lsk_chain_headers of
- * the rows from a0 + d on (the second segments lie off the 64-row grid of the plan's headers). */
+ * headers, row0 == 0 and n_x == n.  tm_pair holds TWO u64 per slot (8 lists of 2 * slots_per_xcd words): the entry of the tile -- its
+ * first row i0 in bits 0..31, its range in bits 32..47, 1024 rows; 0 = empty slot -- and d | h << 32 | bond << 59: the rows
+ * [i0, i0 + 512) and [i0 + d, i0 + d + 512) are mapped onto each other row by row by `bond`, a far pair (>= 12) inside one of the
+ * operator's runs, and the wave headers of rows i0 + d ... are entries h ... of hdr_b (8 bytes each; h < 2^27).  hdr_b = the
+ * lsk_chain_headers of every range's second segments, each made from that range's first such row on (they lie off the 64-row grid of
+ * the plan's headers).  The plan's other tile map leaves all those rows out. */
 int lsk_chain_paired(lsk_operator op, lsk_basis bs, lsk_tilemap tm_pair, int64_t n, uint64_t const *records, void const *x, void *y,
-                     int n_cached, double cv0, void const *wave_plan, int64_t d, int64_t a0, void const *hdr_b, int bond, void *stream);
+                     int n_cached, double cv0, void const *wave_plan, void const *hdr_b, void *stream);
 /* ---- staged row kernel for arbitrary exchange pairs (k_pairs_t, k_rows.hip): Heisenberg / XXZ on any lattice -------------
  * pairs are sorted by class: [0, n_near) both sites below bit 11, [n_near, n_near + n_str) i < 11 <= j, then both >= 11 */
 #define LSK_MAX_PAIRS 128

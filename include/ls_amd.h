@@ -891,6 +891,19 @@ int64_t ls_amd_plan_chain_paired_rows(ls_amd_plan const *pl);
  * runs on its records).  Returns 1 (out[0..5] = rows, first and one-past-last paired row of the first segments, d, slots per XCD of
  * rest and of pairs), 0 when the basis has no whole paired segment, < 0 on error; free both with ls_amd_test_free. */
 int ls_amd_test_tilemap_paired(int L, int weight, int tile_rows, int64_t chunk, uint64_t **rest, uint64_t **pairs, int64_t *out);
+/* Pairing levels.  The top site bits read as disjoint pairs (L-1, L-2), (L-3, L-4), ... are levels 1, 2, ...; a row is paired across
+ * the bond L - 2 level of the first level, from the top, whose two bits differ (LS_AMD_CHAIN_PAIR_LEVELS=n stops at level n; 1 = the
+ * top bond alone).  ls_amd_plan_chain_paired_rows_at: the rows paired at `level` (level 1: ls_amd_plan_chain_paired_rows);
+ * ls_amd_plan_chain_pair_levels: the deepest level at which the plan pairs rows, 0 for an unpaired plan. */
+int64_t ls_amd_plan_chain_paired_rows_at(ls_amd_plan const *pl, int level);
+int ls_amd_plan_chain_pair_levels(ls_amd_plan const *pl);
+/* Host-only test hook: the two tile maps of ls_amd_test_tilemap_paired for up to `levels` levels of a ring (every bond in a run), the
+ * paired map dealt in chunks of pair_chunk, and the table of ranges.  Returns the number of ranges (0: no whole paired segment,
+ * nothing is filled; < 0 on error).  out[0..3] = rows, slots per XCD of rest and of pairs, deepest level in use.  *ranges = six int64
+ * per range in table order -- level, bond, first and one-past-last row of its first segments, d, first header of its second
+ * segments -- and a tile of `pairs` holds its range's place in that table in bits 32..47.  Free all three with ls_amd_test_free. */
+int ls_amd_test_tilemap_pair_levels(int L, int weight, int tile_rows, int64_t chunk, int64_t pair_chunk, int levels, uint64_t **rest,
+                                    uint64_t **pairs, int64_t **ranges, int64_t *out);
 void ls_amd_test_free(void *p);
 /* Host-only test hook: the near-window search of the staged pull kernel for projected bases (k_tile_pull): position of
  * `key` among the ascending reps[0, n) (n <= 1280, stored as saturating 32-bit offsets from reps[0] exactly as a tile
