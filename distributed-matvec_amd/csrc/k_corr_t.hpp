@@ -3,8 +3,9 @@
 // ones (FERMI = true; the plans call that family "k_corr_hop_fermi").
 //     R[i][j] = sum over the rows r with bit i set and bit j clear of  conj(psi_r) / n(r) * <s|psi>,   s = r ^ 1 << i ^ 1 << j
 // with <s|psi> = chi(g0) [sign(g0, s)] n(rep s) psi[index(rep s)], g0 s = rep s: the matrix element k_cross_pull computes in its
-// stages B1 / B2, with source = target.  It is the row loop of k_cross_pull; a few ordered pairs (i, j) per pass, uniform across the
-// block, take the place of the flip-mask groups.  What differs from there:
+// stages B1 / B2, with source = target (B1 through the same function, sector_project of k_cross_t.hpp).  It is the row loop of
+// k_cross_pull; a few ordered pairs (i, j) per pass, uniform across the block, take the place of the flip-mask groups.  What
+// differs from there:
 //   - the packet list is compacted in a FIXED order (pair, then wave, then lane: the counts of every (pair, wave) go through LDS
 //     and every thread takes its offsets from their prefix sums), so the packets of a pair lie one after another and a packet
 //     does not depend on the order in which the waves arrive;
@@ -16,7 +17,7 @@
 #pragma once
 #include <cstdlib>
 
-#include "k_cross_t.hpp" // cross_index, and through it lsk_dev.hpp / lsk_fermi.hpp
+#include "k_cross_t.hpp" // sector_project, cross_index, and through it lsk_dev.hpp / lsk_fermi.hpp
 
 constexpr int kCorrPP = 8;                   // ordered pairs per pass
 constexpr int kCorrCap = kBlock * kCorrPP;   // packets a pass of one tile can generate
@@ -117,15 +118,11 @@ __global__ __launch_bounds__(kBlock) void k_corr_hop(lsk_basis bs, lsk_group_ele
             if (tid == 0) s_off[kCorrPP] = run;
             __syncthreads();
             const int np = run; // (every thread summed the same counts)
-            // ---- stage B1: project every packet (general K4: minimum, character, stabiliser norm) -- k_cross_pull's -------------
+            // ---- stage B1: project every packet (sector_project, k_cross_t.hpp) ---------------------------------------------------
             if (project) {
                 for (int e = tid; e < np; e += kBlock) {
-                    W rep; double chr, chi, stab;
-                    if constexpr (FERMI) fermi_state_info_w<W, PM1>(bs, elems, s_beta[e], rep, chr, chi, stab);
-                    else state_info_w<W, PM1>(bs, elems, s_beta[e], rep, chr, chi, stab);
-                    const double n2 = stab * bs.inv_order;
-                    if (!(n2 > 1e-12)) { s_row[e] = 0xffff; continue; } // zero norm: contributes nothing
-                    const double nb = sqrt(n2);
+                    W rep; double chr, chi, nb;
+                    if (!sector_project<W, PM1, FERMI>(bs, elems, s_beta[e], rep, chr, chi, nb)) { s_row[e] = 0xffff; continue; }
                     s_beta[e] = rep;
                     if (PM1) s_val[NC * e] = chr * nb;
                     else { s_val[2 * e] = chr * nb; s_val[2 * e + 1] = -chi * nb; } // chi(g0) = conj(chr, chi), times n(rep)

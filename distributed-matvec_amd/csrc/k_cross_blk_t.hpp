@@ -1,7 +1,8 @@
 // k_cross_blk_t.hpp -- the block form of the cross-sector pull kernel: Y[:, k] = A X[:, k] for the K columns of
 // an (n_src, K) block, k_cross_pull_blk.  k_cross_blk.hip instantiates it for the bases without permutation signs (FERMI = false),
 // k_cross_blk_fermi.hip for the projected fermionic ones (FERMI = true; "k_cross_pull_blk_fermi").  The formulation is that of
-// k_cross_pull (k_cross_t.hpp), whose stages A, B1 and the look-up of B2 are repeated here word for word -- they do not depend on x:
+// k_cross_pull (k_cross_t.hpp), whose stages A, B1 and the look-up of B2 are repeated here -- they do not depend on x -- with the slot
+// allocation of A and the core of B1 as the same functions (cross_wave_slot, sector_project) and the look-up word for word:
 // one target row per thread, the adjoint's flip-mask groups expanded into the LDS packet list kGCCross groups per pass, every packet
 // projected into the source basis and resolved to (source index, coefficient) ONCE.  Only the tail of B2 differs: a resolved packet
 // gathers a chunk of kCrossKC columns of X -- with interleaved columns (strides (K, 1)) 64 B (f64) or 128 B (c128) of consecutive
@@ -92,12 +93,8 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull_blk(int n_groups, lsk_gro
                 double cr = 0.0, ci = 0.0;
                 if (valid) term_sum<REAL>(terms, G.begin, G.end, a, cr, ci);
                 const bool act = valid && (fabs(cr) > tiny || (!REAL && fabs(ci) > tiny));
-                const unsigned long long ball = __ballot(act);
-                int base = 0;
-                if (lane == 0 && ball) base = atomicAdd(&s_n, __popcll(ball));
-                base = __shfl(base, 0);
+                const int slot = cross_wave_slot(act, lane, &s_n);
                 if (act) {
-                    const int slot = base + __popcll(ball & ((1ULL << lane) - 1));
                     s_beta[slot] = a ^ G.x;
                     s_row[slot] = (uint16_t)tid;
                     if (RC) s_coef[slot] = cr * inv_na;
@@ -109,12 +106,8 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull_blk(int n_groups, lsk_gro
             // ---- stage B1: project every packet into the SOURCE basis (general K4: minimum, character, stabiliser norm) --
             if (project) {
                 for (int e = tid; e < n; e += kBlock) {
-                    W rep; double chr, chi, stab;
-                    if constexpr (FERMI) fermi_state_info_w<W, PM1>(sbs, elems, (W)s_beta[e], rep, chr, chi, stab);
-                    else state_info_w<W, PM1>(sbs, elems, (W)s_beta[e], rep, chr, chi, stab);
-                    const double n2 = stab * sbs.inv_order;
-                    if (!(n2 > 1e-12)) { s_row[e] = 0xffff; continue; } // zero norm in the source sector: contributes nothing
-                    const double nb = sqrt(n2);
+                    W rep; double chr, chi, nb;
+                    if (!sector_project<W, PM1, FERMI>(sbs, elems, (W)s_beta[e], rep, chr, chi, nb)) { s_row[e] = 0xffff; continue; }
                     s_beta[e] = (uint64_t)rep;
                     if (RC) s_coef[e] = s_coef[e] * chr * nb;
                     else { // times chi1(g0) = conj(chr, chi), times n1(rep)

@@ -20,24 +20,5 @@ extern "C" int lsk_cross_fermi_pull(int n_groups, lsk_group const *groups, lsk_t
     }
     if (n_dst <= 0 || n_groups <= 0) return 0;
     if (!gt.entries || gt.L != src.number_sites) { snprintf(g_err, sizeof(g_err), "%s: a projected fermionic source is looked up in its static index table", __func__); return -1; }
-    if (!cplx && !(is_real && src.chars_pm1)) { snprintf(g_err, sizeof(g_err), "%s: f64 needs a real operator and +-1 characters", __func__); return -1; }
-    const int64_t work_blocks = (n_dst + kBlock - 1) / kBlock;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 g(1), b(kBlock);
-#define LSK_CXF_ARGS n_groups, groups, terms, src, src.elems, six, gt, n_dst, dst_reps, dst_norms, (double const *)x, (double *)y, tiny, d_count, d_err
-#define LSK_CXF_ONE(W, PM1, CPLX, REAL)                                                                                                  \
-    do { g.x = resident_grid(k_cross_pull<W, PM1, CPLX, REAL, true>, work_blocks); hipLaunchKernelGGL((k_cross_pull<W, PM1, CPLX, REAL, true>), g, b, 0, s, LSK_CXF_ARGS); } while (0)
-    // {32, 64-bit words} x {f64 (real terms, +-1 characters) | c128 x {+-1, complex characters} x {real, complex terms}}: 10 kernels
-#define LSK_CXF_LAUNCH(W)                                                                                                                \
-    do {                                                                                                                                 \
-        if (!cplx) LSK_CXF_ONE(W, true, false, true);                                                                                    \
-        else if (src.chars_pm1) { if (is_real) LSK_CXF_ONE(W, true, true, true); else LSK_CXF_ONE(W, true, true, false); }               \
-        else { if (is_real) LSK_CXF_ONE(W, false, true, true); else LSK_CXF_ONE(W, false, true, false); }                                \
-    } while (0)
-    if (src.number_sites <= 32) LSK_CXF_LAUNCH(uint32_t); else LSK_CXF_LAUNCH(uint64_t);
-#undef LSK_CXF_LAUNCH
-#undef LSK_CXF_ONE
-#undef LSK_CXF_ARGS
-    LSK_LAUNCH_CHECK();
-    return 0;
+    return cross_pull_launch<true>(__func__, n_groups, groups, terms, is_real, src, six, gt, cplx, n_dst, dst_reps, dst_norms, x, y, tiny, d_count, d_err, stream);
 }

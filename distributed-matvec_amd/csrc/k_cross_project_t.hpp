@@ -13,8 +13,8 @@
 // and no floating-point atomics at all, a fixed order of the sum: two applies return the same bytes (LDS adds in order of arrival
 // would not, with |G2| times as many summands per row as a restricted plan has).  The error flag keeps its meaning: an image with
 // non-zero source norm that is not in the source basis.
-// The stages are restated here, not shared as functions with k_cross_pull: the machine code of the k_cross_pull instantiations is
-// pinned (kernel_isa.json), and this kernel has no emitting mode.
+// The slot allocation of stage A and the core of B1 are the functions of k_cross_t.hpp that k_cross_pull runs on (cross_wave_slot,
+// sector_project); the look-up of B2 is restated (see there), and this kernel has no emitting mode.
 // PM1: the SOURCE's characters are +-1 (integer stabiliser sums in stage B1); TPM1: the TARGET's are (w is real); REAL: real terms.
 // The coefficient of a packet stays real exactly when all three hold (RC), the only form f64 admits.  FERMI: either basis is a
 // projected fermionic one -- the target's elements then carry sign(g, r') (where the target has a sign table) and stage B1 projects
@@ -90,12 +90,8 @@ __global__ __launch_bounds__(kBlock) void k_cross_project(int n_groups, lsk_grou
                         double cr = 0.0, ci = 0.0;
                         if (row) term_sum<REAL>(terms, G.begin, G.end, a, cr, ci);
                         const bool act = row && (fabs(cr) > tiny || (!REAL && fabs(ci) > tiny));
-                        const unsigned long long ball = __ballot(act);
-                        int base = 0;
-                        if (lane == 0 && ball) base = atomicAdd(&s_n, __popcll(ball));
-                        base = __shfl(base, 0);
+                        const int slot = cross_wave_slot(act, lane, &s_n); // < kCapCross: <= kGCCross packets per row
                         if (act) {
-                            const int slot = base + __popcll(ball & ((1ULL << lane) - 1)); // < kCapCross: <= kGCCross packets per row
                             mine[k] = slot;
                             s_beta[slot] = a ^ G.x;
                             s_live[slot] = 1;
@@ -111,12 +107,8 @@ __global__ __launch_bounds__(kBlock) void k_cross_project(int n_groups, lsk_grou
                     // ---- stage B1: project every packet into the SOURCE basis (minimum, character, stabiliser norm) -------------
                     if (project) {
                         for (int e = tid; e < n; e += kBlock) {
-                            W rep; double chr, chi, stab;
-                            if (FERMI && sbs.fermi != 0) fermi_state_info_w<W, PM1>(sbs, elems, (W)s_beta[e], rep, chr, chi, stab);
-                            else state_info_w<W, PM1>(sbs, elems, (W)s_beta[e], rep, chr, chi, stab);
-                            const double n2 = stab * sbs.inv_order;
-                            if (!(n2 > 1e-12)) { s_live[e] = 0; continue; } // zero norm in the source sector: contributes nothing
-                            const double nb = sqrt(n2);
+                            W rep; double chr, chi, nb; // (signed characters where the SOURCE is the fermionic basis)
+                            if (!sector_project<W, PM1, FERMI>(sbs, elems, (W)s_beta[e], rep, chr, chi, nb, sbs.fermi != 0)) { s_live[e] = 0; continue; }
                             s_beta[e] = (uint64_t)rep;
                             if (RC) s_coef[CW * e] = s_coef[CW * e] * chr * nb;
                             else { // times chi1(g0) = conj(chr, chi), times n1(rep)

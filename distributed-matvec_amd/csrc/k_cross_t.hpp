@@ -6,6 +6,8 @@
 // chi(g) sign(g, a) of lsk_fermi.hpp (fermi_state_info_w) instead of state_info_w.  Nothing else in the formula changes: chr, chi
 // and stab then carry sign(g0, beta) and the signed stabiliser sum, and the zero-norm test drops the orbits whose signed sum
 // vanishes (which happens in ANY fermionic sector).  The branch is discarded at compile time by the spin instantiations.
+// The header is the root of the include chain of all seven sector kernels, so it also holds what they share as functions
+// (cross_wave_slot, sector_project, below cross_index) and, at the end, the launcher of both k_cross_pull units.
 #pragma once
 #include "lsk_dev.hpp"
 #include "lsk_fermi.hpp"
@@ -28,6 +30,43 @@ __device__ __forceinline__ int64_t cross_index(lsk_index const &ix, uint64_t s) 
     }
     if (ix.count <= 0 || (ix.dir_sites < 64 && (s >> ix.dir_sites) != 0)) return -1; // (SEARCH: the prefix table covers dir_sites bits)
     return search_index(ix, s);
+}
+
+// ---- what the seven sector kernels share as functions (k_cross_pull, k_cross_pull_blk, k_cross_project here; k_corr_hop, k_expect,
+// k_expect_blk, k_expect_mat through k_corr_t.hpp): the slot allocation of the cross kernels and the core of stage B1 with its
+// zero-norm threshold.  With these two every 32-bit instantiation keeps its machine code, instruction for instruction, and every
+// 64-bit one its register counts, LDS and occupancy (profiles/sector_stages_resources.txt).  The look-up of stage B2, the ordered compaction
+// of k_corr_hop / k_expect* and the emit predicate of k_expect* stay as text in each kernel: as shared functions (the look-up in three
+// forms) each of them cost some instantiation 1 - 5 % -- these kernels sit at 106 SGPRs with spills to VGPR lanes, and any change of
+// their text moves the allocation (profiles/sector_stages_ab.txt).  Keep the copies equal by hand: the key-width guard gt.L < 64 and
+// the out-of-range rule of the look-up are the same in all seven.
+
+// Stage A of the cross kernels: the next slot of the block's packet list for every active lane -- a ballot, one LDS atomicAdd per
+// wave, so the slots follow the order in which the waves arrive.  (The value is meaningless for a lane that is not active.)
+__device__ __forceinline__ int cross_wave_slot(bool act, int lane, int *s_n) {
+    const unsigned long long ball = __ballot(act);
+    int base = 0;
+    if (lane == 0 && ball) base = atomicAdd(s_n, __popcll(ball));
+    base = __shfl(base, 0);
+    return base + __popcll(ball & ((1ULL << lane) - 1));
+}
+
+// Stage B1, the core: project the image s into the basis (general K4: minimum, character, stabiliser norm) -- its representative,
+// the character (chr, chi) of the element g0 that maps s there, and nb = n(rep).  false: zero norm in the sector, the packet
+// contributes nothing (with FERMI that happens in ANY sector: the signed stabiliser sum vanishes).  What a kernel multiplies into its
+// slot is its own: the roundings differ from kernel to kernel and are part of their results.  FERMI projects with the signed
+// characters chi(g) sign(g, s) of lsk_fermi.hpp; `signs` is the run-time half of that switch, which k_cross_project alone needs (its
+// FERMI says that EITHER basis is fermionic).
+template <typename W, bool PM1, bool FERMI>
+__device__ __forceinline__ bool sector_project(lsk_basis const &bs, lsk_group_elem const *__restrict__ elems, W s, W &rep, double &chr,
+                                               double &chi, double &nb, bool signs = true) {
+    double stab;
+    if (FERMI && signs) fermi_state_info_w<W, PM1>(bs, elems, s, rep, chr, chi, stab);
+    else state_info_w<W, PM1>(bs, elems, s, rep, chr, chi, stab);
+    const double n2 = stab * bs.inv_order;
+    if (!(n2 > 1e-12)) return false;
+    nb = sqrt(n2);
+    return true;
 }
 
 // The compile-time mode of the kernel rides on its word type, so that the apply kernels keep their five template arguments, their
@@ -96,12 +135,8 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group c
                 if (valid) term_sum<REAL>(terms, G.begin, G.end, a, cr, ci);
                 // (tiny: the rounding residue of terms that cancel -- sum_j e^{-iqj} sigma^z_j on a state of shorter period -- is no packet)
                 const bool act = valid && (fabs(cr) > tiny || (!REAL && fabs(ci) > tiny));
-                const unsigned long long ball = __ballot(act);
-                int base = 0;
-                if (lane == 0 && ball) base = atomicAdd(&s_n, __popcll(ball));
-                base = __shfl(base, 0);
+                const int slot = cross_wave_slot(act, lane, &s_n);
                 if (act) {
-                    const int slot = base + __popcll(ball & ((1ULL << lane) - 1));
                     s_beta[slot] = a ^ G.x;
                     s_row[slot] = (uint16_t)tid;
                     if constexpr (EMIT) s_g[slot] = (uint8_t)(g - g0);
@@ -114,12 +149,8 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group c
             // ---- stage B1: project every packet into the SOURCE basis (general K4: minimum, character, stabiliser norm) --
             if (project) {
                 for (int e = tid; e < n; e += kBlock) {
-                    W rep; double chr, chi, stab;
-                    if constexpr (FERMI) fermi_state_info_w<W, PM1>(sbs, elems, (W)s_beta[e], rep, chr, chi, stab);
-                    else state_info_w<W, PM1>(sbs, elems, (W)s_beta[e], rep, chr, chi, stab);
-                    const double n2 = stab * sbs.inv_order;
-                    if (!(n2 > 1e-12)) { s_row[e] = 0xffff; continue; } // zero norm in the source sector: contributes nothing
-                    const double nb = sqrt(n2);
+                    W rep; double chr, chi, nb;
+                    if (!sector_project<W, PM1, FERMI>(sbs, elems, (W)s_beta[e], rep, chr, chi, nb)) { s_row[e] = 0xffff; continue; }
                     s_beta[e] = (uint64_t)rep;
                     if (RC) s_coef[e] = s_coef[e] * chr * nb;
                     else { // times chi1(g0) = conj(chr, chi), times n1(rep)
@@ -210,4 +241,36 @@ __global__ __launch_bounds__(kBlock) void k_cross_pull(int n_groups, lsk_group c
         }
         __syncthreads();
     }
+}
+
+// the launch of both units (who: the entry point, for its messages): {32, 64-bit words} x {f64 (real terms, +-1 characters) | c128 x
+// {+-1, complex characters} x {real, complex terms}}: 10 kernels per unit.  d_count != NULL: nothing is read from x or written to y;
+// the packets that reach a source row are added to *d_count
+template <bool FERMI>
+static int cross_pull_launch(char const *who, int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src,
+                             lsk_index six, lsk_gtab gt, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms,
+                             void const *x, void *y, double tiny, unsigned long long *d_count, int *d_err, void *stream) {
+    if (n_dst <= 0 || n_groups <= 0) return 0;
+    if (!cplx && !(is_real && src.chars_pm1)) { snprintf(g_err, sizeof(g_err), "%s: f64 needs a real operator and +-1 characters", who); return -1; }
+    if (src.proj == LSK_PROJ_NONE && gt.entries) { snprintf(g_err, sizeof(g_err), "%s: an unprojected source is looked up by its index", who); return -1; }
+    const int64_t work_blocks = (n_dst + kBlock - 1) / kBlock;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 g(1), b(kBlock);
+#define LSK_CX_ONE(W, PM1, CPLX, REAL)                                                                                                   \
+    do {                                                                                                                                 \
+        g.x = resident_grid(k_cross_pull<W, PM1, CPLX, REAL, FERMI>, work_blocks);                                                       \
+        hipLaunchKernelGGL((k_cross_pull<W, PM1, CPLX, REAL, FERMI>), g, b, 0, s, n_groups, groups, terms, src, src.elems, six, gt,      \
+                           n_dst, dst_reps, dst_norms, (double const *)x, (double *)y, tiny, d_count, d_err);                            \
+    } while (0)
+#define LSK_CX_LAUNCH(W)                                                                                                                 \
+    do {                                                                                                                                 \
+        if (!cplx) LSK_CX_ONE(W, true, false, true);                                                                                     \
+        else if (src.chars_pm1) { if (is_real) LSK_CX_ONE(W, true, true, true); else LSK_CX_ONE(W, true, true, false); }                 \
+        else { if (is_real) LSK_CX_ONE(W, false, true, true); else LSK_CX_ONE(W, false, true, false); }                                  \
+    } while (0)
+    if (src.number_sites <= 32) LSK_CX_LAUNCH(uint32_t); else LSK_CX_LAUNCH(uint64_t);
+#undef LSK_CX_LAUNCH
+#undef LSK_CX_ONE
+    LSK_LAUNCH_CHECK();
+    return 0;
 }

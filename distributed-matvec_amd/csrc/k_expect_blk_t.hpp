@@ -21,7 +21,7 @@
 //     equal inputs give equal bytes.
 // The group x = 0 is neither projected nor looked up: its product is |Psi[r, c]|^2.
 #pragma once
-#include "k_expect_t.hpp" // through it k_corr_t.hpp (kCorrWaves, corr_grid) and k_cross_t.hpp (cross_index)
+#include "k_expect_t.hpp" // through it k_corr_t.hpp (kCorrWaves, corr_grid) and k_cross_t.hpp (sector_project, cross_index)
 
 constexpr int kExpKC = 8;                        // columns per block: products per packet, and loads in flight per packet
 constexpr int kExpBlkPP = 4;                     // flip-mask groups per pass of the c128 kinds (60 KB of static LDS; 8 do not fit in 64 KB)
@@ -148,16 +148,12 @@ __global__ __launch_bounds__(kBlock) void k_expect_blk(lsk_basis bs, lsk_group_e
             if (tid == 0) s_off[PP] = run;
             __syncthreads();
             const int np = run; // (every thread summed the same counts)
-            // ---- stage B1: project every packet (general K4: minimum, character, stabiliser norm) -- k_expect's, once per chunk ----
+            // ---- stage B1: project every packet (sector_project, k_cross_t.hpp), once per chunk --------------------------------------
             if (project) {
                 for (int e = tid; e < np; e += kBlock) {
                     if (s_row[e] & kDiag) continue;
-                    W rep; double chr, chi, stab;
-                    if constexpr (FERMI) fermi_state_info_w<W, PM1>(bs, elems, s_beta[e], rep, chr, chi, stab);
-                    else state_info_w<W, PM1>(bs, elems, s_beta[e], rep, chr, chi, stab);
-                    const double n2 = stab * bs.inv_order;
-                    if (!(n2 > 1e-12)) { s_row[e] = kDead; continue; }
-                    const double nb = sqrt(n2);
+                    W rep; double chr, chi, nb;
+                    if (!sector_project<W, PM1, FERMI>(bs, elems, s_beta[e], rep, chr, chi, nb)) { s_row[e] = kDead; continue; }
                     s_beta[e] = rep;
                     if (PM1) s_fac[e] *= chr * nb;
                     else { // chi(g0) = conj(chr, chi), times n(rep) / n(r)

@@ -4,7 +4,7 @@
 //     R[u] = sum over the rows r with r & m_u == r_u of  (-1)^popcount(r & s_u) conj(psi_r) / n(r) * <r ^ x_u|psi>
 // for every unique device term u = (m, r, x, s) of the batch (row-wise orientation, coefficient 1: the host holds the coefficients).
 // It is k_corr_hop (k_corr_t.hpp) with "item = any term" in the place of "item = ordered pair": the same tiles, the same stages B1 / B2
-// (projection of an image, look-up, four look-ups in flight), the same error flag, one partial per (block, item) and the sum over the
+// (projection of an image by sector_project, look-up, four look-ups in flight), the same error flag, one partial per (block, item) and the sum over the
 // blocks in block order by lsk_corr_sum.  What differs from there:
 //   - a PACKET belongs to a flip-mask group, not to a term: the image r ^ x is projected and looked up once, and its product
 //     conj(psi_r) / n(r) <r ^ x|psi> serves every term of the group.  The row's factor travels in the packet's slot from stage A on,
@@ -19,7 +19,7 @@
 // Every Jordan-Wigner and permutation sign of a fermionic term is inside s and the host's coefficient already, so FERMI switches the
 // signed projection of B1 and nothing else.
 #pragma once
-#include "k_corr_t.hpp" // kCorrPP, kCorrCap, kCorrWaves, corr_grid; through it k_cross_t.hpp: cross_index
+#include "k_corr_t.hpp" // kCorrPP, kCorrCap, kCorrWaves, corr_grid; through it k_cross_t.hpp: sector_project, cross_index
 
 template <typename W, bool PM1, bool CPLX, bool FERMI>
 __global__ __launch_bounds__(kBlock) void k_expect(lsk_basis bs, lsk_group_elem const *__restrict__ elems, lsk_index six, lsk_gtab gt,
@@ -103,16 +103,12 @@ __global__ __launch_bounds__(kBlock) void k_expect(lsk_basis bs, lsk_group_elem 
             if (tid == 0) s_off[kCorrPP] = run;
             __syncthreads();
             const int np = run; // (every thread summed the same counts)
-            // ---- stage B1: project every packet (general K4: minimum, character, stabiliser norm) -- k_cross_pull's -------------
+            // ---- stage B1: project every packet (sector_project, k_cross_t.hpp) ---------------------------------------------------
             if (project) {
                 for (int e = tid; e < np; e += kBlock) {
                     if (s_row[e] & kDiag) continue;
-                    W rep; double chr, chi, stab;
-                    if constexpr (FERMI) fermi_state_info_w<W, PM1>(bs, elems, s_beta[e], rep, chr, chi, stab);
-                    else state_info_w<W, PM1>(bs, elems, s_beta[e], rep, chr, chi, stab);
-                    const double n2 = stab * bs.inv_order;
-                    if (!(n2 > 1e-12)) { s_row[e] = kDead; continue; }
-                    const double nb = sqrt(n2);
+                    W rep; double chr, chi, nb;
+                    if (!sector_project<W, PM1, FERMI>(bs, elems, s_beta[e], rep, chr, chi, nb)) { s_row[e] = kDead; continue; }
                     s_beta[e] = rep;
                     const double fr = chr * nb, fi = -chi * nb; // chi(g0) = conj(chr, chi), times n(rep)
                     if (PM1) {

@@ -42,9 +42,14 @@ def test_abi_makefile_and_python_names():
 
 def test_the_block_kernel_has_no_floating_point_atomics_and_one_chunk_width():
     """the bitwise guarantee of k_expect carries over: the template adds in a fixed order, in registers and plain LDS stores"""
-    src = open(os.path.join(CSRC, "k_expect_blk_t.hpp"), encoding="utf-8").read()
-    code = "\n".join(line.split("//")[0] for line in src.splitlines())
-    assert "atomicAdd" not in code and "unsafeAtomicAdd" not in code
+    def code_of(header):
+        src = open(os.path.join(CSRC, header), encoding="utf-8").read()
+        return "\n".join(line.split("//")[0] for line in src.splitlines())
+
+    code = code_of("k_expect_blk_t.hpp")
+    # ... and the headers it takes its stages and constants from
+    for header in ("k_expect_blk_t.hpp", "k_expect_t.hpp", "k_corr_t.hpp"):
+        assert "atomicAdd" not in code_of(header) and "unsafeAtomicAdd" not in code_of(header), header
     assert re.search(r"constexpr int kExpKC = 8;", code)
     assert "corr_grid(n)" in code and "lsk_corr_sum(" in code
     for unit, fermi in (("k_expect_blk.hip", False), ("k_expect_blk_fermi.hip", True)):

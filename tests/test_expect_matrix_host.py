@@ -47,10 +47,15 @@ def test_abi_makefile_and_python_names():
 
 
 def test_the_matrix_kernel_reuses_the_block_stages_without_floating_point_atomics():
-    src = open(os.path.join(CSRC, "k_expect_mat_t.hpp"), encoding="utf-8").read()
-    code = "\n".join(line.split("//")[0] for line in src.splitlines())
+    def code_of(header):
+        src = open(os.path.join(CSRC, header), encoding="utf-8").read()
+        return "\n".join(line.split("//")[0] for line in src.splitlines())
+
+    code = code_of("k_expect_mat_t.hpp")
     assert '#include "k_expect_blk_t.hpp"' in code
-    assert "atomicAdd" not in code and "unsafeAtomicAdd" not in code
+    # ... and the headers it takes its stages and constants from
+    for header in ("k_expect_mat_t.hpp", "k_expect_t.hpp", "k_corr_t.hpp"):
+        assert "atomicAdd" not in code_of(header) and "unsafeAtomicAdd" not in code_of(header), header
     assert "expect_blk_fold<NC>(" in code and "corr_grid(n)" in code and "lsk_corr_sum(" in code and "kExpKC" in code
     assert re.search(r"constexpr int kExpMatKA = [48];", code)
     for unit, fermi in (("k_expect_mat.hip", False), ("k_expect_mat_fermi.hip", True)):
