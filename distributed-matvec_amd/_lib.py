@@ -181,6 +181,8 @@ def load():
         "ls_amd_cross_apply": (C.c_int, [vp, vp, vp, vp]),
         "ls_amd_cross_apply_block": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp]),
         "ls_amd_cross_block_kernel_name": (C.c_char_p, [vp, C.c_int]),
+        "ls_amd_cross_apply_block_path": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp]),
+        "ls_amd_cross_block_kernel_name_path": (C.c_char_p, [vp, C.c_int, C.c_int]),
         "ls_amd_cross_check": (C.c_int, [vp, vp]),
         "ls_amd_cross_kernel_name": (C.c_char_p, [vp]),
         "ls_amd_cross_nnz": (C.c_int64, [vp]),

@@ -969,11 +969,25 @@ class CrossSectorPlan:
         if check:
             self.check()
 
-    def apply_block(self, x, y, check: bool = True):
+    BLOCK_METHODS = {None: 0, "columns": 1, "kernel": 2}  # LS_AMD_CROSS_BLOCK_AUTO | _COLUMNS | _KERNEL
+
+    @classmethod
+    def _block_path(cls, who, method):
+        if not isinstance(method, (str, type(None))) or method not in cls.BLOCK_METHODS:
+            raise ValueError(f"CrossSectorPlan.{who}: method = {method!r} is none of None (LS_AMD_CROSS_PROJECT_BLOCK, else 'columns'), "
+                             "'columns', 'kernel'")
+        return cls.BLOCK_METHODS[method]
+
+    def apply_block(self, x, y, check: bool = True, method=None):
         """Y[:, k] <- A X[:, k] for the K columns of the (n_src, K) and (n_dst, K) device tensors x and y (ls_amd_cross_apply_block):
         any strides -- (K, 1) interleaved is the fast layout, a transposed (K, n) tensor the column-major one -- and the plan's
         dtype; 1 <= K <= 64; y is assigned; x and y must not overlap.  Stages A and B1 and the look-up of the images run once per
-        chunk of 8 columns instead of once per column; block_kernel(K) names the path."""
+        chunk of 8 columns instead of once per column; block_kernel(K) names the path.  method chooses the
+        path of a groups="project" plan: "columns" loops apply over the columns (byte for byte K applies), "kernel" runs the block
+        form k_cross_project_blk (the target's element loop once per chunk of 8 columns, a fixed order of summation), None follows
+        LS_AMD_CROSS_PROJECT_BLOCK=columns|kernel (unset: columns).  The argument wins over the environment; the other plans have one
+        block kernel whatever it says.  ValueError for any other value, before any device work."""
+        path = self._block_path("apply_block", method)
         torch = _torch()
         for name, t in (("x", x), ("y", y)):
             if not isinstance(t, torch.Tensor) or t.dim() != 2:
@@ -985,14 +999,16 @@ class CrossSectorPlan:
         if x.shape[0] != self.n_src or y.shape[0] != self.n_dst or x.shape[1] != y.shape[1]:
             raise LsAmdError(f"apply_block: x {tuple(x.shape)} must be ({self.n_src}, K) and y {tuple(y.shape)} ({self.n_dst}, K)")
         K = int(x.shape[1])
-        _lib.check(_lib.load().ls_amd_cross_apply_block(self.h, K, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
-                                                        C.c_void_p(y.data_ptr()), y.stride(0), y.stride(1), _stream_ptr()))
+        _lib.check(_lib.load().ls_amd_cross_apply_block_path(self.h, path, K, C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
+                                                             C.c_void_p(y.data_ptr()), y.stride(0), y.stride(1), _stream_ptr()))
         if check:
             self.check()
 
-    def block_kernel(self, K: int) -> str:
-        """path a block of K columns takes on this plan: "k_cross_pull_blk", "k_cross_pull_blk_fermi" or "columns" (groups="project")"""
-        name = _lib.load().ls_amd_cross_block_kernel_name(self.h, int(K))
+    def block_kernel(self, K: int, method=None) -> str:
+        """path a block of K columns takes on this plan: "k_cross_pull_blk", "k_cross_pull_blk_fermi"; groups="project": "columns", or
+        "k_cross_project_blk[_fermi]" with method="kernel" (None: LS_AMD_CROSS_PROJECT_BLOCK, as in apply_block)"""
+        path = self._block_path("block_kernel", method)
+        name = _lib.load().ls_amd_cross_block_kernel_name_path(self.h, path, int(K))
         if name is None:
             _lib.check(-1)
         return name.decode()

@@ -6247,21 +6247,56 @@ int ls_amd_cross_apply(ls_amd_cross *cx, void const *d_x, void *d_y, void *strea
 }
 
 /* ---- blocks of vectors (include/ls_amd.h: ls_amd_cross_apply_block; csrc/k_cross_blk.hip) ---- */
-/* SAME and RESTRICT plans have the block kernel; a projecting plan (k_cross_project has no block form) takes the column loop */
-static int cross_block_columns(ls_amd_cross const *cx) { return cx->mode == LS_AMD_CROSS_PROJECT; }
+/* SAME and RESTRICT plans have one block kernel, k_cross_pull_blk.  A projecting plan has two paths: the column loop over
+ * ls_amd_cross_apply (the default) and the block kernel k_cross_project_blk.  path: LS_AMD_CROSS_BLOCK_AUTO follows
+ * LS_AMD_CROSS_PROJECT_BLOCK=columns|kernel, read at every call (unset: columns).  1: the column loop, 0: a block kernel, -1 with a
+ * message: an unknown path or value */
+static int cross_block_path_ok(char const *who, int path) {
+    if (path != LS_AMD_CROSS_BLOCK_AUTO && path != LS_AMD_CROSS_BLOCK_COLUMNS && path != LS_AMD_CROSS_BLOCK_KERNEL)
+        return set_error("%s: unknown path %d (LS_AMD_CROSS_BLOCK_AUTO, LS_AMD_CROSS_BLOCK_COLUMNS or LS_AMD_CROSS_BLOCK_KERNEL)", who, path);
+    return 0;
+}
+static int cross_block_columns(char const *who, ls_amd_cross const *cx, int path) {
+    if (cross_block_path_ok(who, path) != 0) return -1;
+    if (cx->mode != LS_AMD_CROSS_PROJECT) return 0;
+    if (path == LS_AMD_CROSS_BLOCK_AUTO) {
+        char const *e = getenv("LS_AMD_CROSS_PROJECT_BLOCK");
+        if (!e || !*e || strcmp(e, "columns") == 0) return 1;
+        if (strcmp(e, "kernel") == 0) return 0;
+        return set_error("%s: LS_AMD_CROSS_PROJECT_BLOCK=%s (columns or kernel)", who, e);
+    }
+    return path == LS_AMD_CROSS_BLOCK_COLUMNS;
+}
 
-char const *ls_amd_cross_block_kernel_name(ls_amd_cross const *cx, int K) {
-    if (!cx) { set_error("ls_amd_cross_block_kernel_name: NULL plan"); return NULL; }
-    if (K < 1 || K > 64) { set_error("ls_amd_cross_block_kernel_name: K = %d is outside [1, 64]", K); return NULL; }
-    if (cross_block_columns(cx)) return "columns";
+char const *ls_amd_cross_block_kernel_name_path(ls_amd_cross const *cx, int path, int K) {
+    char const *const who = "ls_amd_cross_block_kernel_name";
+    if (cross_block_path_ok(who, path) != 0) return NULL; /* (the path and K before the plan: refusals that need no plan) */
+    if (K < 1 || K > 64) { set_error("%s: K = %d is outside [1, 64]", who, K); return NULL; }
+    if (!cx) { set_error("%s: NULL plan", who); return NULL; }
+    int const columns = cross_block_columns(who, cx, path);
+    if (columns < 0) return NULL;
+    if (columns) return "columns";
+    if (cx->mode == LS_AMD_CROSS_PROJECT)
+        return cx->src.fermi || cx->dst.fermi ? lsk_cross_project_blk_fermi_kernel_name() : lsk_cross_project_blk_kernel_name();
     return cx->src.fermi ? lsk_cross_blk_fermi_kernel_name() : lsk_cross_blk_kernel_name();
+}
+char const *ls_amd_cross_block_kernel_name(ls_amd_cross const *cx, int K) {
+    return ls_amd_cross_block_kernel_name_path(cx, LS_AMD_CROSS_BLOCK_AUTO, K);
 }
 
 int ls_amd_cross_apply_block(ls_amd_cross *cx, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row, int64_t y_col,
                              void *stream) {
+    return ls_amd_cross_apply_block_path(cx, LS_AMD_CROSS_BLOCK_AUTO, K, d_x, x_row, x_col, d_y, y_row, y_col, stream);
+}
+
+int ls_amd_cross_apply_block_path(ls_amd_cross *cx, int path, int K, void const *d_x, int64_t x_row, int64_t x_col, void *d_y, int64_t y_row,
+                                  int64_t y_col, void *stream) {
     char const *const who = "ls_amd_cross_apply_block";
-    if (!cx) return set_error("%s: NULL plan", who);
+    if (cross_block_path_ok(who, path) != 0) return -1; /* (the path and K before the plan: refusals that need no plan) */
     if (K < 1 || K > 64) return set_error("%s: K = %d is outside [1, 64]", who, K);
+    if (!cx) return set_error("%s: NULL plan", who);
+    int const columns = cross_block_columns(who, cx, path);
+    if (columns < 0) return -1;
     int64_t const ns = cx->n_src, nd = cx->n_dst;
     if (nd == 0) return 0;
     if (!d_y || (!d_x && ns > 0)) return set_error("%s: NULL %s", who, !d_y ? "Y" : "X");
@@ -6278,8 +6313,13 @@ int ls_amd_cross_apply_block(ls_amd_cross *cx, int K, void const *d_x, int64_t x
         for (int k = 0; k < K; ++k) DEV(lsk_copy_strided(nd, (int)w, zero, 1, y + (size_t)k * (size_t)y_col * w, y_row, stream));
         return 0;
     }
-    if (!cross_block_columns(cx)) {
+    if (!columns) {
         lsk_gtab const gt = cx->gtab ? cx->gtab->tab : no_gtab();
+        if (cx->mode == LS_AMD_CROSS_PROJECT) {
+            DEV(lsk_cross_project_blk(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, gt, cx->dst, cx->cplx, nd,
+                                      cx->d_dst_reps, cx->d_norms, K, d_x, x_row, x_col, d_y, y_row, y_col, cx->tiny, cx->d_err, stream));
+            return 0;
+        }
         DEV(lsk_cross_pull_blk(cx->n_groups, cx->d_groups, cx->d_terms, cx->is_real, cx->src, cx->six, gt, cx->cplx, nd, cx->d_dst_reps,
                                cx->d_norms, K, d_x, x_row, x_col, d_y, y_row, y_col, cx->tiny, cx->d_err, stream));
         return 0;

@@ -630,6 +630,22 @@ char const *lsk_cross_project_fermi_kernel_name(void);
 int lsk_cross_project_fermi(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
                             lsk_gtab gt, lsk_basis dst, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms,
                             void const *x, void *y, double tiny, unsigned long long *d_count, int *d_err, void *stream);
+/* the block form of the projecting kernel (k_cross_project_blk.hip, k_cross_project_blk; DESIGN.md sections 6b, 6h): y[r', k] for the
+ * K columns (1 <= K <= 64) of the blocks x and y, element strides (row, column) as for lsk_cross_pull_blk, whose chunks of 8 columns,
+ * grid and LS_AMD_CROSS_BLOCKS cap it shares.  The stages of lsk_cross_project run once per chunk; a row's sums live in registers and
+ * are stored once, one plain store per (row, column), in a fixed order of summation.  No counting pass; the error flag keeps its
+ * meaning.  lsk_cross_project_blk hands a pair with a projected fermionic basis on either side to lsk_cross_project_blk_fermi
+ * (k_cross_project_blk_fermi.hip, k_cross_project_blk_fermi). */
+char const *lsk_cross_project_blk_kernel_name(void);
+int lsk_cross_project_blk(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
+                          lsk_gtab gt, lsk_basis dst, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms, int K,
+                          void const *x, int64_t x_row, int64_t x_col, void *y, int64_t y_row, int64_t y_col, double tiny, int *d_err,
+                          void *stream);
+char const *lsk_cross_project_blk_fermi_kernel_name(void);
+int lsk_cross_project_blk_fermi(int n_groups, lsk_group const *groups, lsk_term const *terms, int is_real, lsk_basis src, lsk_index six,
+                                lsk_gtab gt, lsk_basis dst, int cplx, int64_t n_dst, uint64_t const *dst_reps, double const *dst_norms,
+                                int K, void const *x, int64_t x_row, int64_t x_col, void *y, int64_t y_row, int64_t y_col, double tiny,
+                                int *d_err, void *stream);
 
 /* the matrix of a cross-sector plan in CSR form (k_csr.hip).  lsk_cross_emit runs stages A, B1, B2 of
  * k_cross_pull (the arguments of lsk_cross_pull; either family) and, instead of gathering from x, hands every packet that reached a

@@ -601,16 +601,30 @@ int ls_amd_cross_apply(ls_amd_cross *plan, void const *d_x, void *d_y, void *str
  * consecutive memory), (1, n) the column-major one.  X and Y must not overlap.  Asynchronous on `stream`.  Plans of mode
  * LS_AMD_CROSS_SAME and LS_AMD_CROSS_RESTRICT run the block kernel (csrc/k_cross_blk.hip): the term sums, the
  * projection of every image and its look-up in the source basis are done once per chunk of 8 columns, not once per column.  Plans
- * of mode LS_AMD_CROSS_PROJECT loop ls_amd_cross_apply over the columns, through contiguous scratch columns that the plan owns where
- * a row stride is not 1.  A = 0 or an empty source clears Y.  The error flag is that of ls_amd_cross_apply: ls_amd_cross_check
+ * of mode LS_AMD_CROSS_PROJECT have two paths.  The default, "columns", loops ls_amd_cross_apply over the columns, through
+ * contiguous scratch columns that the plan owns where a row stride is not 1: byte for byte the K single applies.  "kernel" runs the
+ * block form of k_cross_project (csrc/k_cross_project_blk.hip, k_cross_project_blk[_fermi]; DESIGN.md sections 6b, 6h): the
+ * target's element loop, the term sums, the projection and the look-up once per chunk of 8 columns, every (row, column) summed in
+ * registers in a fixed order (two calls return the same bytes; they differ from the column loop's in the last bits).
+ * LS_AMD_CROSS_PROJECT_BLOCK=columns|kernel, read at every call, chooses (unset: columns; any other value is refused by name); it
+ * has no effect on the other two modes.  A = 0 or an empty source clears Y.  The error flag is that of ls_amd_cross_apply: ls_amd_cross_check
  * serves both.  -1 with a message: K outside 1...64, NULL X or Y, strides that make elements share storage, overlapping X and Y.
  * Environment: LS_AMD_CROSS_BLOCKS=<k>, read at every launch, caps the row blocks of the block kernel's grid (a test hook: a
  * workgroup then walks several tiles). */
 int ls_amd_cross_apply_block(ls_amd_cross *plan, int K, void const *d_x, int64_t x_row, int64_t x_col,
                              void *d_y, int64_t y_row, int64_t y_col, void *stream);
 /* the path ls_amd_cross_apply_block takes for K columns: "k_cross_pull_blk", "k_cross_pull_blk_fermi" for a projected fermionic
- * source, "columns" for LS_AMD_CROSS_PROJECT.  NULL with a message: NULL plan, K outside 1...64. */
+ * source; for LS_AMD_CROSS_PROJECT "columns", or "k_cross_project_blk" / "k_cross_project_blk_fermi" (either basis a projected
+ * fermionic one) under LS_AMD_CROSS_PROJECT_BLOCK=kernel.  NULL with a message: NULL plan, K outside 1...64. */
 char const *ls_amd_cross_block_kernel_name(ls_amd_cross const *plan, int K);
+/* The same two with the path of a LS_AMD_CROSS_PROJECT plan as an argument: _AUTO follows LS_AMD_CROSS_PROJECT_BLOCK (the two
+ * functions above are these with _AUTO), _COLUMNS and _KERNEL choose whatever the environment says.  On LS_AMD_CROSS_SAME and
+ * LS_AMD_CROSS_RESTRICT plans every path is the one block kernel.  An unknown path is refused by name; the path and K are checked
+ * before the plan. */
+enum { LS_AMD_CROSS_BLOCK_AUTO = 0, LS_AMD_CROSS_BLOCK_COLUMNS = 1, LS_AMD_CROSS_BLOCK_KERNEL = 2 };
+int ls_amd_cross_apply_block_path(ls_amd_cross *plan, int path, int K, void const *d_x, int64_t x_row, int64_t x_col,
+                                  void *d_y, int64_t y_row, int64_t y_col, void *stream);
+char const *ls_amd_cross_block_kernel_name_path(ls_amd_cross const *plan, int path, int K);
 /* synchronises `stream` and reports the device error flag: -1 ("... not in the source basis") when an image of A+ with non-zero
  * source norm was not found among the source's representatives -- A leaves the target's weight sector, say; y is then not A x.
  * The run-time counterpart of ls_amd_plan_check's "invalid index". */

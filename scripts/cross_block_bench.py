@@ -131,10 +131,10 @@ def thermal(L, q):
     events = []
     inner = D.CrossSectorPlan.apply_block
 
-    def bracketed(self, x, y, check=True):
+    def bracketed(self, x, y, check=True, method=None):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        inner(self, x, y, check=check)
+        inner(self, x, y, check=check, method=method)
         e1.record()
         events.append((e0, e1))
 
