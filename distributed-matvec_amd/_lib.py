@@ -211,6 +211,15 @@ def load():
         "ls_amd_project_destroy": (None, [vp]),
         "ls_amd_test_project_full_size": (C.c_int64, [bp]),
         "ls_amd_test_project_state_index": (C.c_int64, [bp, C.c_uint64]),
+        "ls_amd_amp_create": (C.c_int, [C.POINTER(vp), bp, vp, C.c_int64, vp]),
+        "ls_amd_amp_num_elements": (C.c_int, [vp]),
+        "ls_amd_amp_amplitudes": (C.c_int, [vp, C.c_int, C.c_int, C.c_int64, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp]),
+        "ls_amd_amp_state_info": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp, vp, vp]),
+        "ls_amd_amp_orbit_states": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp]),
+        "ls_amd_amp_check": (C.c_int, [vp, vp]),
+        "ls_amd_amp_kernel_name": (C.c_char_p, [vp]),
+        "ls_amd_amp_destroy": (None, [vp]),
+        "ls_amd_test_orbit_state": (C.c_uint64, [bp, C.c_uint64, C.c_int, C.POINTER(C.c_int)]),
         "ls_amd_corr_create": (C.c_int, [C.POINTER(vp), bp, vp, C.c_int64, vp]),
         "ls_amd_corr_modes": (C.c_int, [vp]),
         "ls_amd_corr_densities": (C.c_int, [vp, C.c_int, vp, c_f64p, c_f64p, C.c_int, vp]),

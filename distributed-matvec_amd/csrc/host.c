@@ -6930,6 +6930,179 @@ char const *ls_amd_project_kernel_name(ls_amd_project const *p) {
 }
 
 /* ============================================================================================ */
+/* amplitudes on product states and orbit images (include/ls_amd.h: ls_amd_amp; csrc/k_amplitude_t.hpp) */
+/* ============================================================================================ */
+/* which words are states of the basis without symmetries (the membership of lsk_project: no layout, so none of its size limits);
+ * host only: the refusals of ls_amd_amp_create that need no device live here */
+static int amp_membership_of(char const *who, ls_hs_basis const *basis, lsk_project *pj) {
+    if (!basis) return set_error("%s: NULL basis", who);
+    if (!reg_get(basis)) return set_error("%s: the basis is not built by this library (ls_amd_adopt_basis first)", who);
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    int const spin = basis->particle_type == LS_HS_SPIN;
+    if (!spin && basis->spin_inversion != 0) return set_error("%s: a fermionic basis has no spin inversion", who);
+    if (e->fermi && e->nbits > 60)
+        return set_error("%s: projected fermionic bases of more than 60 modes are not supported (%d modes: the static index table does "
+                         "not fit, as for their matvec and cross-sector plans)", who, e->nbits);
+    memset(pj, 0, sizeof(*pj));
+    if (!spin && e->product) {
+        pj->kind = LSK_PROJECT_PRODUCT;
+        pj->half = basis->number_sites; pj->n_up = e->prod_up; pj->n_dn = e->prod_dn;
+    } else pj->kind = e->hamming_weight < 0 ? LSK_PROJECT_ALL : LSK_PROJECT_FIXED;
+    return 0;
+}
+
+/* the effective group: the permutation elements, each followed by its product with the global inversion on a spin basis that has one
+ * (element 2 p = permutation p, 2 p + 1 = permutation p then ^ site_mask: the order of k_orbit_image) */
+static int amp_num_elements(ls_hs_basis const *basis) {
+    return BEXT(basis)->order * (basis->particle_type == LS_HS_SPIN && basis->spin_inversion != 0 ? 2 : 1);
+}
+
+uint64_t ls_amd_test_orbit_state(ls_hs_basis const *basis, uint64_t state, int element, int *ok) {
+    lsk_project pj;
+    if (ok) *ok = 0;
+    if (amp_membership_of("ls_amd_test_orbit_state", basis, &pj) != 0) return 0;
+    struct ls_amd_basis_ext const *e = BEXT(basis);
+    int const inv = basis->particle_type == LS_HS_SPIN && basis->spin_inversion != 0;
+    uint64_t const all = e->nbits >= 64 ? ~0ULL : ((1ULL << e->nbits) - 1);
+    if (element < 0 || element >= amp_num_elements(basis)) {
+        set_error("ls_amd_test_orbit_state: element %d is outside [0, %d)", element, amp_num_elements(basis));
+        return 0;
+    }
+    if (state & ~all) { set_error("ls_amd_test_orbit_state: the state 0x%llx has bits above the %d sites", (unsigned long long)state, e->nbits); return 0; }
+    uint64_t t = host_apply_elem(&e->elems[inv ? element >> 1 : element], state, e->nbits);
+    if (inv && (element & 1)) t ^= all;
+    if (ok) *ok = 1;
+    return t;
+}
+
+struct ls_amd_amp {
+    lsk_basis bs;             /* device tables owned by the basis */
+    lsk_project pj;           /* the membership kind and its numbers */
+    lsk_index six;
+    uint32_t *d_table;        /* owned: prefix table of a searched index */
+    ls_amd_gtab *gtab;        /* shared static index table {representative -> row} (projected bases) */
+    int pm1;                  /* every character is +-1: f64 allowed */
+    int fermi;                /* a projected fermionic basis: k_amplitude_pull_fermi */
+    int modes, n_elements;
+    int *d_err;               /* owned: [0] a representative that is missing, [1] a row or element out of range */
+    uint64_t const *d_reps;   /* borrowed */
+    int64_t n;
+};
+
+void ls_amd_amp_destroy(ls_amd_amp *p) {
+    if (!p) return;
+    if (p->d_table) lsk_free(p->d_table);
+    if (p->d_err) lsk_free(p->d_err);
+    if (p->gtab) ls_amd_internal_gtab_release(p->gtab);
+    free(p);
+}
+
+static int amp_setup(ls_amd_amp *p, ls_hs_basis const *basis, void *stream) {
+    if (basis_device(basis, &p->bs) != 0) return -1;
+    p->pm1 = cross_every_char_pm1(basis);
+    void *q = NULL;
+    DEV(lsk_malloc(&q, 4 * sizeof(int)));
+    p->d_err = (int *)q;
+    DEV(lsk_memset_async(p->d_err, 0, 4 * sizeof(int), stream));
+    DEV(lsk_sync(stream));
+    if (sector_lookup("ls_amd_amp_create", basis, &p->bs, p->d_reps, p->n, p->d_err, &p->six, &p->d_table, &p->gtab, stream) != 0) return -1;
+    DEV(lsk_sync(stream));
+    return 0;
+}
+
+int ls_amd_amp_create(ls_amd_amp **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, void *stream) {
+    if (out) *out = NULL;
+    if (!out || !basis) return set_error("ls_amd_amp_create: NULL %s", !out ? "handle" : "basis");
+    if (n < 0 || (n > 0 && !d_reps)) return set_error("ls_amd_amp_create: NULL representatives or a negative count");
+    lsk_project pj;
+    if (amp_membership_of("ls_amd_amp_create", basis, &pj) != 0) return -1;
+    if (n >= 0xffffffffLL) return set_error("ls_amd_amp_create: source bases with >= 2^32 - 1 states are not supported");
+    ls_amd_amp *p = (ls_amd_amp *)calloc(1, sizeof(*p));
+    if (!p) return set_error("ls_amd_amp_create: out of host memory");
+    p->pj = pj;
+    p->fermi = BEXT(basis)->fermi != 0;
+    p->modes = BEXT(basis)->nbits;
+    p->n_elements = amp_num_elements(basis);
+    p->d_reps = d_reps; p->n = n;
+    if (amp_setup(p, basis, stream) != 0) { ls_amd_amp_destroy(p); return -1; }
+    *out = p;
+    return 0;
+}
+
+int ls_amd_amp_num_elements(ls_amd_amp const *p) {
+    if (!p) return set_error("ls_amd_amp_num_elements: NULL plan");
+    return p->n_elements;
+}
+
+int ls_amd_amp_amplitudes(ls_amd_amp *p, ls_amd_dtype dtype, int K, int64_t B, uint64_t const *d_states, void const *d_psi, int64_t psi_row,
+                          int64_t psi_col, void *d_out, int64_t out_row, int64_t out_col, void *stream) {
+    char const *const who = "ls_amd_amp_amplitudes";
+    if (!p) return set_error("%s: NULL plan", who);
+    if (dtype != LS_AMD_F64 && dtype != LS_AMD_C128) return set_error("%s: unknown dtype %d", who, (int)dtype);
+    if (dtype == LS_AMD_F64 && !p->pm1) return set_error("%s: f64 needs +-1 characters (complex characters: use c128)", who);
+    if (K < 1 || K > LSK_PROJECT_MAX_K) return set_error("%s: K = %d columns, outside [1, %d]", who, K, LSK_PROJECT_MAX_K);
+    if (B < 0) return set_error("%s: a negative count of states (%lld)", who, (long long)B);
+    if (B == 0) return 0;
+    if (!d_states || !d_out || (!d_psi && p->n > 0)) return set_error("%s: NULL %s", who, !d_states ? "states" : (!d_out ? "out" : "psi"));
+    if (K == 1) { psi_col = 0; out_col = 0; }
+    if (psi_row < 0 || psi_col < 0) return set_error("%s: negative strides of psi", who);
+    if (block_strides(who, B, K, out_row, out_col, "out") != 0) return -1;
+    size_t const w = dtype == LS_AMD_C128 ? 16 : 8;
+    if (p->n > 0 && block_overlap(w, p->n, d_psi, psi_row, psi_col, w, B, d_out, out_row, out_col, K)) return set_error("%s: out overlaps psi", who);
+    lsk_project pj = p->pj;
+    pj.K = K;
+    pj.phi_s0 = psi_row; pj.phi_s1 = psi_col; pj.out_s0 = out_row; pj.out_s1 = out_col;
+    lsk_gtab const gt = p->gtab ? p->gtab->tab : no_gtab();
+    int const cplx = dtype == LS_AMD_C128;
+    if (p->fermi) DEV(lsk_amplitude_pull_fermi(p->bs, p->six, gt, pj, cplx, B, d_states, d_psi, d_out, p->d_err, stream));
+    else DEV(lsk_amplitude_pull(p->bs, p->six, gt, pj, cplx, B, d_states, d_psi, d_out, p->d_err, stream));
+    return 0;
+}
+
+int ls_amd_amp_state_info(ls_amd_amp *p, int64_t B, uint64_t const *d_states, uint64_t *d_reps_out, int64_t *d_index, double *d_characters,
+                          double *d_norms, void *stream) {
+    char const *const who = "ls_amd_amp_state_info";
+    if (!p) return set_error("%s: NULL plan", who);
+    if (B < 0) return set_error("%s: a negative count of states (%lld)", who, (long long)B);
+    if (B == 0) return 0;
+    if (!d_states) return set_error("%s: NULL states", who);
+    lsk_gtab const gt = p->gtab ? p->gtab->tab : no_gtab();
+    if (p->fermi) DEV(lsk_amplitude_info_fermi(p->bs, p->six, gt, p->pj, B, d_states, d_reps_out, d_index, d_characters, d_norms, p->d_err, stream));
+    else DEV(lsk_amplitude_info(p->bs, p->six, gt, p->pj, B, d_states, d_reps_out, d_index, d_characters, d_norms, p->d_err, stream));
+    return 0;
+}
+
+int ls_amd_amp_orbit_states(ls_amd_amp *p, int64_t B, int64_t const *d_rows, int32_t const *d_elements, uint64_t *d_out, void *stream) {
+    char const *const who = "ls_amd_amp_orbit_states";
+    if (!p) return set_error("%s: NULL plan", who);
+    if (B < 0) return set_error("%s: a negative count of pairs (%lld)", who, (long long)B);
+    if (B == 0) return 0;
+    if (!d_rows || !d_elements || !d_out) return set_error("%s: NULL %s", who, !d_rows ? "rows" : (!d_elements ? "elements" : "out"));
+    if (p->fermi) DEV(lsk_orbit_image_fermi(p->bs, p->n, p->d_reps, B, d_rows, d_elements, d_out, p->d_err, stream));
+    else DEV(lsk_orbit_image(p->bs, p->n, p->d_reps, B, d_rows, d_elements, d_out, p->d_err, stream));
+    return 0;
+}
+
+int ls_amd_amp_check(ls_amd_amp *p, void *stream) {
+    if (!p) return set_error("ls_amd_amp_check: NULL plan");
+    int flag[2] = {0, 0}, zero[2] = {0, 0};
+    DEV(lsk_sync(stream));
+    DEV(lsk_d2h(flag, p->d_err, sizeof(flag)));
+    if (flag[0] || flag[1]) DEV(lsk_h2d(p->d_err, zero, sizeof(zero)));
+    if (flag[0])
+        return set_error("sector amplitudes: the representative of a queried state has non-zero norm and is not in the basis (the array of "
+                         "representatives does not belong to this basis or is not the whole sector)");
+    if (flag[1])
+        return set_error("orbit states: a row outside [0, %lld) or an element outside [0, %d)", (long long)p->n, p->n_elements);
+    return 0;
+}
+
+char const *ls_amd_amp_kernel_name(ls_amd_amp const *p) {
+    if (!p) { set_error("ls_amd_amp_kernel_name: NULL plan"); return NULL; }
+    return p->fermi ? lsk_amplitude_fermi_kernel_name() : lsk_amplitude_kernel_name();
+}
+
+/* ============================================================================================ */
 /* two-point correlation matrices (include/ls_amd.h: ls_amd_corr; csrc/k_corr.hip) */
 /* ============================================================================================ */
 /* The device sums over the representatives alone (the RAW matrices); C[i][j] = |G|^-1 sum_g R[g(i)][g(j)] over the whole group is

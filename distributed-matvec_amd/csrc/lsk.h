@@ -746,6 +746,34 @@ int lsk_project_pull(lsk_basis bs, lsk_project pj, uint64_t const *d_binom, int 
 int lsk_project_pull_fermi(lsk_basis bs, lsk_project pj, uint64_t const *d_binom, int cplx, int64_t n, uint64_t const *reps,
                            double const *norms, void const *phi, void *out, int *d_err, void *stream);
 
+/* amplitudes of sector states on a batch of product states, and orbit images (k_amplitude.hip, k_amplitude_fermi.hip on
+ * k_amplitude_t.hpp).  For the B words states[0, B), in any order, duplicates allowed, and the K columns of psi,
+ *     out[j, c] = conj(character(s_j)) n(rep_j) psi[index(rep_j), c]        (state_info(s_j) = (rep_j, character, n); signed on
+ *                                                                            projected fermionic bases; psi[index(s_j), c] unprojected)
+ * and 0 for a word that is no state of the basis without symmetries (pj.kind and its numbers: the membership of lsk_project; pj.full is
+ * not read) or lies on a zero-norm orbit.  index: gt (projected bases: the static index table of the array) or six (unprojected).
+ * psi[i, c] = psi[i * pj.phi_s0 + c * pj.phi_s1], out[j, c] = out[j * pj.out_s0 + c * pj.out_s1] in ELEMENTS of the dtype, K = pj.K.
+ * Plain stores; d_err[0] is raised by a representative inside the conserved numbers that is missing from the array (it reads 0).
+ * _info: the same stages without psi -- rep, index (-1 where the amplitude reads 0), character (re, im: 2 B doubles) and n per state;
+ * any output may be NULL.  lsk_orbit_image: out[j] = g_e reps[rows[j]], e = elements[j] over the effective group (spin inversion:
+ * element 2 p = permutation p, 2 p + 1 = permutation p then ^ site_mask); d_err[1] is raised by a row or element out of range (out 0).
+ * The _fermi forms take projected fermionic bases (bs.fermi), the plain ones every other basis. */
+#define LSK_AMP_COLS 8 /* columns per chunk of k_amplitude_pull */
+char const *lsk_amplitude_kernel_name(void);
+char const *lsk_amplitude_fermi_kernel_name(void);
+int lsk_amplitude_pull(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_project pj, int cplx, int64_t B, uint64_t const *states,
+                       void const *psi, void *out, int *d_err, void *stream);
+int lsk_amplitude_pull_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_project pj, int cplx, int64_t B, uint64_t const *states,
+                             void const *psi, void *out, int *d_err, void *stream);
+int lsk_amplitude_info(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_project pj, int64_t B, uint64_t const *states, uint64_t *reps_out,
+                       int64_t *index, double *characters, double *norms, int *d_err, void *stream);
+int lsk_amplitude_info_fermi(lsk_basis bs, lsk_index six, lsk_gtab gt, lsk_project pj, int64_t B, uint64_t const *states,
+                             uint64_t *reps_out, int64_t *index, double *characters, double *norms, int *d_err, void *stream);
+int lsk_orbit_image(lsk_basis bs, int64_t n, uint64_t const *reps, int64_t B, int64_t const *rows, int32_t const *elements, uint64_t *out,
+                    int *d_err, void *stream);
+int lsk_orbit_image_fermi(lsk_basis bs, int64_t n, uint64_t const *reps, int64_t B, int64_t const *rows, int32_t const *elements,
+                          uint64_t *out, int *d_err, void *stream);
+
 /* two-point correlation matrices of a sector state (k_corr.hip, k_corr_fermi.hip): sums over the
  * representatives reps[0, n) alone -- the host averages them over the group afterwards.  A pair is the 16-bit word i | j << 8 of
  * two bits of the state word.  Both routines reduce in two steps without floating-point atomics: one partial per (block, pair) in

@@ -20,10 +20,12 @@ from .evolve import (EvolveResult, ThermalCorrelationResult, ThermalExpectationR
                      thermal_expectation)
 from . import projection  # noqa: E402
 from .projection import SectorProjection, product_state, project  # noqa: F401,E402
+from . import sampling  # noqa: E402
+from .sampling import SectorAmplitudes, amplitudes, sample_states, snapshots  # noqa: F401,E402
 from . import kpm  # noqa: E402
 from .kpm import (KpmMatrixResult, block_gram, chebyshev_moment_matrices, cross_correlation, greens_matrix,  # noqa: F401,E402
                   moment_matrices_from_grams, reconstruct_matrix, spectral_matrix)
 
 _kpm_matrix = ["KpmMatrixResult", "block_gram", "chebyshev_moment_matrices", "cross_correlation", "greens_matrix",
                "moment_matrices_from_grams", "reconstruct_matrix", "spectral_matrix"]
-__all__ = _kpm_matrix + list(_api.__all__) + list(_entanglement.__all__) + list(projection.__all__) +[n for n in correlations.__all__ if n != "correlations"] + [n for n in expectation.__all__ if n != "expectation"] + [n for n in evolve.__all__ if n != "evolve"]
+__all__ = _kpm_matrix + list(_api.__all__) + list(_entanglement.__all__) + list(projection.__all__) + list(sampling.__all__) + [n for n in correlations.__all__ if n != "correlations"] + [n for n in expectation.__all__ if n != "expectation"] + [n for n in evolve.__all__ if n != "evolve"]

@@ -773,6 +773,47 @@ int64_t ls_amd_test_project_full_size(ls_hs_basis const *basis);
  * a message that names why the word is no state of the basis (bits above the sites / modes, another weight or particle numbers) */
 int64_t ls_amd_test_project_state_index(ls_hs_basis const *basis, uint64_t state);
 
+/* ---- amplitudes of sector states on product states, and orbit images (csrc/k_amplitude.hip, k_amplitude_fermi.hip) ----
+ * The value of a sector state on a BATCH of product states, without the full-basis vector of the expansion: with state_info(s) =
+ * (rep, character, norm) of a word s of the basis without symmetries,
+ *     <s|psi> = conj(character(s)) norm(rep) psi[index(rep)]
+ * (the character carries the orbit sign on a projected fermionic basis; psi[index(s)] on an unprojected basis).  The B words may come
+ * in any order, with duplicates.  A word that is no state of the basis without symmetries -- a bit above the sites, another Hamming
+ * weight or particle number, another (N_up, N_down) split -- and a word on an orbit of zero norm read 0 in every column: no error (the
+ * rule of ls_amd_expect for images that leave the conserved numbers).  A representative inside the conserved numbers that is missing
+ * from d_reps raises the plan's flag, which ls_amd_amp_check reports ("... not in the basis ...").  k_amplitude_pull (k_amplitude_pull_fermi
+ * on projected fermionic bases): one state per lane; projection and look-up once per state whatever K; plain stores, so two calls
+ * return the same bytes.  One partition.  The inverse direction, for Born sampling: Sum_{s in orbit(r)} |<s|psi>|^2 = |psi_r|^2 and a
+ * uniform element of the effective group maps r uniformly onto its orbit, so drawing a row with probability |psi_r|^2 and an element
+ * uniformly samples |<s|psi>|^2 exactly; ls_amd_amp_orbit_states applies the elements (k_orbit_image). */
+typedef struct ls_amd_amp ls_amd_amp;
+/* d_reps: the n ascending representatives of `basis` in HBM (borrowed until ls_amd_amp_destroy).  Builds the look-up of the array: the
+ * static index table of a projected basis (shared with the matvec plans over the same array), a closed form or a searched index
+ * otherwise.  Refuses by name: NULL arguments, a negative count, >= 2^32 - 1 rows, projected fermionic bases above 60 modes. */
+int ls_amd_amp_create(ls_amd_amp **out, ls_hs_basis const *basis, uint64_t const *d_reps, int64_t n, void *stream);
+int ls_amd_amp_num_elements(ls_amd_amp const *plan); /* effective group order, inversion / flip included */
+/* out[j, c] = <s_j|psi_c> for the B words d_states and the K columns of psi (n rows): psi[i, c] = psi[i * psi_row + c * psi_col],
+ * out[j, c] = out[j * out_row + c * out_col] in ELEMENTS of the dtype, 1 <= K <= 64.  LS_AMD_F64 needs +-1 characters.  Refuses strides
+ * that make two elements of out share storage, and an out that overlaps psi.  B = 0 is a no-op. */
+int ls_amd_amp_amplitudes(ls_amd_amp *plan, ls_amd_dtype dtype, int K, int64_t B, uint64_t const *d_states, void const *d_psi,
+                          int64_t psi_row, int64_t psi_col, void *d_out, int64_t out_row, int64_t out_col, void *stream);
+/* the device-pointer form of ls_hs_state_info + ls_hs_state_index: representative, row (-1 for a word outside the basis, on a zero-norm
+ * orbit, or whose representative is missing), character (re, im: 2 B doubles; with the orbit sign on projected fermionic bases, as in
+ * ls_hs.h) and norm of every word.  A word outside the basis reports itself, character 0 and norm 0.  Any output may be NULL. */
+int ls_amd_amp_state_info(ls_amd_amp *plan, int64_t B, uint64_t const *d_states, uint64_t *d_reps_out, int64_t *d_index,
+                          double *d_characters /* 2B */, double *d_norms, void *stream);
+/* out[j] = g_e reps[rows[j]], e = elements[j] in [0, ls_amd_amp_num_elements): on a spin basis with the global inversion element 2 p is
+ * permutation p and 2 p + 1 is permutation p followed by the flip of every site; every other basis uses its own element list (the up <->
+ * down flip of a spinful basis is among its elements).  A row or element out of range raises the flag (and stores 0). */
+int ls_amd_amp_orbit_states(ls_amd_amp *plan, int64_t B, int64_t const *d_rows, int32_t const *d_elements, uint64_t *d_out, void *stream);
+/* synchronises the stream; -1 with a message if a kernel since the last check raised the flag (then cleared) */
+int ls_amd_amp_check(ls_amd_amp *plan, void *stream);
+char const *ls_amd_amp_kernel_name(ls_amd_amp const *plan); /* "k_amplitude_pull" / "k_amplitude_pull_fermi" */
+void ls_amd_amp_destroy(ls_amd_amp *plan);
+/* host only, no device: the image of `state` under element `element` in the numbering of ls_amd_amp_orbit_states; *ok = 0 with a message
+ * for an element out of range or a word with bits above the sites */
+uint64_t ls_amd_test_orbit_state(ls_hs_basis const *basis, uint64_t state, int element, int *ok);
+
 /* ---- two-point correlation matrices of a sector state (csrc/k_corr.hip, k_corr_fermi.hip) ---------------
  * For a NORMALISED state psi on the n representatives of `basis` (projected or not), over the M bits of a state word (the sites
  * of a spin or spinless basis; the 2 L modes of a spinful one, mode (i, up) = bit i, mode (i, down) = bit i + L):
