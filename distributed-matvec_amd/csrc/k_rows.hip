@@ -671,8 +671,8 @@ extern "C" int lsk_direct_gx(lsk_operator op, lsk_basis bs, lsk_index ix, int cp
 // site bits are 01 are one contiguous range R01 and those with 10 the next one, both D = C(L-2, k-1) rows long, and bond L - 2 maps
 // row R01 + j onto row R01 + D + j.  A paired tile is 512 rows of R01 and their 512 partners: both are in the block's LDS anyway, so
 // that bond's partner is the row's own place in the other segment's core -- one LDS read instead of a far gather that always
-// misses the L2 (51.6 % of the rows of chain_32 have it).  LDS stays what it was: two windows of 512 + 2 x 256 (+ 2) rows are 2052
-// rows against 2050, the halo of 256 serves pairs 0..10, and pair 11 (partners up to 462 rows away) reads LDS when every partner of
+// misses the L2 (51.6 % of the rows of chain_32 have it).  LDS stays what it was: two windows of 512 + 2 x 256 rows are the 2048
+// rows of the one window of 1024 + 2 x 512, the halo of 256 serves pairs 0..10, and pair 11 (partners up to 462 rows away) reads LDS when every partner of
 // the wave-row lies inside the window -- the rows of a wave move together, about half of the wave-rows -- and gathers otherwise (L1 /
 // L2 hits mostly).  The second segments lie off the 64-row grid of the wave headers (D mod 64 = 16 on chain_32) and have headers
 // of their own, made from their first row on.  The rows outside the whole 512-row segments of R01 and their partners stay with
@@ -718,6 +718,29 @@ constexpr int kChainFarC = 6; // complex: 6 x 16 bytes in flight per lane
 // in hdr_b; bits 59..63 = the range's bond.  hdr_b = the wave headers of all second segments (two u32 per 64 rows, each range's made
 // from its second segments' first row on, range after range)
 struct chain_pair_args { uint32_t const *hdr_b; };
+// The LDS window of a tile (of each of the two segments of a paired tile): core + 2 x halo rows of x from an even row on, in all
+// 2048 f64 rows or 1024 c128 elements, i.e. exactly four 16-byte loads per thread.  The core starts HALO or HALO + 1 rows in and the
+// pairs below LDSP reach at most HALO - 1 rows (C(11, 5) = 462 < 512, C(10, 5) = 252 < 256), so no row reads past its window.
+template <bool CPLX, int TILE, bool PAIR> struct ChainWindow {
+    static constexpr int HALO = (CPLX || PAIR) ? 256 : kChainHalo;          // rows of x before and after the core
+    static constexpr int LDSP = (CPLX || PAIR) ? 11 : kChainLdsPairs;       // pairs below this one are served from the window
+    static constexpr int CORE = PAIR ? TILE / 2 : TILE;                     // the tile's own rows in one window
+    static constexpr int ROWS = CORE + 2 * HALO;                            // one window
+    static constexpr int WINDOW = PAIR ? 2 * ROWS : ROWS;                   // s_x: the windows one after the other
+    // The windows of the tile whose (first segment's) first row is row `first` of x (and whose second segment's is `first_b`): w0 /
+    // w0b = their first rows (even; may be < 0).  Returns "interior": every row of every window lies in [0, n_x), i.e. the unchecked
+    // prologue, which loads exactly [w0, w0 + ROWS) (and [w0b, w0b + ROWS)) in 16-byte pieces, reads inside x.
+    __host__ __device__ static __forceinline__ bool place(int64_t first, int64_t first_b, int64_t n_x, int64_t &w0, int64_t &w0b) {
+        w0 = (first - HALO) & ~(int64_t)1;
+        w0b = PAIR ? (first_b - HALO) & ~(int64_t)1 : 0;
+        return w0 >= 0 && w0 + ROWS <= n_x && (!PAIR || (w0b >= 0 && w0b + ROWS <= n_x));
+    }
+};
+// 16 bytes per lane from global memory straight into LDS (no register in between, nothing to wait for before the next one goes out):
+// lane l of the wave writes lds + 16 l, `lds` being the same for the whole wave
+__device__ __forceinline__ void chain_stage16(void const *src, void *lds) {
+    __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void *)const_cast<void *>(src), (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
+}
 template <typename W, typename R, bool CPLX, int TILE, bool REC, bool PAIR>
 __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk_term const *__restrict__ diag,
                                                     int hamming_weight, uint4 const *__restrict__ g_img, int img16, int kc,
@@ -734,12 +757,15 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
     // complex vectors: 11 LDS pairs and a 256-row halo (>= C(10, 5)) keep the block at 20.7 KB like the f64 one, i.e. more
     // resident blocks per CU; pair 11 then gathers from global memory (its partners are <= 462 rows away: L1 / L2 hits)
     // PAIR (f64 on fused records only): a tile is two segments of SEG rows, D rows apart, each with a 256-row halo; the two windows
-    // lie one after the other in s_x (WSEG rows each, 2052 in all against 2050), and pair 11 gathers as in the complex kernel
-    constexpr int HALO = (CPLX || PAIR) ? 256 : kChainHalo;
-    constexpr int LDSP = (CPLX || PAIR) ? 11 : kChainLdsPairs;
+    // lie one after the other in s_x (WSEG rows each, 2048 in all like the one window), and pair 11 gathers as in the complex kernel
+    typedef ChainWindow<CPLX, TILE, PAIR> CW;
+    constexpr int LDSP = CW::LDSP;
     constexpr int SEG = TILE / 2;
-    constexpr int WSEG = SEG + 2 * HALO + 2;
-    constexpr int WINDOW = PAIR ? 2 * WSEG : TILE + 2 * HALO + 2;
+    constexpr int WSEG = CW::ROWS; // (paired tiles: one segment's window)
+    constexpr int WINDOW = CW::WINDOW;
+    constexpr int PASS = kBlock * (int)(16 / sizeof(typename ChainX<CPLX>::type)); // rows per pass of the block
+    constexpr int NPASS = WINDOW / PASS;
+    static_assert(WINDOW % PASS == 0 && NPASS == 4 && (!PAIR || WSEG % PASS == 0), "a window is four whole passes of the block");
     static_assert(!PAIR || (REC && !CPLX && SEG % kBlock == 0 && SEG % 64 == 0), "paired tiles: f64 on fused records");
     constexpr int FAR = CPLX ? kChainFarC : kChainFar;
     constexpr R kNone = ~(R)0;
@@ -759,9 +785,15 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
     R const *const s_binom = reinterpret_cast<R const *>(s_img);
     uint2 const *const s_near = reinterpret_cast<uint2 const *>(reinterpret_cast<char const *>(s_img) + near_off);
     __shared__ X s_x[WINDOW + 1]; // last slot: 0, read by the lanes whose near pair is aligned
-    for (int k = threadIdx.x; k < img16; k += kBlock) s_img[k] = g_img[k];
     (void)NB;
     if (threadIdx.x == 0) s_x[WINDOW] = cx_zero<X>();
+    // Tile prologue: the image, the wave headers and the whole window are requested before anything is waited for -- one round trip to
+    // memory instead of one per pass (a window was five dependent passes of load, wait, LDS write; the image two more).  Image and
+    // interior windows go straight into LDS, 16 bytes per lane (chain_stage16; a lane past the image's end is switched off and writes
+    // nothing); a window that touches either end of x, or an x that is not 16-byte aligned (a view one element into a tensor), keeps
+    // the checked loads.  Both tests are block-uniform.
+    for (int k0 = (int)(threadIdx.x & ~63u); k0 < img16; k0 += kBlock)
+        if (k0 + (int)(threadIdx.x & 63u) < img16) chain_stage16(g_img + k0 + (threadIdx.x & 63u), s_img + k0);
     const int xcd = blockIdx.x & 7;
     const int64_t blocks_per_xcd = gridDim.x >> 3;
     const int lane = threadIdx.x & 63;
@@ -783,7 +815,10 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
         // (fused records: bits 59..63 of an entry are flags, kChainTilePlain = this tile starts or ends off the 64-row grid of the
         // wave headers and runs on its records; a paired tile is always whole)
         const int cnt_slot = REC ? (int)((slot >> 48) & 0x7ffu) : (int)(slot >> 48);
-        if (cnt_slot == 0) continue; // block-uniform
+        if (cnt_slot == 0) { // block-uniform
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the image is on its way into LDS: a block without a tile does not end before it is there)
+            continue;
+        }
         const int cnt = PAIR ? TILE : cnt_slot;
         const int64_t i0 = (int64_t)(slot & (PAIR ? 0xffffffffULL : 0xffffffffffffULL)); // (paired tiles: bits 32..47 = the range)
         // (paired tiles: the tile's range -- block-uniform, scalar loads)
@@ -791,8 +826,12 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
         const int64_t pr_d = PAIR ? (int64_t)(uint32_t)slot1 : 0;
         const uint32_t pr_hdr = PAIR ? (uint32_t)(slot1 >> 32) & 0x7ffffffu : 0u;
         const int pr_bond = PAIR ? (int)(slot1 >> 59) : -1;
-        const int64_t w0 = (row0 + i0 - HALO) & ~(int64_t)1; // first row of the window (even; may be < 0)
-        const int64_t w0b = PAIR ? (i0 + pr_d - HALO) & ~(int64_t)1 : 0; // (paired tiles: of the second segment's window)
+        int64_t w0, w0b; // first row of the window (even; may be < 0); paired tiles: of the second segment's window too
+        // (the alignment of x is taken here, tile by tile, from a copy the optimizer cannot see through: hoisted out of the tile loop
+        // it is one more value held in scalar registers for the whole kernel, which has none to spare at 7 blocks per CU)
+        uint32_t x_low = (uint32_t)reinterpret_cast<uintptr_t>(x_v);
+        asm volatile("" : "+s"(x_low));
+        const bool interior = CW::place(row0 + i0, i0 + pr_d, n_x, w0, w0b) && (x_low & 15u) == 0;
         // row of the tile that this thread works on in iteration s, as an offset from i0
         auto row_off = [&](int s) -> int { return PAIR ? (s >> 1) * (int)pr_d + (s & 1) * kBlock + (int)threadIdx.x : s * kBlock + threadIdx.x; };
         W a_next = 0;
@@ -838,27 +877,42 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
             }
             load_row(row, a_next, t0_next, t1_next);
         };
-        if (wave0 < cnt) { // first row of this thread: requested before the window is staged
+        // (the thread's number as a copy the optimizer cannot see through: the addresses made from it below, hoisted out of the tile
+        // loop, are registers held for the whole kernel, which then spills)
+        int tid = (int)threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        if (interior) {
+            // pass u of wave w: rows PASS u + 128 w (c128: 64 w) of the window onwards, lane after lane -- the image in s_x is the
+            // one the checked loads below make; a paired tile's passes 2 and 3 are the second segment's window (the source address)
+#pragma unroll
+            for (int u = 0; u < NPASS; ++u) {
+                const int64_t first = (PAIR && u * PASS >= WSEG) ? w0b + (u * PASS - WSEG) : w0 + u * PASS; // (block-uniform)
+                chain_stage16(x + first + (PASS / kBlock) * tid, reinterpret_cast<char *>(s_x) + 16 * (u * kBlock + (tid & ~63)));
+            }
+        } else { // (a tile at either end of x, or an unaligned x: pass after pass, each load checked)
+            if (CPLX) {
+                for (int j = tid; j < WINDOW; j += kBlock) {
+                    const int64_t row = w0 + j;
+                    s_x[j] = (row >= 0 && row < n_x) ? x[row] : cx_zero<X>();
+                }
+            } else {
+                double const *xd = (double const *)x_v;
+                double *sd = (double *)s_x;
+                for (int j = 2 * tid; j < WINDOW; j += 2 * kBlock) {
+                    const int64_t row = (PAIR && j >= WSEG) ? w0b + (j - WSEG) : w0 + j; // (WSEG is even: a pair of rows stays in its window)
+                    double2 v;
+                    if (row >= 0 && row + 1 < n_x) v = *reinterpret_cast<double2 const *>(xd + row);
+                    else { v.x = (row >= 0 && row < n_x) ? xd[row] : 0.0; v.y = (row + 1 >= 0 && row + 1 < n_x) ? xd[row + 1] : 0.0; }
+                    sd[j] = v.x;
+                    sd[j + 1] = v.y;
+                }
+            }
+        }
+        // the one wait of the prologue: headers, image and window have arrived in this wave (the barrier below: in every wave)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (wave0 < cnt) { // first row of this thread: its word comes from the header just waited for
             const int64_t rr = i0 + ((int)threadIdx.x < cnt ? (int)threadIdx.x : cnt - 1);
             fetch_row(0, rr);
-        }
-        __syncthreads(); // every wave is done with the previous window (and s_binom is loaded)
-        if (CPLX) {
-            for (int j = threadIdx.x; j < WINDOW; j += kBlock) {
-                const int64_t row = w0 + j;
-                s_x[j] = (row >= 0 && row < n_x) ? x[row] : cx_zero<X>();
-            }
-        } else {
-            double const *xd = (double const *)x_v;
-            double *sd = (double *)s_x;
-            for (int j = 2 * threadIdx.x; j < WINDOW; j += 2 * kBlock) {
-                const int64_t row = (PAIR && j >= WSEG) ? w0b + (j - WSEG) : w0 + j; // (WSEG is even: a pair of rows stays in its window)
-                double2 v;
-                if (row >= 0 && row + 1 < n_x) v = *reinterpret_cast<double2 const *>(xd + row);
-                else { v.x = (row >= 0 && row < n_x) ? xd[row] : 0.0; v.y = (row + 1 >= 0 && row + 1 < n_x) ? xd[row + 1] : 0.0; }
-                sd[j] = v.x;
-                sd[j + 1] = v.y;
-            }
         }
         __syncthreads();
         const int own0 = (int)(row0 + i0 - w0);
@@ -1067,6 +1121,7 @@ __device__ __forceinline__ void chain_rows(lsk_runs const &runs, int n_diag, lsk
             r_pending = ghost ? -1 : r;
         }
         if (r_pending >= 0) cx_store_nt(y + i0 + r_pending, y_pending);
+        if (t + blocks_per_xcd < slots_per_xcd) __syncthreads(); // (a launch of fewer blocks than tiles: every wave is done with this window)
     }
 }
 template <typename W, typename R, bool CPLX, int TILE, bool REC>
@@ -1304,6 +1359,23 @@ static int launch_chain(lsk_operator op, lsk_basis bs, lsk_index ix, lsk_tilemap
 // rows per tile: 1024 (f64) / 512 (c128).  Measured r2 on chain_32: doubling them (fewer blocks, 1.5x instead of 2x window
 // loads, but 5 instead of 7 blocks per CU) is slower, 8.72 vs 8.26 ms (f64), 15.5 vs 15.4 ms (c128).
 extern "C" int lsk_chain_tile_rows(int cplx) { return cplx ? 512 : 1024; }
+
+// host test hook: the LDS windows of one tile as the kernels place them (ChainWindow<>::place, the function they call).  kind 0 = f64
+// tile, 1 = c128 tile, 2 = paired f64 tile; first = the tile's first row in x (row0 + its first local row), first_b = the first row of
+// a paired tile's second segment.  out[0..1] = first row of the windows in x (may be < 0), out[2] = rows of one window, out[3] =
+// windows, out[4] = rows of a tile in one window, out[5] = halo, out[6] = pairs served from the window.  Returns 1 when the tile is
+// interior (the prologue loads out[2] rows from out[0] -- and from out[1] -- on without a check), 0 when not, -1: no such kind.
+template <typename CW> static int chain_tile_windows(int64_t first, int64_t first_b, int64_t n_x, int windows, int64_t *out) {
+    const bool interior = CW::place(first, first_b, n_x, out[0], out[1]);
+    out[2] = CW::ROWS; out[3] = windows; out[4] = CW::CORE; out[5] = CW::HALO; out[6] = CW::LDSP;
+    return interior ? 1 : 0;
+}
+extern "C" int ls_amd_test_chain_tile_windows(int kind, int64_t first, int64_t first_b, int64_t n_x, int64_t *out) {
+    if (kind == 0) return chain_tile_windows<ChainWindow<false, 1024, false>>(first, first_b, n_x, 1, out);
+    if (kind == 1) return chain_tile_windows<ChainWindow<true, 512, false>>(first, first_b, n_x, 1, out);
+    if (kind == 2) return chain_tile_windows<ChainWindow<false, 1024, true>>(first, first_b, n_x, 2, out);
+    return -1;
+}
 
 extern "C" int lsk_chain(lsk_operator op, lsk_basis bs, lsk_index ix, int cplx, int wide_ranks, int fused_records, lsk_tilemap tm,
                          int64_t n, uint64_t const *reps, int64_t row0, int64_t n_x, void const *x, void *y, int n_cached,

@@ -971,6 +971,12 @@ int ls_amd_test_nw_find(uint64_t const *reps, int n, uint64_t key);
 /* Host-only test hook: the near-pair table of the staged row kernel (distributed-matvec_amd/csrc/k_rows.hip: chain_lds_image) for
  * vectors of `elem` bytes per entry and `ldsp` pairs served from the LDS window: 480 entries of four int16 into `out`. */
 int ls_amd_test_chain_near_table(int elem, int ldsp, int16_t *out);
+/* Host-only test hook: the LDS windows of one tile of the staged row kernel, placed by the function the kernels call (k_rows.hip:
+ * ChainWindow).  kind 0 = f64 tile, 1 = c128 tile, 2 = paired f64 tile; first = the tile's first row in x, first_b = that of a paired
+ * tile's second segment.  out[0..1] = first row of the windows (may be < 0), out[2] = rows of one window, out[3] = windows, out[4] =
+ * the tile's rows in one window, out[5] = halo, out[6] = pairs served from the window.  Returns 1 when the tile is interior -- the
+ * prologue loads every window whole, without a bounds check --, 0 when it keeps the checked loads, -1 on an unknown kind. */
+int ls_amd_test_chain_tile_windows(int kind, int64_t first, int64_t first_b, int64_t n_x, int64_t *out);
 /* Host-only test hook: the word tables behind the wave headers of the staged row kernel (host.c: chain_wave_tables).  U[4096]: the
  * 12-bit words grouped by weight, ascending inside each weight, class k starting at class_off[k] (14 entries, the last 4096);
  * Rg[4096]: Rg[w] = rank of w ^ (1 << low_site) inside its own weight class (low_site < 12; < 0: all zero). */
